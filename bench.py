@@ -8,7 +8,15 @@ all kernels hand-written HIP (kinet_amd).  One step = one detection forward over
 of `--batch` frames per GPU whose pixels are already resident in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload config2|config3|config5]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (driver)
+
+A run without `--full` sets up, warms up, times the K steps and prints the headline line (metric,
+value, unit, ms_per_step, dtype, config, ...).  `--full` adds what takes runs of its own: the
+HIP-event roofline pass (MSDA HBM / MFMA rooflines, per-family device time), the config-3 and
+config-5 sub-benchmarks, the config-4 `train` sub-object, the CPU baseline and the detail record.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (dump_outputs);
+inputs and weights are seeded, so two builds can be compared output for output.
 
 `--workload config5` (BASELINE.json configs[4], cfgs/train_full_res.yaml): ResNet-101,
 d=288 (head_dim 36), 500 object + 20 track queries, separate per-frame encoders and an
@@ -120,6 +128,14 @@ def parse():
     ap.add_argument('--detail', default=None,
                     help='where the full JSON record goes (default gpurun_out/bench_detail.json); stdout '
                          'carries the compact line')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline figure: the HIP-event roofline pass, the config-3 / '
+                         'config-5 sub-benchmarks, the config-4 train leg, the CPU baseline and the detail record '
+                         '(each still switched off by its own --no-* option).  Without it a run sets up, warms up, '
+                         'times --steps steps and prints the headline line')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy '
+                         '(float32; outputs over the size budget as a fixed seeded sample of their elements)')
     ap.add_argument('--cpu-stub', action='store_true',
                     help='tests only: run the launch/timing skeleton with a tiny CPU model over gloo')
     a = ap.parse_args()
@@ -462,10 +478,57 @@ def train_leg(a, dev, world):
             dist.destroy_process_group()
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # array data per --dump-outputs directory
+
+
+def _named_tensors(x, name, acc):
+    """The tensors of a forward's return value (tuples / lists / dicts / NestedTensors), with dotted names."""
+    if torch.is_tensor(x):
+        acc.append((name, x))
+    elif isinstance(x, dict):
+        for k, v in x.items():
+            _named_tensors(v, f'{name}.{k}', acc)
+    elif isinstance(x, (list, tuple)):
+        for i, v in enumerate(x):
+            _named_tensors(v, f'{name}.{i}', acc)
+    elif hasattr(x, 'tensors'):
+        _named_tensors(x.tensors, name, acc)
+    return acc
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: every tensor the forward returned (predictions, aux outputs, backbone features,
+    encoder memory, decoder states; a tracking step's targets too), one DIR/<name>.npy each, float32
+    (float64 stays).  The budget is shared smallest first: an output within its share is written whole,
+    a larger one as the elements at sorted torch.randint(numel) indices of a CPU generator seeded 0 --
+    the same elements for the same shape in every run and every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    items = []
+    for n, o in zip(('out', 'targets', 'features_all', 'memory_slices', 'hs'), out):
+        _named_tensors(o, n, items)
+
+    def size(t):
+        return t.numel() * (8 if t.dtype == torch.float64 else 4)
+    items.sort(key=lambda it: size(it[1]))
+    left = DUMP_BUDGET_BYTES
+    for i, (n, t) in enumerate(items):
+        share = left // (len(items) - i)
+        if size(t) > share:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (share // (size(t) // t.numel()),), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        t = t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu()
+        left -= size(t)
+        np.save(os.path.join(path, n + '.npy'), t.numpy())
+
+
 def run_workload(a, name, dev, world, rank, batch, streams, height, width, dtype_name, steps, warmup):
-    """Time `steps` forwards of workload `name` (WORKLOADS) after `warmup`, then trace 3 more on
-    one stream.  Returns (elapsed seconds (max over ranks), trace families, MSDA launches,
-    GEMM/conv roofline split, decoder touched bytes).  With one batch in flight the library's
+    """Time `steps` forwards of workload `name` (WORKLOADS) after `warmup`, then (--full) trace 3
+    more on one stream.  Returns (elapsed seconds (max over ranks), trace families, MSDA launches,
+    GEMM/conv roofline split, decoder touched bytes), the last four None without --full.  With
+    --dump-outputs the headline workload's last timed step is written out (dump_outputs) before
+    the trace.  With one batch in flight the library's
     launch-fill policy is "solo" (kinet_set_solo_launch: partial-round shapes on smaller tiles)."""
     from kinet_amd import _native
     old = _native.lib().kinet_set_solo_launch(1 if max(1, streams) == 1 else 0)
@@ -586,11 +649,16 @@ def _run_workload(a, name, dev, world, rank, batch, streams, height, width, dtyp
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     assert torch.isfinite(out[0]['pred_boxes']).all()
+    if a.dump_outputs and rank == 0 and name == a.workload:
+        dump_outputs(out, a.dump_outputs)
     del out
     if graphed:
         del graphs, gouts
     run_workload.graphed[name] = graphed
     run_workload.graph_check[name] = graph_check
+    if not a.full:   # the headline figure needs nothing below
+        del model, batches, extra
+        return elapsed, None, None, None, None
 
     # roofline pass: HIP events around every launch of 3 more steps, one stream (the traced
     # kernel durations must not overlap)
@@ -790,6 +858,25 @@ def compact_line(full, detail_path):
     return line
 
 
+def headline(a, wl, world, elapsed):
+    """The headline keys of the result line: all a run without --full prints, and the head of the
+    --full record."""
+    return {
+        'metric': 'frames/sec (3x800x1333, 300 obj+track queries) at 1/2/4/8 GPUs; MSDeformAttn ms/call',
+        'value': a.batch * a.steps * world / elapsed, 'unit': 'frames/s', 'n_gpus': world, 'world_size': world,
+        'steps': a.steps, 'warmup': a.warmup,
+        'ms_per_step': elapsed / a.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
+        'vs_baseline': None, 'dtype': a.dtype,
+        'data': 'synthetic N(0,1) 3x%dx%d frames, random-init weights (reference init)' % (a.height, a.width),
+        'config': {'workload': wl['desc'],
+                   'frames_per_gpu_per_step': a.batch, 'in_flight_batches': max(1, a.streams),
+                   'frame': [3, a.height, a.width],
+                   'launch': 'HIP graph replay per in-flight slot' if run_workload.graphed.get(a.workload)
+                             else 'eager',
+                   'graph_check': run_workload.graph_check.get(a.workload),
+                   'parallelism': f'replicas x{world}'}}
+
+
 def main():
     a = parse()
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -816,6 +903,12 @@ def main():
     BB.STEM_FROM_IMAGE = bool(a.stem_image)
     elapsed, fam, msda, split, dec_touched = run_workload(a, a.workload, dev, world, rank, a.batch, a.streams,
                                                           a.height, a.width, a.dtype, a.steps, a.warmup)
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(headline(a, wl, world, elapsed), separators=(',', ':')))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # config 5 (BASELINE configs[4], the HBM-stress MSDA case) beside the headline: a short
     # timed run of its own workload with its own MSDA roofline (not part of `value`)
@@ -860,8 +953,6 @@ def main():
         cpu = cpu_baseline(a.cpu_seconds)
 
     if rank == 0:
-        frames_total = a.batch * a.steps * world
-        value = frames_total / elapsed
         dt_name = a.dtype
         mfma_ms = sum(fam[f]['ms'] for f in ('gemm', 'conv') if f in fam)
         mfma_flops = sum(fam[f]['flops'] for f in ('gemm', 'conv') if f in fam)
@@ -881,20 +972,8 @@ def main():
                      'device_ms_per_step': mfma_ms,
                      'pmc_mfma_util': pmc_mfma_util() if a.workload == 'config2' else None}
         roofline = msda_roof or mfma_roof
-        line = {
-            'metric': 'frames/sec (3x800x1333, 300 obj+track queries) at 1/2/4/8 GPUs; MSDeformAttn ms/call',
-            'value': value, 'unit': 'frames/s', 'n_gpus': world, 'world_size': world,
-            'steps': a.steps, 'warmup': a.warmup,
-            'ms_per_step': elapsed / a.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
-            'vs_baseline': None, 'dtype': dt_name,
-            'data': 'synthetic N(0,1) 3x%dx%d frames, random-init weights (reference init)' % (a.height, a.width),
-            'config': {'workload': wl['desc'],
-                       'frames_per_gpu_per_step': a.batch, 'in_flight_batches': max(1, a.streams),
-                       'frame': [3, a.height, a.width],
-                       'launch': 'HIP graph replay per in-flight slot' if run_workload.graphed.get(a.workload)
-                                 else 'eager',
-                       'graph_check': run_workload.graph_check.get(a.workload),
-                       'parallelism': f'replicas x{world}'},
+        line = headline(a, wl, world, elapsed)
+        line.update({
             'roofline': roofline,
             'roofline_mfma': mfma_roof,
             'roofline_gemm_conv_split': split,
@@ -904,7 +983,7 @@ def main():
             'config5': c5,
             'cpu_baseline': cpu,
             'train': train,
-        }
+        })
         detail = a.detail or os.path.join('gpurun_out', 'bench_detail.json')
         try:
             os.makedirs(os.path.dirname(os.path.abspath(detail)), exist_ok=True)

@@ -85,17 +85,17 @@ def test_state_dict_matches_reference(golden_dir, fixture, cfgs, over):
     assert 'bbox' in post
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/cfgs'), reason='reference configs only in the build container')
-def test_config_values_match_reference_yaml():
+def test_config_values_match_reference_yaml(golden_dir):
+    # tests/golden/cfgs/: the reference's own settings files (cfgs/train.yaml and the named ones)
     import yaml
     from kinet_amd.models.config import DEFAULTS, NAMED
-    with open('/root/reference/cfgs/train.yaml') as f:
+    with open(os.path.join(golden_dir, 'cfgs', 'train.yaml')) as f:
         base = yaml.safe_load(f)
     for k, v in DEFAULTS.items():
         if k in base:
             assert base[k] == v, k
     for name, vals in NAMED.items():
-        with open(f'/root/reference/cfgs/{name}.yaml') as f:
+        with open(os.path.join(golden_dir, 'cfgs', f'{name}.yaml')) as f:
             y = yaml.safe_load(f)
         for k, v in vals.items():
             assert y[k] == v, (name, k)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Per-kernel launch durations from a rocprofv3 kernel trace, split into ALL dispatches (what
 `--stats` averages) and ISOLATED dispatches (no other kernel running at any moment of the
-dispatch).  bench.py measures its roofline kernels with HIP events over single-stream steps, so
+dispatch).  bench.py --full measures its roofline kernels with HIP events over single-stream steps, so
 its launches are the isolated ones; the timed steps run several batches in flight on separate
 streams, where a one-workgroup-per-CU kernel shares the chip and its dispatch interval
 stretches.  This file is the cross-check between the rocprof summary and the bench line.
