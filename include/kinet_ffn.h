@@ -54,6 +54,29 @@ int kinet_bottleneck_pair(const void* X, int ldx, const void* R, const void* pac
                           const float* b1, void* Y, void* T, int M, int D, int F, int DB, int dtype,
                           kinet_stream_t stream);
 
+/* Stage 1's first pair with block 0's downsample branch folded in: the identity of layer1[0] is
+ * a 1x1 stride-1 64 -> 256 conv + FrozenBN over the block input X0 (the max-pool output), so the
+ * block output is one GEMM over the concatenated K = 64 + 64 and the 256-channel identity tensor
+ * is never written or read:
+ *   Y = relu(X (s3 W3)^T + X0 (s_ds W_ds)^T + b3ds)   (M, F)   b3ds = b3 + b_ds, summed in f32
+ *   T = relu(Y (s1 W1)^T + b1)                        (M, DB)
+ * The identity branch stays in the f32 accumulators (the unfused path rounds it to dtype first
+ * and applies s_ds in the epilogue), so outputs differ from downsample launch + pair at rounding
+ * level.
+ * kinet_bottleneck_pack_ds: f32 W3 (F, 64), W_ds (F, 64), W1 (DB, F), scales s3 (F), s_ds (F),
+ * s1 (DB) -> (64 + 64 + DB) * F elements of dtype; per 32-channel chunk the W3 fragments, then
+ * the W_ds fragments, then the W1 fragments, each row scaled before the one rounding.
+ * D = 64, F = 256, DB = 64 only (KINET_ERR_ARG otherwise); X rows of stride ldx >= 64, X0 rows
+ * of stride ldx0 >= 64 (multiples of 8); Y, T dense; every tensor below 2 GiB; b3ds (F), b1 (DB)
+ * f32; dtype KINET_BF16 / KINET_F16. */
+int kinet_bottleneck_pack_ds(const float* W3, const float* Wds, const float* W1, const float* s3,
+                             const float* sds, const float* s1, void* packed, int D, int F, int DB,
+                             int dtype, kinet_stream_t stream);
+
+int kinet_bottleneck_pair_ds(const void* X, int ldx, const void* X0, int ldx0, const void* packed,
+                             const float* b3ds, const float* b1, void* Y, void* T, int M, int D, int F,
+                             int DB, int dtype, kinet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,8 @@ _SIGS = {
     'kinet_stem_conv_image': [P, P, P, P, P, I, I, I, I, P],
     'kinet_bottleneck_pack': [P, P, P, P, P, I, I, I, I, P],
     'kinet_bottleneck_pair': [P, I, P, P, P, P, P, P, I, I, I, I, I, P],
+    'kinet_bottleneck_pack_ds': [P, P, P, P, P, P, P, I, I, I, I, P],
+    'kinet_bottleneck_pair_ds': [P, I, P, I, P, P, P, P, P, I, I, I, I, I, P],
     'kinet_layernorm': [P] * 5 + [I, I, F, I, I, P],
     'kinet_groupnorm': [P] * 4 + [I] * 5 + [F, I, P, P],
     'kinet_groupnorm_workspace': [I] * 5,

@@ -45,7 +45,8 @@ struct FfnArgs {
                // (timing only, results are garbage); 2 = the 4-wave x 32-row tile at D = 256;
                // 8 = the 8-wave x 16-row tile (default: 8 waves x 32 rows, ffn_fused_rt2_kernel);
                // 16 = kinet_bottleneck_pair at D = 64 on the LDS-ring kernel (bneck_pair_kernel);
-               // 128 / 256 = kinet_bottleneck_pair at D = 128 / 256 on 1- / 2-row-tile waves
+               // 128 / 256 = kinet_bottleneck_pair at D = 128 / 256 on 1- / 2-row-tile waves;
+               // 512 = kinet_bottleneck_pair_ds on 2-row-tile waves (bneck64_ds_kernel<T, 2>)
 };
 
 thread_local int ffn_debug = 0;   // test-only knob (kinet_ffn_set_debug), per calling thread
@@ -933,6 +934,192 @@ __global__ __launch_bounds__(WAVES * 64, 1024 / (WAVES * 64)) void bneck64_kerne
     }
 }
 
+// Stage 1's FIRST pair with block 0's downsample branch folded in (kinet_bottleneck_pair_ds):
+// the identity of block 0 is conv_ds(x0) * s_ds + b_ds, a 1x1 64 -> 256 conv over the same rows,
+// so the block output is ONE GEMM with the K dimensions concatenated,
+//   Y = relu([t2 | x0] [s3 W3 | s_ds W_ds]^T + (b3 + b_ds)),
+// and the 256-channel identity tensor is neither written nor read: per row 128 B (t2) + 128 B
+// (x0) in, 512 B (Y) + 128 B (T) out, against 1920 B for the downsample launch + the plain pair.
+// Same scheme as bneck64_kernel: weights resident in LDS (12 fragments per chunk: W3, W_ds, W1
+// = 96 KiB, one 16-wave workgroup per CU), every wave on its own 16*RT-row tile, phase A takes
+// KS steps on t2 and KS more on x0 into the same f32 accumulators (the identity branch is never
+// rounded), no residual registers.  RT = 1 loads the next tile's t2 / x0 rows at the tile start
+// into a second register set; RT = 2 (ffn_debug 512, A/B) shares each fragment read between two
+// row tiles and loads the next tile's rows after the last chunk's phase A.
+struct PairDsArgs {
+    const void* X;    // t2 (M, 64), row stride ldx
+    const void* X0;   // block input (M, 64), row stride ldx0
+    const void* W;    // kinet_bottleneck_pack_ds
+    const float* b3;  // b3 + b_ds
+    const float* b1;
+    void* Y;   // block output (M, 256), dense
+    void* T;   // next conv1 output (M, 64), dense
+    int ldx, ldx0, M;
+    int x_bytes, x0_bytes, w_bytes, y_bytes, t_bytes;
+};
+
+template <typename T, int RT>
+__global__ __launch_bounds__(1024) void bneck64_ds_kernel(const PairDsArgs p, const int ntiles) {
+    constexpr int F = 256, DB = 64, WAVES = 16, KS = 2, NT = DB / 16, KSB = DB / 32, FR = 4 * KS + NT, NCH = F / 32;
+    constexpr bool PF = RT == 1;
+    constexpr unsigned OOB = 0x80000000u;
+    __shared__ __attribute__((aligned(16))) char wl[NCH * FR * 1024];
+    __shared__ float pb3[F], pb1[DB];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = lane >> 4, c16 = lane & 15;
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.X, (short)0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.X0, (short)0, p.x0_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, (short)0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(p.Y, (short)0, p.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rt_ = __builtin_amdgcn_make_buffer_rsrc(p.T, (short)0, p.t_bytes, 0x00020000);
+    for (int i = threadIdx.x; i < F; i += WAVES * 64) pb3[i] = p.b3[i];
+    if (threadIdx.x < DB) pb1[threadIdx.x] = p.b1[threadIdx.x];
+    static_assert(NCH * FR % WAVES == 0, "whole DMA rounds");
+#pragma unroll
+    for (int k = 0; k < NCH * FR / WAVES; ++k) {
+        const int f = k * WAVES + wave;
+        dma16(rw, wl + f * 1024, (unsigned)f * 1024u + (unsigned)lane * 16u);
+    }
+    ffn_wait_vmcnt<0>();
+    __syncthreads();
+
+    const int nw = gridDim.x * WAVES;
+    int tile = blockIdx.x * WAVES + wave;
+    if (tile >= ntiles) return;
+    auto row_of = [&](int t, int rt) { return (t * RT + rt) * 16 + c16; };
+    auto load_rows = [&](int t, const __amdgpu_buffer_rsrc_t& rs, int ld, u32x4 (&dst)[RT][KS]) {
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            const int r = row_of(t, rt);
+            const bool ok = t < ntiles && r < p.M;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+                dst[rt][ks] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                            rs, ok ? ((unsigned)r * (unsigned)ld + (unsigned)(32 * ks + 8 * g)) * 2u : OOB, 0, 0));
+        }
+    };
+    const int poff = chunk_piece_off(g);
+    u32x4 xr[RT][KS], x0r[RT][KS], xn[PF ? RT : 1][KS], x0n[PF ? RT : 1][KS];
+    load_rows(tile, rx, p.ldx, xr);
+    load_rows(tile, rx0, p.ldx0, x0r);
+    // first tile landed (once per wave), as in bneck64_kernel
+    __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0)
+    for (; tile < ntiles; tile += nw) {
+        const int next = tile + nw;
+        if constexpr (PF) {
+            load_rows(next, rx, p.ldx, xn);
+            load_rows(next, rx0, p.ldx0, x0n);
+        }
+        f32x4 acc[RT][NT];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[rt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // opaque per tile: keeps the 96 weight-fragment reads in the loop
+        int woff = lane * 16;
+        asm volatile("" : "+v"(woff));
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const char* wb = wl + c * FR * 1024 + woff;
+            f32x4 h0[RT], h1[RT];
+            {
+                const f32x4 ba = *reinterpret_cast<const f32x4*>(pb3 + c * 32 + 4 * g);
+                const f32x4 bb = *reinterpret_cast<const f32x4*>(pb3 + c * 32 + 16 + 4 * g);
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) {
+                    h0[rt] = ba;
+                    h1[rt] = bb;
+                }
+            }
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {   // conv3 over t2
+                const u32x4 fa0 = *reinterpret_cast<const u32x4*>(wb + ks * 1024);
+                const u32x4 fa1 = *reinterpret_cast<const u32x4*>(wb + (KS + ks) * 1024);
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) {
+                    Mma<T>::run(h0[rt], fa0, xr[rt][ks]);
+                    Mma<T>::run(h1[rt], fa1, xr[rt][ks]);
+                }
+            }
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {   // the downsample conv over x0, same accumulators
+                const u32x4 fd0 = *reinterpret_cast<const u32x4*>(wb + (2 * KS + ks) * 1024);
+                const u32x4 fd1 = *reinterpret_cast<const u32x4*>(wb + (3 * KS + ks) * 1024);
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) {
+                    Mma<T>::run(h0[rt], fd0, x0r[rt][ks]);
+                    Mma<T>::run(h1[rt], fd1, x0r[rt][ks]);
+                }
+            }
+            u32x4 hb[RT];
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                hb[rt][0] = pack2<T>(fmaxf(h0[rt][0], 0.f), fmaxf(h0[rt][1], 0.f));
+                hb[rt][1] = pack2<T>(fmaxf(h0[rt][2], 0.f), fmaxf(h0[rt][3], 0.f));
+                hb[rt][2] = pack2<T>(fmaxf(h1[rt][0], 0.f), fmaxf(h1[rt][1], 0.f));
+                hb[rt][3] = pack2<T>(fmaxf(h1[rt][2], 0.f), fmaxf(h1[rt][3], 0.f));
+                const int r = row_of(tile, rt);
+                const unsigned yo = ((unsigned)r * (unsigned)F + (unsigned)(32 * c + poff)) * 2u;
+                __builtin_amdgcn_raw_buffer_store_b128(chunk_swap(u32x2{hb[rt][0], hb[rt][1]}, u32x2{hb[rt][2], hb[rt][3]}),
+                                                       ry, r < p.M ? yo : OOB, 0, 0);
+            }
+            if constexpr (!PF) {
+                if (c == NCH - 1) {   // t2 / x0 of this tile are done with: the next tile's rows
+                    load_rows(next, rx, p.ldx, xr);
+                    load_rows(next, rx0, p.ldx0, x0r);
+                }
+            }
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const u32x4 fw = *reinterpret_cast<const u32x4*>(wb + (4 * KS + nt) * 1024);
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) Mma<T>::run(acc[rt][nt], fw, hb[rt]);
+            }
+        }
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            const int r = row_of(tile, rt);
+#pragma unroll
+            for (int kp = 0; kp < KSB; ++kp) {
+                const int n0 = 32 * kp + 8 * g;
+                u32x4 w;
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    w[e] = pack2<T>(fmaxf(acc[rt][2 * kp][2 * e] + pb1[n0 + 2 * e], 0.f),
+                                    fmaxf(acc[rt][2 * kp][2 * e + 1] + pb1[n0 + 2 * e + 1], 0.f));
+                    w[2 + e] = pack2<T>(fmaxf(acc[rt][2 * kp + 1][2 * e] + pb1[n0 + 4 + 2 * e], 0.f),
+                                        fmaxf(acc[rt][2 * kp + 1][2 * e + 1] + pb1[n0 + 4 + 2 * e + 1], 0.f));
+                }
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, w), rt_,
+                                                       r < p.M ? ((unsigned)r * (unsigned)DB + (unsigned)n0) * 2u : OOB, 0, 0);
+            }
+        }
+        if constexpr (PF) {
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    xr[rt][ks] = xn[rt][ks];
+                    x0r[rt][ks] = x0n[rt][ks];
+                }
+        }
+    }
+}
+
+template <typename T>
+void launch_pair_ds(const PairDsArgs& a, hipStream_t s) {
+    // one 16-wave workgroup per CU (96 KiB of weights), as bneck64_kernel<T, 128, 16>
+    const int cus = cu_count();
+    if (ffn_debug & 512) {   // A/B knob: two 16-row tiles per wave
+        const int nt = (a.M + 31) / 32, nb = (nt + 15) / 16;
+        hipLaunchKernelGGL((bneck64_ds_kernel<T, 2>), dim3(nb < cus ? nb : cus), dim3(1024), 0, s, a, nt);
+    } else {
+        const int nt = (a.M + 15) / 16, nb = (nt + 15) / 16;
+        hipLaunchKernelGGL((bneck64_ds_kernel<T, 1>), dim3(nb < cus ? nb : cus), dim3(1024), 0, s, a, nt);
+    }
+}
+
 template <typename T, int D, int RT, int WAVES, int WG_PER_CU>
 void launch_pair_cfg(const PairArgs& a, hipStream_t s) {
     constexpr int ROWS = WAVES * 16 * RT;
@@ -1011,6 +1198,39 @@ __global__ void bneck_pack_kernel(const float* __restrict__ W3, const float* __r
             v = W3[(long)h * D + 32 * ks + 8 * g + j] * s3[h];
         } else {
             const int nt = f - 2 * KS;
+            const int h = 32 * c + (j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4));
+            const int n = ffn_sigma(nt, c16);
+            v = W1[(long)n * F + h] * s1[n];
+        }
+        out[idx] = Cvt<T>::from(v);
+    }
+}
+
+// kinet_bottleneck_pack_ds (D = DB = 64): per chunk the 2 KS W3 fragments, then the 2 KS W_ds
+// fragments in the same (h-tile, k-step) order, then the NT W1 fragments; every row scaled by
+// its FrozenBN scale before the one rounding to T
+template <typename T>
+__global__ void bneck_pack_ds_kernel(const float* __restrict__ W3, const float* __restrict__ Wd,
+                                     const float* __restrict__ W1, const float* __restrict__ s3,
+                                     const float* __restrict__ sd, const float* __restrict__ s1, T* __restrict__ out,
+                                     int F) {
+    constexpr int D = 64, KS = D / 32, NT = 64 / 16, FR = 4 * KS + NT;
+    const long total = (long)(F / 32) * FR * 512;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const long per_chunk = (long)FR * 512;
+        const int c = (int)(idx / per_chunk);
+        const int rem = (int)(idx - (long)c * per_chunk);
+        const int f = rem >> 9, e = rem & 511;
+        const int lane = e >> 3, j = e & 7, g = lane >> 4, c16 = lane & 15;
+        float v;
+        if (f < 4 * KS) {
+            const bool ds = f >= 2 * KS;
+            const int ff = ds ? f - 2 * KS : f;
+            const int ht = ff / KS, ks = ff - ht * KS;
+            const int h = 32 * c + 16 * ht + c16;
+            v = (ds ? Wd : W3)[(long)h * D + 32 * ks + 8 * g + j] * (ds ? sd : s3)[h];
+        } else {
+            const int nt = f - 4 * KS;
             const int h = 32 * c + (j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4));
             const int n = ffn_sigma(nt, c16);
             v = W1[(long)n * F + h] * s1[n];
@@ -1181,6 +1401,58 @@ extern "C" int kinet_bottleneck_pair(const void* X, int ldx, const void* R, cons
     hipStream_t s = (hipStream_t)stream;
     const int rc = dtype == KINET_BF16 ? launch_pair<bf16_t>(a, D, DB, s) : launch_pair<f16_t>(a, D, DB, s);
     if (rc) return rc;
+    KINET_LAUNCH_CHECK();
+    return KINET_OK;
+}
+
+extern "C" int kinet_bottleneck_pack_ds(const float* W3, const float* Wds, const float* W1, const float* s3,
+                                        const float* sds, const float* s1, void* packed, int D, int F, int DB,
+                                        int dtype, kinet_stream_t stream) {
+    KINET_CHECK_ARG(D == 64 && F == 256 && DB == 64,
+                    "bottleneck_pack_ds: stage 1 only, D = 64, F = 256, DB = 64 (got D=%d F=%d DB=%d)", D, F, DB);
+    KINET_CHECK_ARG(dtype == KINET_BF16 || dtype == KINET_F16, "bottleneck_pack_ds: dtype must be bf16 or f16");
+    KINET_CHECK_ARG(W3 && Wds && W1 && s3 && sds && s1 && packed, "bottleneck_pack_ds: null pointer");
+    const long total = (long)(D + 64 + DB) * F;
+    const int grid = (int)((total + 255) / 256 < kMaxGridStride ? (total + 255) / 256 : kMaxGridStride);
+    if (dtype == KINET_BF16)
+        hipLaunchKernelGGL(bneck_pack_ds_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, W3, Wds, W1, s3,
+                           sds, s1, (bf16_t*)packed, F);
+    else
+        hipLaunchKernelGGL(bneck_pack_ds_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, W3, Wds, W1, s3,
+                           sds, s1, (f16_t*)packed, F);
+    KINET_LAUNCH_CHECK();
+    return KINET_OK;
+}
+
+extern "C" int kinet_bottleneck_pair_ds(const void* X, int ldx, const void* X0, int ldx0, const void* packed,
+                                        const float* b3ds, const float* b1, void* Y, void* T, int M, int D, int F,
+                                        int DB, int dtype, kinet_stream_t stream) {
+    KINET_CHECK_ARG(D == 64, "bottleneck_pair_ds: D must be 64 (got %d)", D);
+    KINET_CHECK_ARG(F == 256, "bottleneck_pair_ds: F must be 256 (got %d)", F);
+    KINET_CHECK_ARG(DB == 64, "bottleneck_pair_ds: DB must be 64 (got %d)", DB);
+    KINET_CHECK_ARG(M >= 0 && ldx >= 64 && ldx % 8 == 0 && ldx0 >= 64 && ldx0 % 8 == 0,
+                    "bottleneck_pair_ds: bad M / ldx / ldx0 (row strides >= 64, multiples of 8)");
+    KINET_CHECK_ARG(dtype == KINET_BF16 || dtype == KINET_F16, "bottleneck_pair_ds: dtype must be bf16 or f16");
+    KINET_CHECK_ARG(b3ds && b1, "bottleneck_pair_ds: the combined bias b3 + b_ds and b1 are required");
+    KINET_CHECK_ARG(X && X0 && packed && Y && T, "bottleneck_pair_ds: null pointer");
+    KINET_CHECK_ARG(al16(X) && al16(X0) && al16(packed) && al16(Y) && al16(T) && al16(b3ds) && al16(b1),
+                    "bottleneck_pair_ds: tensors and BN biases must be 16-byte aligned");
+    if (M == 0) return KINET_OK;
+    const long long xb = ((long long)(M - 1) * ldx + D) * 2, x0b = ((long long)(M - 1) * ldx0 + 64) * 2;
+    const long long fb = (long long)M * F * 2;
+    KINET_CHECK_ARG(xb < (1LL << 31) && x0b < (1LL << 31) && fb < (1LL << 31),
+                    "bottleneck_pair_ds: tensors larger than 2 GiB (split the call)");
+    PairDsArgs a{};
+    a.X = X; a.X0 = X0; a.W = packed; a.b3 = b3ds; a.b1 = b1; a.Y = Y; a.T = T;
+    a.ldx = ldx; a.ldx0 = ldx0; a.M = M;
+    a.x_bytes = (int)xb;
+    a.x0_bytes = (int)x0b;
+    a.y_bytes = (int)fb;
+    a.w_bytes = (int)((long long)(D + 64 + DB) * F * 2);
+    a.t_bytes = (int)((long long)M * DB * 2);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == KINET_BF16) launch_pair_ds<bf16_t>(a, s);
+    else launch_pair_ds<f16_t>(a, s);
     KINET_LAUNCH_CHECK();
     return KINET_OK;
 }

@@ -465,6 +465,51 @@ def bottleneck_pair(x, residual, packed, b3, b1):
     return y, t
 
 
+def bottleneck_pack_ds(w3, wds, w1, s3, sds, s1, b3, bds, dtype):
+    """kinet_bottleneck_pack_ds of stage 1's block-0 conv3 (256, 64, 1, 1), its downsample conv
+    (256, 64, 1, 1) and block 1's conv1 (64, 256, 1, 1) with their FrozenBN scales folded in ->
+    (packed weights, b3 + b_ds in f32), cached per parameter version."""
+    def make(a, d, b, sa, sd, sb, ba, bd):
+        F_, D, DB = a.shape[0], a.shape[1], b.shape[0]
+        a32 = a.detach().reshape(F_, D).float().contiguous()
+        d32 = d.detach().reshape(F_, D).float().contiguous()
+        b32 = b.detach().reshape(DB, F_).float().contiguous()
+        out = torch.empty((2 * D + DB) * F_, dtype=dtype, device=a.device)
+        N.call('kinet_bottleneck_pack_ds', N.ptr(a32), N.ptr(d32), N.ptr(b32), N.ptr(f32(sa)), N.ptr(f32(sd)),
+               N.ptr(f32(sb)), N.ptr(out), D, F_, DB, N.dtype_code(dtype), N.stream(a.device))
+        return out, (ba.detach().float() + bd.detach().float()).contiguous()
+    return cached_multi([w3, wds, w1, s3, sds, s1, b3, bds], ('bneck_pack_ds', dtype), make)
+
+
+def bottleneck_pair_ds_supported(dtype, w3, wds, w1):
+    """The downsample-folded pair covers stage 1 only: 16-bit rows, conv3 (256, 64, 1, 1), the
+    downsample conv (256, 64, 1, 1) over a 64-channel block input, the next conv1 (64, 256, 1, 1)."""
+    return (dtype in (torch.bfloat16, torch.float16) and tuple(w3.shape) == (256, 64, 1, 1)
+            and tuple(wds.shape) == (256, 64, 1, 1) and tuple(w1.shape) == (64, 256, 1, 1))
+
+
+def bottleneck_pair_ds(x, x0, packed, b3ds, b1):
+    """Stage 1's first bottleneck pair with block 0's downsample folded in
+    (kinet_bottleneck_pair_ds): x = block 0's conv2 output (B, H, W, 64), x0 = the block input
+    (B, H, W, 64) -> (y, t): y = relu(conv3(x) * s3 + conv_ds(x0) * s_ds + b3ds) (256 channels),
+    t = relu(conv1'(y) * s1 + b1) (64 channels); packed, b3ds from bottleneck_pack_ds."""
+    N.require_gpu(x, x0)
+    B, H, W, D = x.shape
+    if D != 64 or x0.shape != x.shape or x0.dtype != x.dtype or not x.is_contiguous() or not x0.is_contiguous():
+        raise RuntimeError('bottleneck_pair_ds: x and x0 must be contiguous (B, H, W, 64) tensors of one dtype')
+    if b3ds.numel() != 256 or b3ds.dtype != torch.float32 or b1.numel() != 64:
+        raise RuntimeError('bottleneck_pair_ds: b3ds must be 256 f32 values and b1 64 values')
+    M, F_, DB = B * H * W, 256, 64
+    y = torch.empty((B, H, W, F_), dtype=x.dtype, device=x.device)
+    t = torch.empty((B, H, W, DB), dtype=x.dtype, device=x.device)
+    e = x.element_size()
+    work = {'family': 'conv', 'flops': 2.0 * M * F_ * (D + 64 + DB), 'shape': ('bneck_ds', M, D, F_, DB),
+            'bytes': (M * D + M * 64 + M * F_ + M * DB + (D + 64 + DB) * F_) * e}
+    N.call('kinet_bottleneck_pair_ds', N.ptr(x), D, N.ptr(x0), 64, N.ptr(packed), N.ptr(b3ds), N.ptr(f32(b1)),
+           N.ptr(y), N.ptr(t), M, D, F_, DB, N.dtype_code(x.dtype), N.stream(x.device), work=work)
+    return y, t
+
+
 def maxpool_3x3s2(x):
     B, H, W, C = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1

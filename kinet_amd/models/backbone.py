@@ -62,6 +62,11 @@ class FrozenBatchNorm2d(nn.Module):
 # profiles/r06c_ab_summary.txt, r06d_ab_summary.txt)
 FUSE_BOTTLENECK_PAIRS = True
 FUSE_PAIR_WIDTHS = (64, 128, 256)
+# Stage 1's downsample conv (1x1, 64 -> 256 over the max-pool output) folded into the first pair
+# (kinet_bottleneck_pair_ds): the 256-channel identity tensor of layer1[0] is neither written nor
+# read.  Only where that pair is fused at all; False runs the downsample conv on its own
+# (A/B: tools/bneck_ab.py, profiles/ds_fold_ab.txt)
+FUSE_DOWNSAMPLE = True
 # 16-bit stem straight from the f32 image (kinet_stem_conv_image); False: pack_image_kwfold +
 # the folded conv (A/B: bench.py --stem-image 0)
 STEM_FROM_IMAGE = True
@@ -115,6 +120,20 @@ def _pair_ok(dtype, blk, nxt):
             and K.bottleneck_pair_supported(dtype, blk.conv3.weight, nxt.conv1.weight))
 
 
+def _fold_downsample_ok(x, b0, nxt):
+    """Block 0's downsample runs inside the first pair launch: a stride-1 1x1 conv over a
+    64-channel 16-bit input (stage 1), and the pair block 0 -> nxt is fused anyway."""
+    ds = b0.downsample
+    if not FUSE_DOWNSAMPLE or ds is None or nxt is None:
+        return False
+    conv = ds[0]
+    return (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.in_channels == 64
+            and b0.conv2.stride == (1, 1) and nxt.conv1.stride == (1, 1) and x.is_contiguous()
+            and _pair_ok(x.dtype, b0, nxt)
+            and K.bottleneck_pair_ds_supported(x.dtype, b0.conv3.weight, conv.weight, nxt.conv1.weight)
+            and x.numel() * 4 * x.element_size() < 2 ** 31)   # the kernel's 32-bit offsets
+
+
 def forward_layer_nhwc(layer, x, t1=None, next_block=None):
     """One ResNet stage over NHWC x -> (stage output, next_block's conv1 output or None).
     With FUSE_BOTTLENECK_PAIRS the chain conv3 (+ residual + ReLU) of block i -> conv1 of block
@@ -122,18 +141,35 @@ def forward_layer_nhwc(layer, x, t1=None, next_block=None):
     block's residual) and not re-read by the next conv1.  `next_block` (the next stage's first
     block) extends the chain across the stage boundary where the pair kernel covers it (stage 1
     -> 2: its conv1 is stride 1); `t1` = this stage's first conv1 output when the previous stage
-    computed it.  Same math as Bottleneck.forward_nhwc per block (torchvision, backbone.py:102)."""
+    computed it.  With FUSE_DOWNSAMPLE stage 1's downsample conv runs inside its first pair
+    (kinet_bottleneck_pair_ds) instead of writing the identity tensor.  Same math as
+    Bottleneck.forward_nhwc per block (torchvision, backbone.py:102)."""
     blocks = list(layer)
     b0 = blocks[0]
     if t1 is None:
         t1 = conv_bn(x, b0.conv1, b0.bn1, True)
-    identity = x if b0.downsample is None else conv_bn(x, b0.downsample[0], b0.downsample[1], False)
+    # stage 1 with FUSE_DOWNSAMPLE: block 0's identity conv runs inside the first pair launch
+    fold_ds = _fold_downsample_ok(x, b0, blocks[1] if len(blocks) > 1 else next_block)
+    if fold_ds:
+        identity = None
+    else:
+        identity = x if b0.downsample is None else conv_bn(x, b0.downsample[0], b0.downsample[1], False)
     t_next = None
     for i, blk in enumerate(blocks):
         t2 = conv_bn(t1, blk.conv2, blk.bn2, True)
         last = i + 1 == len(blocks)
         nxt = next_block if last else blocks[i + 1]
-        if (nxt is not None and nxt.conv1.stride == (1, 1) and _pair_ok(t2.dtype, blk, nxt)
+        if i == 0 and fold_ds:
+            ds, bnd = b0.downsample[0], b0.downsample[1]
+            s3, b3 = blk.bn3.folded()
+            sd, bd = bnd.folded()
+            s1, b1 = nxt.bn1.folded()
+            packed, b3ds = K.bottleneck_pack_ds(blk.conv3.weight, ds.weight, nxt.conv1.weight, s3, sd, s1, b3, bd,
+                                                t2.dtype)
+            identity, t1 = K.bottleneck_pair_ds(t2, x, packed, b3ds, b1)
+            if last:
+                t_next = t1
+        elif (nxt is not None and nxt.conv1.stride == (1, 1) and _pair_ok(t2.dtype, blk, nxt)
                 and t2.numel() * 4 * t2.element_size() < 2 ** 31):   # the kernel's 32-bit offsets
             s3, b3 = blk.bn3.folded()
             s1, b1 = nxt.bn1.folded()
