@@ -36,6 +36,36 @@ int kinet_ffn_fused(const void* X, int ldx, const void* packed, const float* b1,
                     const float* ln_gamma, const float* ln_beta, float ln_eps, void* Y, int ldy,
                     int M, int D, int F, int dtype, kinet_stream_t stream);
 
+/* Encoder layer tail in ONE launch: the deformable attention's out-projection, its residual add
+ * and post-norm, then the FFN sub-layer above (DeformableTransformerEncoderLayer.forward,
+ * deformable_transformer.py:290-299 after the sampler):
+ *   x = LayerNorm1( R + A Wo^T + bo )                      (M, D), never written to memory
+ *   y = LayerNorm2( x + linear2( relu( linear1(x) ) ) )     (M, D)
+ * A = the sampler's output, row stride lda; R = the layer input (residual), row stride ldr.
+ * x is rounded to dtype exactly once, after LayerNorm1 -- the point where the two-launch path
+ * (kinet_gemm_ex with the LayerNorm epilogue, then kinet_ffn_fused) stores it -- and that rounded
+ * x is both linear1's operand and the FFN's residual.  The out-projection sums run in f32 in
+ * ascending k, in another order than the GEMM's, so a rounding of x may differ from the
+ * two-launch path's by one ulp of dtype.
+ * kinet_ffn_pack_attn: Wo (D, D), W1 (F, D), W2 (D, F) of dtype -> D*D + 2*D*F elements: first
+ * Wo as (D/32) * (D/16) 1-KiB MFMA operand fragments, k-step major (fragment (ks, nt), lane
+ * (g, c), element j = Wo[32 (nt / 2) + 8 (c / 4) + 4 (nt % 2) + c % 4][32 ks + 8 g + j]), i.e. at
+ * D = 256 four ring chunks of 32 fragments; then exactly the stream kinet_ffn_pack writes.
+ * kinet_attn_out_ffn_fused: D = 256 only (at D = 288 Wo does not fill whole ring chunks:
+ * KINET_ERR_ARG), F % 32 == 0, F <= 2048; lda, ldr, ldy >= D and multiples of 8; every pointer
+ * 16-byte aligned; every tensor below 2 GiB; bo, ln1_gamma, ln1_beta (D) f32 required; b1 (F),
+ * b2 (D) f32; ln2_gamma / ln2_beta (D) f32 or both NULL (then y = x + FFN(x)); Y must not overlap
+ * A or R.  Correct for every M >= 1 (M == 0: nothing is launched); it runs on the 8-wave x
+ * 32-row tile, which pays from about 16384 rows. */
+int kinet_ffn_pack_attn(const void* Wo, const void* W1, const void* W2, void* packed, int D, int F,
+                        int dtype, kinet_stream_t stream);
+
+int kinet_attn_out_ffn_fused(const void* A, int lda, const void* R, int ldr, const void* packed,
+                             const float* bo, const float* ln1_gamma, const float* ln1_beta,
+                             float ln1_eps, const float* b1, const float* b2, const float* ln2_gamma,
+                             const float* ln2_beta, float ln2_eps, void* Y, int ldy, int M, int D,
+                             int F, int dtype, kinet_stream_t stream);
+
 /* ResNet bottleneck pair (torchvision Bottleneck as the reference instantiates it,
  * backbone.py:94-108): block i's conv3 + FrozenBN + residual + ReLU and the next block's conv1 +
  * FrozenBN + ReLU, both 1x1 stride 1 over NHWC rows, in ONE launch (phase A = conv3, its

@@ -44,9 +44,18 @@ struct FfnArgs {
     int dbg;   // diagnostic knobs (kinet_ffn_set_debug): 1 = no weight DMA after the prologue
                // (timing only, results are garbage); 2 = the 4-wave x 32-row tile at D = 256;
                // 8 = the 8-wave x 16-row tile (default: 8 waves x 32 rows, ffn_fused_rt2_kernel);
+               // 64 = kinet_attn_out_ffn_fused stages its residual loads under the Wo chunks (RV = 1);
                // 16 = kinet_bottleneck_pair at D = 64 on the LDS-ring kernel (bneck_pair_kernel);
                // 128 / 256 = kinet_bottleneck_pair at D = 128 / 256 on 1- / 2-row-tile waves;
                // 512 = kinet_bottleneck_pair_ds on 2-row-tile waves (bneck64_ds_kernel<T, 2>)
+    // kinet_attn_out_ffn_fused only (ffn_fused_rt2_kernel<.., PRE>): x = LN1(R + A Wo^T + bo)
+    const void* A;   // attention output (M, D), row stride lda
+    const void* R;   // residual (M, D), row stride ldr
+    const float* bo;
+    const float* g1;
+    const float* be1;
+    float eps1;
+    int lda, ldr, a_bytes, r_bytes;
 };
 
 thread_local int ffn_debug = 0;   // test-only knob (kinet_ffn_set_debug), per calling thread
@@ -106,6 +115,11 @@ __device__ __forceinline__ void ffn_lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
+}
+
+// dma16 with a wave-uniform part of the source offset in an SGPR
+__device__ __forceinline__ void dma16s(__amdgpu_buffer_rsrc_t r, char* dst, unsigned voff, int soff) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)dst, 16, voff, soff, 0, 0);
 }
 
 constexpr int FFN_MAX_F = 2048;
@@ -399,7 +413,18 @@ __global__ __launch_bounds__(WAVES * 64) void ffn_fused_kernel(const FfnArgs p, 
 // B of a chunk follows its own phase A (no cross-chunk software pipeline) and the ring holds 3
 // chunks (2 in flight + the one being computed).  Same packed weights, same sums in the same
 // order per output element as ffn_fused_kernel (bit-identical results).
-template <typename T, int D>
+//
+// PRE (kinet_attn_out_ffn_fused): the attention out-projection and its post-norm run in front of
+// the FFN on the same tile, x = LN1(R + A Wo^T + bo), so x is never written to or read from HBM.
+// Wo travels through the ring as PCH chunks ahead of each tile's hidden chunks (fragment (ks, nt)
+// = Wo[ffn_sigma(nt, .)][32 ks ..], ks-major: kinet_ffn_pack_attn); the products accumulate in
+// acc, idle until phase B, in phase B's output layout -- the columns a lane holds of tile pair
+// (2kp, 2kp+1) are the columns of its fragment xr[kp], so + bo + R, LayerNorm and pack2 leave x
+// in xr as phase A's operand.  The A (samp) fragments sit in xr until their last MFMA; RV picks
+// where the residual is loaded into the registers they free: 0 = all 2 KS after the last
+// pre-chunk, 1 = fragments 2(u-1), 2(u-1)+1 at the start of pre-chunk u (their A fragments were
+// last used by pre-chunk u-1), only the last pair after the last pre-chunk.
+template <typename T, int D, bool PRE = false, int RV = 0>
 __global__ __launch_bounds__(512) void ffn_fused_rt2_kernel(const FfnArgs p, const int ntiles) {
     constexpr int RT = 2, WAVES = 8;
     using G = FfnGeo<D>;
@@ -409,12 +434,18 @@ __global__ __launch_bounds__(512) void ffn_fused_rt2_kernel(const FfnArgs p, con
     constexpr int ROWS = WAVES * 16 * RT;
     constexpr int NS = 3;
     constexpr unsigned OOB = 0x80000000u;
-    constexpr int PAR = (FFN_MAX_F + 3 * D) * 4;
+    constexpr int PCH = PRE ? KS * NT / FR : 0;   // Wo chunks per tile (FR fragments each)
+    static_assert(!PRE || (KS * NT) % FR == 0, "Wo must fill whole ring chunks");
+    static_assert(!PRE || (FR % NT == 0 && KS % (FR / NT) == 0), "whole k-steps per Wo chunk");
+    constexpr int PAR = (FFN_MAX_F + (PRE ? 6 : 3) * D) * 4;
     __shared__ __attribute__((aligned(16))) char lds[PAR + NS * G::CHUNK];
     float* const pb1 = reinterpret_cast<float*>(lds);
     float* const pb2 = pb1 + FFN_MAX_F;
     float* const pg = pb2 + D;
     float* const pbe = pg + D;
+    float* const pbo = pbe + D;      // PRE only: out-projection bias, LN1 gamma / beta
+    float* const pg1 = pbo + D;
+    float* const pbe1 = pg1 + D;
     char* const ring = lds + PAR;
 
     const int P = gridDim.x, bx = blockIdx.x;
@@ -425,29 +456,45 @@ __global__ __launch_bounds__(512) void ffn_fused_rt2_kernel(const FfnArgs p, con
     const int g = lane >> 4, c16 = lane & 15;
     const int nch = p.F / 32;
     const bool ln = p.ln_g != nullptr;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.X, (short)0, p.x_bytes, 0x00020000);
+    // the tile's operand rows: x, or with PRE the attention output A
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(PRE ? p.A : p.X), (short)0,
+                                                                        PRE ? p.a_bytes : p.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, (short)0, p.w_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(p.Y, (short)0, p.y_bytes, 0x00020000);
+    const int ldx = PRE ? p.lda : p.ldx;
 
     for (int i = threadIdx.x; i < p.F; i += WAVES * 64) pb1[i] = p.b1[i];
     for (int i = threadIdx.x; i < D; i += WAVES * 64) {
         pb2[i] = p.b2[i];
         pg[i] = ln ? p.ln_g[i] : 1.f;
         pbe[i] = ln ? p.ln_b[i] : 0.f;
+        if constexpr (PRE) {
+            pbo[i] = p.bo[i];
+            pg1[i] = p.g1[i];
+            pbe1[i] = p.be1[i];
+        }
     }
+    // chunk c of the packed stream ([PCH Wo chunks,] then the hidden chunks) -> ring slot q % NS
     auto dma_chunk = [&](int q, int c) {
         char* dst = ring + (q % NS) * G::CHUNK;
         const unsigned src = (unsigned)c * (unsigned)G::CHUNK + (unsigned)lane * 16u;
 #pragma unroll
         for (int k = 0; k < FRW; ++k) {
             const int f = k * WAVES + wave;
-            dma16(rw, dst + f * 1024, src + (unsigned)f * 1024u);
+            if constexpr (PRE) {
+                // the wave-uniform part of the source goes in the scalar offset: the unrolled Wo
+                // chunks otherwise keep FRW loop-invariant vector addresses each (spilled)
+                dma16s(rw, dst + f * 1024, (unsigned)lane * 16u, c * G::CHUNK + f * 1024);
+            } else {
+                dma16(rw, dst + f * 1024, src + (unsigned)f * 1024u);
+            }
         }
     };
-    const int total = cnt * nch;
+    const int ncht = nch + PCH;   // ring chunks per tile
+    const int total = cnt * ncht;
     __syncthreads();   // parameters in LDS
     dma_chunk(0, 0);
-    if (total > 1) dma_chunk(1, nch > 1 ? 1 : 0);
+    if (total > 1) dma_chunk(1, ncht > 1 ? 1 : 0);
 
     u32x4 xr[RT][KS];
     f32x4 acc[RT][NT];
@@ -458,7 +505,10 @@ __global__ __launch_bounds__(512) void ffn_fused_rt2_kernel(const FfnArgs p, con
             const int r = tile * ROWS + wave * 16 * RT + 16 * rt + c16;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                const unsigned off = r < p.M ? ((unsigned)r * (unsigned)p.ldx + (unsigned)(32 * ks + 8 * g)) * 2u : OOB;
+                // (PRE: one select per row, the column as a constant on top -- an OOB offset stays
+                // OOB -- so the per-fragment offsets are not 2 KS values kept live across the tile)
+                const unsigned off = PRE ? (r < p.M ? ((unsigned)r * (unsigned)ldx + (unsigned)(8 * g)) * 2u : OOB) + 64u * ks
+                                         : r < p.M ? ((unsigned)r * (unsigned)ldx + (unsigned)(32 * ks + 8 * g)) * 2u : OOB;
                 xr[rt][ks] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));
             }
         }
@@ -466,17 +516,130 @@ __global__ __launch_bounds__(512) void ffn_fused_rt2_kernel(const FfnArgs p, con
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) acc[rt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (PRE) {
+            const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)p.R, (short)0, p.r_bytes, 0x00020000);
+            // residual fragment kp of both row tiles into the registers of the A fragments kp
+            auto load_res = [&](int kp) {
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) {
+                    const int r = tile * ROWS + wave * 16 * RT + 16 * rt + c16;
+                    const unsigned off = (r < p.M ? ((unsigned)r * (unsigned)p.ldr + (unsigned)(8 * g)) * 2u : OOB) + 64u * kp;
+                    xr[rt][kp] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, off, 0, 0));
+                }
+            };
+            constexpr int KPC = FR / NT;   // k-steps per Wo chunk
+            constexpr int PDW = RV == 1 ? 3 : 4;   // Wo fragments read ahead of their MFMAs (RV 1: 4 spill)
+#pragma unroll
+            for (int u = 0; u < PCH; ++u) {
+                const int q = ti * ncht + u;
+                // chunk q landed (a hidden chunk always follows: q + 1 < total).  Younger than its
+                // DMA: chunk q+1's DMA and, with RV == 1 from u = 2 on, the RT * KPC residual loads
+                // of pre-chunk u-1 (those of pre-chunk u-2 are counted as older, whichever side of
+                // that iteration's DMA they were issued on); at u = 0 also the previous tile's
+                // stores and this tile's A loads, which this then waits for too
+                if (RV == 1 && u >= 2) ffn_wait_vmcnt<FRW + RT * KPC>();
+                else ffn_wait_vmcnt<FRW>();
+                ffn_lds_barrier();   // chunk q visible; slot (q+2) % NS (chunk q-1) free
+                if (q + 2 < total) {
+                    int cn = u + 2;
+                    if (cn >= ncht) cn -= ncht;
+                    dma_chunk(q + 2, cn);
+                }
+                if constexpr (RV == 1) {
+                    if (u > 0) {
+#pragma unroll
+                        for (int k = 0; k < KPC; ++k) load_res((u - 1) * KPC + k);
+                    }
+                }
+                const char* wb = ring + (q % NS) * G::CHUNK;
+                auto frag = [&](int f) { return *reinterpret_cast<const u32x4*>(wb + lane * 16 + f * 1024); };
+                // x^T(D x rows) += Wo[:, k-steps of this chunk] A^T: fragment f = (k-step f / NT,
+                // tile f % NT), each feeding both row tiles; per accumulator the k-steps ascend
+                u32x4 fo[FR];
+#pragma unroll
+                for (int f = 0; f < PDW; ++f) fo[f] = frag(f);
+#pragma unroll
+                for (int f = 0; f < FR; ++f) {
+                    if (f + PDW < FR) fo[f + PDW] = frag(f + PDW);
+#pragma unroll
+                    for (int rt = 0; rt < RT; ++rt) Mma<T>::run(acc[rt][f % NT], fo[f], xr[rt][u * KPC + f / NT]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+#pragma unroll
+            for (int kp = (RV == 1 ? KS - KPC : 0); kp < KS; ++kp) load_res(kp);
+            // x = LN1(acc + bo + R), rounded to T: phase A's operand and the FFN's residual.  acc
+            // and xr fill most of the register file here, so one row tile at a time
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                // (the parameters are re-read from LDS for each row tile: held in registers from
+                // the first to the second they would not fit)
+                asm volatile("" ::: "memory");
+                float s = 0.f;
+#pragma unroll
+                for (int kp = 0; kp < KS; ++kp) {
+                    const f32x4 boa = *reinterpret_cast<const f32x4*>(pbo + 32 * kp + 8 * g);
+                    const f32x4 bob = *reinterpret_cast<const f32x4*>(pbo + 32 * kp + 8 * g + 4);
+                    f32x4 xa, xb;
+                    unpack4<T>(u32x2{xr[rt][kp][0], xr[rt][kp][1]}, reinterpret_cast<float*>(&xa));
+                    unpack4<T>(u32x2{xr[rt][kp][2], xr[rt][kp][3]}, reinterpret_cast<float*>(&xb));
+                    const f32x4 va = acc[rt][2 * kp] + boa + xa;
+                    const f32x4 vb = acc[rt][2 * kp + 1] + bob + xb;
+                    acc[rt][2 * kp] = va;
+                    acc[rt][2 * kp + 1] = vb;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) s += va[i] + vb[i];   // the epilogue's order
+                }
+                s += __shfl_xor(s, 16);
+                s += __shfl_xor(s, 32);
+                const float mean = s * (1.f / (float)D);
+                float qv = 0.f;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float d = acc[rt][nt][i] - mean;
+                        qv += d * d;
+                    }
+                qv += __shfl_xor(qv, 16);
+                qv += __shfl_xor(qv, 32);
+                const float rstd = rsqrtf(qv * (1.f / (float)D) + p.eps1);
+#pragma unroll
+                for (int kp = 0; kp < KS; ++kp) {
+                    const int n0 = 32 * kp + 8 * g;
+                    float o[8];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        o[i] = acc[rt][2 * kp][i];
+                        o[4 + i] = acc[rt][2 * kp + 1][i];
+                    }
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) o[k] = (o[k] - mean) * rstd * pg1[n0 + k] + pbe1[n0 + k];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) xr[rt][kp][k] = pack2<T>(o[2 * k], o[2 * k + 1]);
+                    // opaque from here on: otherwise the epilogue's unpack of x is folded into
+                    // these conversions and their results stay live (spilled) across the chunk
+                    // loop next to the packed words
+                    asm volatile("" : "+v"(xr[rt][kp]));
+                }
+            }
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) acc[rt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
         for (int c = 0; c < nch; ++c) {
-            const int q = ti * nch + c;
+            const int q = ti * ncht + PCH + c;
             // chunk q landed: younger are at most chunk q+1's DMA (plus, at a tile boundary, the
-            // previous tile's stores and this tile's x loads -- then this waits for those too)
+            // previous tile's stores and this tile's x loads -- then this waits for those too;
+            // with PRE everything issued before LN1 has been waited for by the loads it consumed)
             if (q + 1 < total) ffn_wait_vmcnt<FRW>();
             else ffn_wait_vmcnt<0>();
             ffn_lds_barrier();   // chunk q visible; slot (q+2) % NS (chunk q-1) free
             if (q + 2 < total) {
-                int cn = c + 2;
-                if (cn >= nch) cn -= nch;
-                if (cn >= nch) cn -= nch;
+                int cn = PCH + c + 2;
+                if (cn >= ncht) cn -= ncht;
+                if (cn >= ncht) cn -= ncht;
                 dma_chunk(q + 2, cn);
             }
             const char* wb = ring + (q % NS) * G::CHUNK;
@@ -599,7 +762,8 @@ __global__ __launch_bounds__(512) void ffn_fused_rt2_kernel(const FfnArgs p, con
                 u32x4 w;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) w[e] = pack2<T>(o[2 * e], o[2 * e + 1]);
-                const unsigned off = r < p.M ? ((unsigned)r * (unsigned)p.ldy + (unsigned)n0) * 2u : OOB;
+                const unsigned off = PRE ? (r < p.M ? ((unsigned)r * (unsigned)p.ldy + (unsigned)(8 * g)) * 2u : OOB) + 64u * kp
+                                         : r < p.M ? ((unsigned)r * (unsigned)p.ldy + (unsigned)n0) * 2u : OOB;
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, w), ry, off, 0, 0);
             }
         }
@@ -1263,6 +1427,20 @@ __global__ void ffn_pack_kernel(const T* __restrict__ W1, const T* __restrict__ 
     }
 }
 
+// kinet_ffn_pack_attn's head: Wo (D, D) as D/32 * D/16 1-KiB MFMA A-operand fragments, k-step
+// major: fragment (ks, nt), lane (g, c16), element j = Wo[ffn_sigma(nt, c16)][32 ks + 8 g + j]
+template <typename T>
+__global__ void attn_pack_kernel(const T* __restrict__ Wo, T* __restrict__ out, int D) {
+    const int NT = D / 16;
+    const long total = (long)D * D;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const int f = (int)(idx >> 9), e = (int)(idx & 511);
+        const int ks = f / NT, nt = f - ks * NT;
+        const int lane = e >> 3, j = e & 7, g = lane >> 4, c16 = lane & 15;
+        out[idx] = Wo[(long)ffn_sigma(nt, c16) * D + 32 * ks + 8 * g + j];
+    }
+}
+
 template <typename T, int D>
 int launch_ffn(const FfnArgs& a, hipStream_t s) {
     // persistent: one workgroup per CU walks row tiles.  Many rows: 4 waves x 32 rows (128
@@ -1294,6 +1472,19 @@ int launch_ffn(const FfnArgs& a, hipStream_t s) {
         hipLaunchKernelGGL((ffn_fused_kernel<T, D, 1, 4>), dim3(nt < 256 ? nt : 256), dim3(256), 0, s, a, nt);
     }
     return KINET_OK;
+}
+
+template <typename T>
+void launch_attn_out_ffn(const FfnArgs& a, hipStream_t s) {
+    // persistent like launch_ffn's 8-wave x 32-row case, the only tile with the pre-phase
+    const int nt = (a.M + 255) / 256;
+    const dim3 grid(nt < 256 ? nt : 256), block(512);
+    // residual loads: all after the last Wo chunk (715 us per batch-28 encoder layer) or, A/B knob,
+    // staged under the Wo chunks (732 us: no faster, profiles/attn_out_ffn_probe.txt)
+    if (a.dbg & 64)
+        hipLaunchKernelGGL((ffn_fused_rt2_kernel<T, 256, true, 1>), grid, block, 0, s, a, nt);
+    else
+        hipLaunchKernelGGL((ffn_fused_rt2_kernel<T, 256, true, 0>), grid, block, 0, s, a, nt);
 }
 
 bool al16(const void* q) { return (((uintptr_t)q) & 15u) == 0; }
@@ -1354,6 +1545,62 @@ extern "C" int kinet_ffn_fused(const void* X, int ldx, const void* packed, const
     if (dtype == KINET_BF16) rc = D == 256 ? launch_ffn<bf16_t, 256>(a, s) : launch_ffn<bf16_t, 288>(a, s);
     else rc = D == 256 ? launch_ffn<f16_t, 256>(a, s) : launch_ffn<f16_t, 288>(a, s);
     if (rc) return rc;
+    KINET_LAUNCH_CHECK();
+    return KINET_OK;
+}
+
+extern "C" int kinet_ffn_pack_attn(const void* Wo, const void* W1, const void* W2, void* packed, int D, int F,
+                                   int dtype, kinet_stream_t stream) {
+    KINET_CHECK_ARG(D > 0 && D % 32 == 0 && F > 0 && F % 32 == 0, "ffn_pack_attn: need D %% 32 == 0 and F %% 32 == 0 (D=%d F=%d)", D, F);
+    KINET_CHECK_ARG(dtype == KINET_BF16 || dtype == KINET_F16, "ffn_pack_attn: dtype must be bf16 or f16");
+    const long total = (long)D * D;
+    const int grid = (int)((total + 255) / 256 < kMaxGridStride ? (total + 255) / 256 : kMaxGridStride);
+    if (dtype == KINET_BF16)
+        hipLaunchKernelGGL(attn_pack_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)Wo,
+                           (bf16_t*)packed, D);
+    else
+        hipLaunchKernelGGL(attn_pack_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f16_t*)Wo,
+                           (f16_t*)packed, D);
+    KINET_LAUNCH_CHECK();
+    return kinet_ffn_pack(W1, W2, (char*)packed + total * 2, D, F, dtype, stream);
+}
+
+extern "C" int kinet_attn_out_ffn_fused(const void* A, int lda, const void* R, int ldr, const void* packed,
+                                        const float* bo, const float* g1, const float* be1, float eps1,
+                                        const float* b1, const float* b2, const float* g2, const float* be2,
+                                        float eps2, void* Y, int ldy, int M, int D, int F, int dtype,
+                                        kinet_stream_t stream) {
+    KINET_CHECK_ARG(D != 288, "attn_out_ffn_fused: D = 288 is not supported (Wo does not fill whole ring chunks); D must be 256");
+    KINET_CHECK_ARG(D == 256, "attn_out_ffn_fused: D must be 256 (got %d)", D);
+    KINET_CHECK_ARG(F > 0 && F % 32 == 0 && F <= FFN_MAX_F, "attn_out_ffn_fused: F must be a multiple of 32 in [32, %d] (got %d)", FFN_MAX_F, F);
+    KINET_CHECK_ARG(M >= 0 && lda >= D && ldr >= D && ldy >= D && lda % 8 == 0 && ldr % 8 == 0 && ldy % 8 == 0,
+                    "attn_out_ffn_fused: bad M / lda / ldr / ldy");
+    KINET_CHECK_ARG(dtype == KINET_BF16 || dtype == KINET_F16, "attn_out_ffn_fused: dtype must be bf16 or f16");
+    KINET_CHECK_ARG(bo != nullptr && g1 != nullptr && be1 != nullptr, "attn_out_ffn_fused: bo and the first LayerNorm's gamma and beta are required");
+    KINET_CHECK_ARG(b1 != nullptr && b2 != nullptr, "attn_out_ffn_fused: b1 and b2 are required");
+    KINET_CHECK_ARG((g2 == nullptr) == (be2 == nullptr), "attn_out_ffn_fused: the second LayerNorm needs both gamma and beta");
+    KINET_CHECK_ARG(al16(A) && al16(R) && al16(Y) && al16(packed) && al16(bo) && al16(g1) && al16(be1) && al16(b1) &&
+                    al16(b2) && (g2 == nullptr || (al16(g2) && al16(be2))),
+                    "attn_out_ffn_fused: A, R, Y, packed weights, biases and LayerNorm params must be 16-byte aligned");
+    if (M == 0) return KINET_OK;
+    const long long ab = ((long long)(M - 1) * lda + D) * 2, rb = ((long long)(M - 1) * ldr + D) * 2;
+    const long long yb = ((long long)(M - 1) * ldy + D) * 2;
+    KINET_CHECK_ARG(ab < (1LL << 31) && rb < (1LL << 31) && yb < (1LL << 31),
+                    "attn_out_ffn_fused: A, R or Y larger than 2 GiB (split the call)");
+    auto overlap = [](const void* u, long long ub, const void* v, long long vb) {
+        return (const char*)u < (const char*)v + vb && (const char*)v < (const char*)u + ub;
+    };
+    KINET_CHECK_ARG(!overlap(Y, yb, A, ab) && !overlap(Y, yb, R, rb), "attn_out_ffn_fused: Y must not alias A or R");
+    FfnArgs a{};
+    a.W = packed; a.b1 = b1; a.b2 = b2; a.ln_g = g2; a.ln_b = be2; a.Y = Y; a.eps = eps2;
+    a.ldy = ldy; a.M = M; a.F = F;
+    a.w_bytes = (int)(((long long)D * D + 2LL * D * F) * 2);
+    a.y_bytes = (int)yb;
+    a.dbg = ffn_debug;
+    a.A = A; a.R = R; a.bo = bo; a.g1 = g1; a.be1 = be1; a.eps1 = eps1;
+    a.lda = lda; a.ldr = ldr; a.a_bytes = (int)ab; a.r_bytes = (int)rb;
+    if (dtype == KINET_BF16) launch_attn_out_ffn<bf16_t>(a, (hipStream_t)stream);
+    else launch_attn_out_ffn<f16_t>(a, (hipStream_t)stream);
     KINET_LAUNCH_CHECK();
     return KINET_OK;
 }

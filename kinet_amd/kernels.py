@@ -252,6 +252,73 @@ def ffn_fused(x, linear1, linear2, norm=None, out=None):
     return out.view(*x.shape[:-1], D)
 
 
+ATTN_OUT_FFN_MIN_ROWS = 16384   # launch_ffn (csrc/ffn.hip) takes the 8-wave x 32-row tile from here
+
+
+def attn_out_ffn_supported(x, out_proj, linear1, linear2):
+    """The out-projection + LayerNorm pre-phase exists on the 8-wave x 32-row FFN tile only:
+    16-bit compute modes, d_model 256, every bias present, and enough rows (x: (..., D)) for
+    launch_ffn to pick that tile.  Looks at shapes and dtypes only."""
+    D = x.shape[-1]
+    M = x.numel() // D if D else 0
+    F_ = linear1.weight.shape[0]
+    return (x.dtype in (torch.bfloat16, torch.float16) and D == 256 and tuple(out_proj.weight.shape) == (D, D)
+            and F_ % 32 == 0 and M >= ATTN_OUT_FFN_MIN_ROWS and out_proj.bias is not None
+            and linear1.bias is not None and linear2.bias is not None)
+
+
+def attn_out_ffn_pack(wo, w1, w2, dtype):
+    """kinet_ffn_pack_attn of (Wo (D, D), W1 (F, D), W2 (D, F)), cached per parameter version."""
+    def make(o, a, b):
+        F_, D = a.shape
+        o16 = o.detach().to(dtype).contiguous()
+        a16 = a.detach().to(dtype).contiguous()
+        b16 = b.detach().to(dtype).contiguous()
+        out = torch.empty(D * D + 2 * D * F_, dtype=dtype, device=a.device)
+        N.call('kinet_ffn_pack_attn', N.ptr(o16), N.ptr(a16), N.ptr(b16), N.ptr(out), D, F_, N.dtype_code(dtype),
+               N.stream(a.device))
+        return out
+    return cached_multi([wo, w1, w2], ('attn_out_ffn_pack', dtype), make)
+
+
+def attn_out_ffn_fused(samp, out_proj, residual, norm1, linear1, linear2, norm2, out=None, force=False):
+    """y = norm2(x + linear2(relu(linear1(x)))) with x = norm1(residual + out_proj(samp)) in one
+    launch (deformable_transformer.py:290-299 after the sampler): x is rounded to the 16-bit type
+    once, after norm1, and stays on chip.  samp, residual (..., D) bf16/f16; norm2 may be None.
+    force=True skips the row-count gate (the kernel is correct for any M; tests)."""
+    N.require_gpu(samp, residual)
+    if not force and not attn_out_ffn_supported(samp, out_proj, linear1, linear2):
+        raise RuntimeError('attn_out_ffn_fused: unsupported shape / dtype (see attn_out_ffn_supported)')
+    D = samp.shape[-1]
+    F_ = linear1.weight.shape[0]
+
+    def rows(t):
+        t2 = t.reshape(-1, D)
+        if t2.stride(-1) != 1 or t2.stride(0) % 8 or t2.data_ptr() % 16:
+            t2 = t2.contiguous()
+        return t2
+    a2, r2 = rows(samp), rows(residual)
+    if r2.dtype != samp.dtype or r2.shape != a2.shape:
+        raise RuntimeError('attn_out_ffn_fused: residual must match samp in shape and dtype')
+    M = a2.shape[0]
+    wp = attn_out_ffn_pack(out_proj.weight, linear1.weight, linear2.weight, samp.dtype)
+    if out is None:
+        out = torch.empty((M, D), dtype=samp.dtype, device=samp.device)
+    elif out.dtype != samp.dtype or out.stride(-1) != 1 or out.numel() != M * D:
+        raise RuntimeError('attn_out_ffn_fused: out must be a unit-stride (M, D) tensor of the input dtype')
+    if norm1 is None or out_proj.bias is None:
+        raise RuntimeError('attn_out_ffn_fused: the out-projection bias and norm1 are required')
+    g2, b2, eps2 = (f32(norm2.weight), f32(norm2.bias), float(norm2.eps)) if norm2 is not None else (None, None, 0.0)
+    e = samp.element_size()
+    work = {'family': 'gemm', 'flops': 4.0 * M * D * F_ + 2.0 * M * D * D, 'shape': ('ffn', M, D, F_, 'attn_out'),
+            'bytes': (3 * M * D + D * D + 2 * D * F_) * e}
+    N.call('kinet_attn_out_ffn_fused', N.ptr(a2), a2.stride(0), N.ptr(r2), r2.stride(0), N.ptr(wp),
+           N.ptr(f32(out_proj.bias)), N.ptr(f32(norm1.weight)), N.ptr(f32(norm1.bias)), float(norm1.eps),
+           N.ptr(f32(linear1.bias)), N.ptr(f32(linear2.bias)), N.ptr(g2), N.ptr(b2), eps2, N.ptr(out), D, M, D, F_,
+           N.dtype_code(samp.dtype), N.stream(samp.device), work=work)
+    return out.view(*samp.shape[:-1], D)
+
+
 def value_proj_headmajor(x, weight, bias, head_dim, row_mask=None, out_dtype=None):
     """MSDA value projection written head-major: x (B, S, K) -> (Nout/head_dim, B, S, head_dim),
     padding rows zeroed (ms_deform_attn.py:64-67).  out_dtype: x.dtype, or float16 from bf16

@@ -50,6 +50,10 @@ def _get_activation_fn(activation):
 
 _FORCE_REFERENCE = [0]
 
+# Encoder layers (inference path): the attention out-projection + norm1 run inside the fused FFN
+# launch (kinet_attn_out_ffn_fused) where K.attn_out_ffn_supported holds; False = the two launches
+FUSE_ATTN_OUT_FFN = True
+
 
 def _active_dropout(module):
     return module.training and any(isinstance(m, (nn.Dropout, nn.MultiheadAttention)) and
@@ -118,6 +122,8 @@ class DeformableTransformerEncoderLayer(nn.Module):
         samp = a.sample(src, reference_points, value, spatial_shapes, query_add=pos,   # (src+pos) @ W
                         query_order=query_order, shapes_host=shapes_host)
         n1, n2 = self.norm1, self.norm2
+        if FUSE_ATTN_OUT_FFN and K.attn_out_ffn_supported(samp, a.output_proj, self.linear1, self.linear2):
+            return K.attn_out_ffn_fused(samp, a.output_proj, src, n1, self.linear1, self.linear2, n2)
         src = K.linear(samp, a.output_proj.weight, a.output_proj.bias, residual=src, ln=(n1.weight, n1.bias, n1.eps))
         if K.ffn_supported(src, self.linear1, self.linear2):
             return K.ffn_fused(src, self.linear1, self.linear2, n2)
