@@ -70,9 +70,15 @@ int kinet_mha_core_dropout(const void* Q, int ldq, const void* Kt, int ldk, cons
 int kinet_dropout_mask(const int64_t* dropout_seed, int64_t n, float dropout_p, uint8_t* keep,
                        kinet_stream_t stream);
 
-/* Diagnostic knob (no reference counterpart): 1 (default) = kinet_mha_core runs head_dim 32,
- * bf16/f16, Lk <= 384 on the MFMA kernel (attn.hip), 0 = always the FMA kernel.  Returns the
- * previous setting. */
+/* Diagnostic knob (no reference counterpart) for kinet_mha_core on bf16 / f16, head_dim 32
+ * (row strides % 8, 16-byte pointers) or 36 (row strides % 4, 8-byte pointers), no dropout:
+ *   1 (default) = the MFMA kernels of attn.hip: keys resident in LDS up to Lk 384 (head_dim 32)
+ *                 / 640 (head_dim 36), the key-streaming kernel for longer key sets;
+ *   0           = always the FMA kernel;
+ *   2           = the key-streaming kernel for every such call whatever Lk (tests reach its
+ *                 tile edges at small sizes).
+ * Every other call (fp32, dropout, other head dims, unaligned operands) runs the FMA kernel at
+ * any setting.  Per calling thread.  Returns the previous setting. */
 int kinet_mha_set_mfma(int enable);
 
 /* Iterative box refinement (deformable_transformer.py:414-425) fused with the next

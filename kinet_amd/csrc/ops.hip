@@ -767,10 +767,11 @@ extern "C" int kinet_add(const void* a, const void* b, void* y, int64_t n, int d
 }
 
 namespace kinet {
-// attn.hip: the MFMA kernel for head_dim 32, 16-bit, Lk <= 384 (false = not covered)
+// attn.hip: the MFMA kernels for 16-bit head_dim 32 / 36 (false = not covered): resident keys up
+// to 384 / 640, the key-streaming kernel above that (mode 2: the streaming kernel at any Lk)
 bool launch_mha_mfma(const void* Q, int ldq, const void* Kt, int ldk, const void* V, int ldv, void* O, int ldo,
                      int batch, int Lq, int Lk, int heads, int head_dim, float scale, int dtype,
-                     const uint8_t* key_mask, hipStream_t stream);
+                     const uint8_t* key_mask, int mode, hipStream_t stream);
 thread_local int mha_use_mfma = 1;   // test-only knob (kinet_mha_set_mfma), per calling thread
 }  // namespace kinet
 
@@ -793,7 +794,7 @@ static int mha_core_impl(const void* Q, int ldq, const void* Kt, int ldk, const 
     const bool drop = dropout_p > 0.f;
     if (!drop && kinet::mha_use_mfma &&
         kinet::launch_mha_mfma(Q, ldq, Kt, ldk, V, ldv, O, ldo, batch, Lq, Lk, heads, head_dim, scale, dtype, key_mask,
-                               s)) {
+                               kinet::mha_use_mfma == 2 ? 2 : 1, s)) {
         KINET_LAUNCH_CHECK();
         return KINET_OK;
     }

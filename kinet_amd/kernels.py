@@ -716,9 +716,17 @@ def dropout_mask(seed, n, p):
     return keep
 
 
+# csrc/attn.hip: the 16-bit head_dim 32 / 36 MFMA kernels keep a head's keys resident in LDS up
+# to these Lk; longer key sets run the key-streaming kernel in tiles of MHA_STREAM_KT keys
+MHA_RESIDENT_MAXK = {32: 384, 36: 640}
+MHA_STREAM_KT = 128
+
+
 def mha_core(q, k, v, heads, scale, key_mask=None, out=None, dropout_p=0.0, seed=None):
     """q (B, Lq, E) (row stride may exceed E), k/v (B, Lk, E) -> (B, Lq, E).  dropout_p > 0:
-    attention-probability dropout with the keep mask of `seed` (kinet_mha_core_dropout)."""
+    attention-probability dropout with the keep mask of `seed` (kinet_mha_core_dropout).
+    No dropout, bf16 / f16, head_dim 32 / 36: the MFMA kernels of csrc/attn.hip (keys resident
+    in LDS up to MHA_RESIDENT_MAXK, streamed above); everything else the FMA kernel."""
     B, Lq, E = q.shape
     Lk = k.shape[1]
     D = E // heads

@@ -1,20 +1,23 @@
-"""`build_model(args) -> (model, criterion, postprocessors)` for the detection hot path,
-mirroring src/trackformer/models/__init__.py:16-71 (deformable branch).
+"""`build_model(args) -> (model, criterion, postprocessors)`, mirroring
+src/trackformer/models/__init__.py:16-125.
 
     from kinet_amd.models import build_model      # instead of trackformer.models
     model, criterion, postprocessors = build_model(args)
     model.set_compute_dtype(torch.bfloat16)        # optional perf mode (default fp32)
 
-`args` is the reference's Namespace (cfgs/train.yaml + named configs).  The deformable image
-branch (the hot path) and the KineT kinematic branch (`args.kine`, :72-107,
-kinet_amd/models/kinet.py) are built; vanilla DETR / masks raise.
+`args` is the reference's Namespace (cfgs/train.yaml + named configs).  All three model
+families are built: the deformable image branch (:51-71, the hot path), the KineT kinematic
+branch (`args.kine`, :72-107, kinet_amd/models/kinet.py) and vanilla DETR (:111-125, the
+reference's default `deformable: false`; kinet_amd/models/detr.py, inference only).  The
+segmentation heads (`masks`) raise.
 """
 import torch
 
 from kinet_amd.models.backbone import build_backbone
 from kinet_amd.models.deformable_detr import DeformableDETR, DeformablePostProcess, PostProcess
 from kinet_amd.models.deformable_transformer import build_deforamble_transformer
-from kinet_amd.models.detr_tracking import DeformableDETRTracking
+from kinet_amd.models.detr import DETR
+from kinet_amd.models.detr_tracking import DeformableDETRTracking, DETRTracking
 from kinet_amd.models.misc import NestedTensor, NestedTensorKinet, nested_tensor_from_tensor_list
 
 NUM_CLASSES = {'coco': 91, 'coco_panoptic': 250, 'coco_person': 20, 'mot': 20, 'mot_crowdhuman': 20,
@@ -33,10 +36,10 @@ def build_model(args):
         model = build_kinet(args, num_classes)
         post = {'bbox': DeformablePostProcess() if args.focal_loss else PostProcess()}
         return model, build_criterion(args, num_classes, matcher), post
-    if not args.deformable:
-        raise NotImplementedError('vanilla DETR (config 1) is outside the MSDeformAttn hot path')
     if getattr(args, 'masks', False):
         raise NotImplementedError('segmentation heads are outside the hot path')
+    if not args.deformable:
+        return _build_detr(args, num_classes)
     backbone = build_backbone(args)
     matcher = None
     try:
@@ -77,5 +80,33 @@ def build_model(args):
     return model, criterion, postprocessors
 
 
-__all__ = ['build_model', 'DeformableDETR', 'DeformableDETRTracking', 'DeformablePostProcess', 'PostProcess',
+def _build_detr(args, num_classes):
+    """models/__init__.py:111-125: vanilla DETR (config 1).  As there, multi_frame_* are not
+    passed on to the model."""
+    from kinet_amd.models.criterion import build_criterion
+    from kinet_amd.models.matcher import build_matcher
+    from kinet_amd.models.transformer import build_transformer
+    matcher = build_matcher(args)
+    detr_kwargs = {
+        'backbone': build_backbone(args),
+        'num_classes': num_classes - 1 if args.focal_loss else num_classes,
+        'num_queries': args.num_queries,
+        'aux_loss': args.aux_loss,
+        'overflow_boxes': args.overflow_boxes,
+        'transformer': build_transformer(args),
+    }
+    if args.tracking:
+        tracking_kwargs = {
+            'track_query_false_positive_prob': args.track_query_false_positive_prob,
+            'track_query_false_negative_prob': args.track_query_false_negative_prob,
+            'matcher': matcher,
+            'backprop_prev_frame': args.track_backprop_prev_frame}
+        model = DETRTracking(tracking_kwargs, detr_kwargs)
+    else:
+        model = DETR(**detr_kwargs)
+    post = {'bbox': DeformablePostProcess() if args.focal_loss else PostProcess()}
+    return model, build_criterion(args, num_classes, matcher), post
+
+
+__all__ = ['build_model', 'DETR', 'DETRTracking', 'DeformableDETR', 'DeformableDETRTracking', 'DeformablePostProcess', 'PostProcess',
            'NestedTensor', 'NestedTensorKinet', 'nested_tensor_from_tensor_list']

@@ -1,7 +1,7 @@
 """Configuration values of the detection path (the reference's Sacred YAMLs, as data).
 
 DEFAULTS are the keys of cfgs/train.yaml that build_model and the detector read; NAMED
-are the named configs layered on top (cfgs/train_deformable.yaml, train_multi_frame.yaml,
+are the named configs layered on top (cfgs/train_detr.yaml, train_deformable.yaml, train_multi_frame.yaml,
 train_tracking.yaml, train_mot17.yaml, train_full_res.yaml, train_kinet.yaml).  `load_args(*names, **kw)`
 returns the argparse.Namespace build_model expects (util/misc.py:668-674 equivalent).
 """
@@ -30,6 +30,8 @@ DEFAULTS = dict(
 )
 
 NAMED = {
+    # cfgs/train_detr.yaml: vanilla DETR at the tracking stack's width (BASELINE configs[0])
+    'train_detr': dict(multi_frame_encoding=False, num_queries=500, hidden_dim=288, activation='relu'),
     'train_deformable': dict(deformable=True, num_feature_levels=4, num_queries=300, dim_feedforward=1024,
                              focal_loss=True, focal_alpha=0.25, focal_gamma=2, cls_loss_coef=2.0,
                              set_cost_class=2.0, overflow_boxes=True, with_box_refine=True, activation='relu'),

@@ -1,5 +1,5 @@
 """Track-query wrapper of the detector (src/trackformer/models/detr_tracking.py:16-283,
-DeformableDETRTracking :892-895).
+DETRTracking :886-889, DeformableDETRTracking :892-895).
 
 Tracking mode (`model.tracking()`, used by the online tracker, tracker.py:309): the
 caller passes `targets=[{'track_query_hs_embeds': (K, d), 'track_query_boxes': (K, 4)}]`
@@ -13,6 +13,7 @@ import torch
 from torch import nn
 
 from kinet_amd.models.deformable_detr import DeformableDETR
+from kinet_amd.models.detr import DETR
 
 
 class DETRTrackingBase(nn.Module):
@@ -45,4 +46,12 @@ class DETRTrackingBase(nn.Module):
 class DeformableDETRTracking(DETRTrackingBase, DeformableDETR):
     def __init__(self, tracking_kwargs, detr_kwargs):
         DeformableDETR.__init__(self, **detr_kwargs)
+        DETRTrackingBase.__init__(self, **tracking_kwargs)
+
+
+class DETRTracking(DETRTrackingBase, DETR):
+    """Vanilla DETR with track queries (tracking mode; DETR itself runs inference only)."""
+
+    def __init__(self, tracking_kwargs, detr_kwargs):
+        DETR.__init__(self, **detr_kwargs)
         DETRTrackingBase.__init__(self, **tracking_kwargs)

@@ -91,6 +91,16 @@ def _layer_norm(x, ln, fast, residual=None):
     return A.layer_norm(x if residual is None else x + residual, ln)
 
 
+def _ffn(layer, x, norm, drop, fast):
+    """norm(x + drop(linear2(dropout(relu(linear1(x)))))), the tail of a post-norm layer.  Layers with
+    `fused_ffn` (vanilla DETR, models/transformer.py) run it as the one-launch fused FFN where
+    K.ffn_supported holds; otherwise two GEMMs with fused epilogues."""
+    if fast and layer.fused_ffn and K.ffn_supported(x, layer.linear1, layer.linear2):
+        return K.ffn_fused(x, layer.linear1, layer.linear2, norm)
+    h = _linear(x, layer.linear1, fast, relu=True, drop=layer.dropout)
+    return _linear(h, layer.linear2, fast, residual=x, ln=norm, drop=drop)
+
+
 def _mlp(mlp, x, fast):
     """detr.py:937-951 MLP (ReLU between layers)."""
     n = len(mlp.layers)
@@ -189,12 +199,16 @@ class TransformerEncoderLayer(nn.Module):
         self.dropout1 = nn.Dropout(dropout)
         self.dropout2 = nn.Dropout(dropout)
 
+    fused_ffn = False   # see _ffn
+
     def run(self, src, pos, key_padding_mask, fast):
         sa = self.self_attn
         o = _attention(sa, src, src, src, fast, q_add=pos, k_add=pos, key_padding_mask=key_padding_mask)
+        if fast and self.fused_ffn and K.attn_out_ffn_supported(o, sa.out_proj, self.linear1, self.linear2):
+            # out_proj + residual + norm1 + FFN + norm2 in one launch
+            return K.attn_out_ffn_fused(o, sa.out_proj, src, self.norm1, self.linear1, self.linear2, self.norm2)
         src = _linear(o, sa.out_proj, fast, residual=src, ln=self.norm1, drop=self.dropout1)
-        h = _linear(src, self.linear1, fast, relu=True, drop=self.dropout)
-        return _linear(h, self.linear2, fast, residual=src, ln=self.norm2, drop=self.dropout2)
+        return _ffn(self, src, self.norm2, self.dropout2, fast)
 
 
 class TransformerDecoderLayer(nn.Module):
@@ -216,6 +230,8 @@ class TransformerDecoderLayer(nn.Module):
         self.dropout2 = nn.Dropout(dropout)
         self.dropout3 = nn.Dropout(dropout)
 
+    fused_ffn = False   # see _ffn
+
     def run(self, tgt, memory, pos, query_pos, memory_key_padding_mask, fast):
         sa, ca = self.self_attn, self.multihead_attn
         o = _attention(sa, tgt, tgt, tgt, fast, q_add=query_pos, k_add=query_pos)
@@ -223,8 +239,7 @@ class TransformerDecoderLayer(nn.Module):
         o = _attention(ca, tgt, memory, memory, fast, q_add=query_pos, k_add=pos,
                        key_padding_mask=memory_key_padding_mask)
         tgt = _linear(o, ca.out_proj, fast, residual=tgt, ln=self.norm2, drop=self.dropout2)
-        h = _linear(tgt, self.linear1, fast, relu=True, drop=self.dropout)
-        return _linear(h, self.linear2, fast, residual=tgt, ln=self.norm3, drop=self.dropout3)
+        return _ffn(self, tgt, self.norm3, self.dropout3, fast)
 
 
 class TransformerEncoder(nn.Module):

@@ -92,7 +92,8 @@ class Tracker:
     def __init__(self, obj_detector, obj_detector_post, tracker_cfg, generate_attention_maps=False, logger=None,
                  verbose=False):
         if generate_attention_maps:
-            raise NotImplementedError('attention maps need a vanilla-DETR decoder (tracker.py:38-40)')
+            raise NotImplementedError('attention maps (tracker.py:38-40) need the decoder\'s attention '
+                                      'probabilities, which the fused attention kernels do not export')
         self.obj_detector = obj_detector
         self.obj_detector_post = obj_detector_post
         self.detection_obj_score_thresh = tracker_cfg['detection_obj_score_thresh']
