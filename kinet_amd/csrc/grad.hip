@@ -520,17 +520,42 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
 }
 
 // ------------------------------------------------------------------------- GroupNorm bwd
-// x, dy: (N, HW, C) NHWC.  pass 1 per (image, HW block): per-channel sums of dy, dy*x, x, x^2
+// x, dy: (N, HW, C) NHWC.  Every sum is taken of x - pivot, the pivot of (image, group) being the
+// mean of the group's first (up to 8) channels at its first (up to 4) pixels: the one-pass
+// variance E[x^2] - mean^2 and dy.x - mean dy cancel against the data's offset otherwise
+// (x = 30 + randn: 3 digits lost).  Every kernel forms the pivot with the same serial sum, so
+// they agree bit for bit.
+template <typename T>
+__device__ __forceinline__ float gn_pivot(const T* x, int n, int HW, int C, int cg, int c) {
+    const T* p = x + (long)n * HW * C + (c / cg) * cg;
+    const int m = min(cg, 8), np = min(HW, 4);
+    // all 32 (predicated) loads in flight at once, then one serial sum: a loop over the live
+    // samples waits out a memory latency per element
+    float v[4][8];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[q][k] = (q < np && k < m) ? ld(p + (long)q * C + k) : 0.f;
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += v[q][k];
+    return s / (float)(m * np);
+}
+
+// pass 1 per (image, HW block): per-channel sums of dy, dy*x, x, x^2 (x shifted by the pivot)
 template <typename T>
 __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const T* __restrict__ dy, const T* __restrict__ x,
-                                                             float* __restrict__ part, int HW, int C, int rb) {
+                                                             float* __restrict__ part, int HW, int C, int rb, int cg) {
     const int n = blockIdx.y, blk = blockIdx.x, nblk = gridDim.x;
     const int p0 = blk * rb, p1 = min(HW, p0 + rb);
     for (int c = threadIdx.x; c < C; c += 256) {
+        const float pv = gn_pivot(x, n, HW, C, cg, c);
         float sdy = 0.f, sdyx = 0.f, sx = 0.f, sxx = 0.f;
         for (int p = p0; p < p1; ++p) {
             const long o = ((long)n * HW + p) * C + c;
-            const float xv = ld(x + o), dv = ld(dy + o);
+            const float xv = ld(x + o) - pv, dv = ld(dy + o);
             sdy += dv;
             sdyx += dv * xv;
             sx += xv;
@@ -550,14 +575,22 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const T* __restrict
 // sums are added in LDS in a fixed order (deterministic)
 template <typename T>
 __global__ __launch_bounds__(256) void gn_bwd_partial_vec_kernel(const T* __restrict__ dy, const T* __restrict__ x,
-                                                                 float* __restrict__ part, int HW, int C, int rb) {
+                                                                 float* __restrict__ part, int HW, int C, int rb,
+                                                                 int cg) {
     __shared__ float red[4 * 1024];   // [row group][4 sums][C], rows_per_it * C <= 1024
     const int n = blockIdx.y, blk = blockIdx.x, nblk = gridDim.x;
     const int p0 = blk * rb, p1 = min(HW, p0 + rb);
     const int C4 = C >> 2, rpi = 256 / C4;
     const int tr = threadIdx.x / C4, tc = threadIdx.x - tr * C4;
     float a[4][4] = {};
+    // one pivot per group, formed once per workgroup (C <= 1024, so at most 1024 groups)
+    __shared__ float pvs[1024];
+    for (int g = threadIdx.x; g < C / cg; g += 256) pvs[g] = gn_pivot(x, n, HW, C, cg, g * cg);
+    __syncthreads();
     if (tr < rpi) {
+        float pv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pv[j] = pvs[(tc * 4 + j) / cg];
         for (int p = p0 + tr; p < p1; p += rpi) {
             const long o = ((long)n * HW + p) * C + tc * 4;
             float xv[4], dv[4];
@@ -571,6 +604,7 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_vec_kernel(const T* __rest
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
+                xv[j] -= pv[j];
                 a[0][j] += dv[j];
                 a[1][j] += dv[j] * xv[j];
                 a[2][j] += xv[j];
@@ -593,10 +627,12 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_vec_kernel(const T* __rest
 // pass 2 (one workgroup per image): per-channel sums over the blocks, then per group the
 // statistics and the two backward scalars; writes stats[n][g] = (mean, rstd, a/cnt, bsum/cnt)
 // and per-image channel sums for dgamma / dbeta
+template <typename T>
 __global__ __launch_bounds__(1024) void gn_bwd_stats_kernel(const float* __restrict__ part, const float* __restrict__ gamma,
-                                                            float* __restrict__ stats, float* __restrict__ chan,
-                                                            int HW, int C, int G, int nblk, float eps) {
-    extern __shared__ float sm[];   // [4][C]
+                                                            const T* __restrict__ x, float* __restrict__ stats,
+                                                            float* __restrict__ chan, int HW, int C, int G, int nblk,
+                                                            float eps) {
+    extern __shared__ float sm[];   // [4][C] sums of the shifted data, [G] shifted means
     const int n = blockIdx.x;
     // one (sum, channel) per thread, the blocks summed in order (4 independent loads in flight)
     for (int i = threadIdx.x; i < 4 * C; i += blockDim.x) {
@@ -623,13 +659,14 @@ __global__ __launch_bounds__(1024) void gn_bwd_stats_kernel(const float* __restr
             bs += gamma[c] * sm[C + c];
         }
         const float cnt = (float)HW * (float)cg;
-        const float mean = sx / cnt;
+        const float mean = sx / cnt;   // of x - pivot
         const float var = fmaxf(sxx / cnt - mean * mean, 0.f);
         const float rstd = rsqrtf(var + eps);
         // sum(dy*gamma*xhat) = rstd * (sum(dy*gamma*x) - mean * sum(dy*gamma))
         const float bx = rstd * (bs - mean * a);
         float* st4 = stats + ((long)n * G + g) * 4;
-        st4[0] = mean;
+        sm[4 * C + g] = mean;
+        st4[0] = gn_pivot(x, n, HW, C, cg, g * cg) + mean;
         st4[1] = rstd;
         st4[2] = a / cnt;
         st4[3] = bx / cnt;
@@ -637,8 +674,8 @@ __global__ __launch_bounds__(1024) void gn_bwd_stats_kernel(const float* __restr
     __syncthreads();
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         const float* st4 = stats + ((long)n * G + c / cg) * 4;
-        // dgamma_n[c] = sum dy*xhat = rstd*(sum dy*x - mean*sum dy); dbeta_n[c] = sum dy
-        chan[((long)n * 2) * C + c] = st4[1] * (sm[C + c] - st4[0] * sm[c]);
+        // dgamma_n[c] = sum dy*xhat = rstd*(sum dy*(x - pivot) - (mean - pivot)*sum dy); dbeta_n[c] = sum dy
+        chan[((long)n * 2) * C + c] = st4[1] * (sm[C + c] - sm[4 * C + c / cg] * sm[c]);
         chan[((long)n * 2 + 1) * C + c] = sm[c];
     }
 }
@@ -1123,8 +1160,12 @@ extern "C" int kinet_layernorm_backward(const void* dy, const void* x, const flo
                                         float* dbeta, int rows, int d, float eps, int dtype, float* workspace,
                                         kinet_stream_t stream) {
     KINET_CHECK_ARG(d > 0 && d <= 1024 && rows >= 0 && workspace && gamma, "layernorm_backward: bad arguments");
-    if (rows == 0) return KINET_OK;
     hipStream_t s = (hipStream_t)stream;
+    if (rows == 0) {   // no rows: the parameter gradients are empty sums
+        if (dgamma) KINET_CHECK_HIP(hipMemsetAsync(dgamma, 0, sizeof(float) * d, s));
+        if (dbeta) KINET_CHECK_HIP(hipMemsetAsync(dbeta, 0, sizeof(float) * d, s));
+        return KINET_OK;
+    }
     const int rpw = 16;
     const int blocks = (rows + 4 * rpw - 1) / (4 * rpw);
     float* pg = workspace;
@@ -1155,8 +1196,12 @@ extern "C" int kinet_groupnorm_backward(const void* dy, const void* x, const flo
                                         float* workspace, kinet_stream_t stream) {
     KINET_CHECK_ARG(N >= 0 && HW > 0 && C > 0 && groups > 0 && C % groups == 0 && workspace && gamma,
                     "groupnorm_backward: bad arguments");
-    if (N == 0) return KINET_OK;
     hipStream_t s = (hipStream_t)stream;
+    if (N == 0) {   // no images: the parameter gradients are empty sums
+        if (dgamma) KINET_CHECK_HIP(hipMemsetAsync(dgamma, 0, sizeof(float) * C, s));
+        if (dbeta) KINET_CHECK_HIP(hipMemsetAsync(dbeta, 0, sizeof(float) * C, s));
+        return KINET_OK;
+    }
     const int nb = gn_blocks(HW);
     const int rb = (HW + nb - 1) / nb;
     float* part = workspace;
@@ -1167,13 +1212,13 @@ extern "C" int kinet_groupnorm_backward(const void* dy, const void* x, const flo
 #define GN_BWD(T)                                                                                                  \
     if (vec)                                                                                                       \
         hipLaunchKernelGGL(gn_bwd_partial_vec_kernel<T>, dim3(nb, N), dim3(256), 0, s, (const T*)dy, (const T*)x, part, \
-                           HW, C, rb);                                                                             \
+                           HW, C, rb, C / groups);                                                                 \
     else                                                                                                           \
         hipLaunchKernelGGL(gn_bwd_partial_kernel<T>, dim3(nb, N), dim3(256), 0, s, (const T*)dy, (const T*)x, part, HW, \
-                           C, rb);                                                                                 \
+                           C, rb, C / groups);                                                                     \
     KINET_LAUNCH_CHECK();                                                                                          \
-    hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(N), dim3(1024), 4 * (size_t)C * sizeof(float), s, part, gamma, stats, \
-                       chan, HW, C, groups, nb, eps);                                                              \
+    hipLaunchKernelGGL(gn_bwd_stats_kernel<T>, dim3(N), dim3(1024), (4 * (size_t)C + groups) * sizeof(float), s, part, \
+                       gamma, (const T*)x, stats, chan, HW, C, groups, nb, eps);                                   \
     KINET_LAUNCH_CHECK();                                                                                          \
     if (vec && total < (1L << 31) && ((uintptr_t)dx % 16) == 0)                                                 \
         hipLaunchKernelGGL(gn_bwd_apply_vec_kernel<T>, dim3(grid_for(total / 4)), dim3(256), 0, s, (const T*)dy,    \

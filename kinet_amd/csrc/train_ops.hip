@@ -562,7 +562,8 @@ using namespace kinet;
 extern "C" int kinet_dropout_add_layernorm(const float* x, const float* r, const float* gamma, const float* beta, float* y,
                                            int rows, int d, float eps, float dropout_p, const int64_t* dropout_seed,
                                            kinet_stream_t stream) {
-    KINET_CHECK_ARG(rows >= 0 && d > 0 && d <= 1024 && x && r && gamma && beta && y && dropout_seed,
+    // an empty input (rows == 0) comes with null row pointers
+    KINET_CHECK_ARG(rows >= 0 && d > 0 && d <= 1024 && (rows == 0 || (x && r && y)) && gamma && beta && dropout_seed,
                     "dropout_add_layernorm: bad arguments (d must be in [1, 1024])");
     KINET_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "dropout_add_layernorm: p must be in [0, 1)");
     if (rows == 0) return KINET_OK;
@@ -598,7 +599,7 @@ extern "C" int kinet_dropout_add_layernorm_backward(const float* dy, const float
                                                     float* dx, float* dr, float* dgamma, float* dbeta, int rows, int d,
                                                     float eps, float dropout_p, const int64_t* dropout_seed,
                                                     float* workspace, kinet_stream_t stream) {
-    KINET_CHECK_ARG(rows >= 0 && d > 0 && d <= 1024 && dy && x && r && gamma && dropout_seed,
+    KINET_CHECK_ARG(rows >= 0 && d > 0 && d <= 1024 && (rows == 0 || (dy && x && r)) && gamma && dropout_seed,
                     "dropout_add_layernorm_backward: bad arguments");
     KINET_CHECK_ARG((dgamma == nullptr) == (dbeta == nullptr) && (!dgamma || workspace),
                     "dropout_add_layernorm_backward: dgamma and dbeta together, with a workspace");

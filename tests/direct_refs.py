@@ -1,9 +1,11 @@
 """High-precision restatements of the small kernels' operations, shared by
-test_ops_direct_gpu.py / test_grad_prims_gpu.py and checked on the CPU by test_direct_refs_cpu.py.
+test_ops_direct_gpu.py / test_grad_prims_gpu.py / test_grad_norm_attn_gpu.py /
+test_train_ops_direct_gpu.py and checked on the CPU by test_direct_refs_cpu.py.
 Plain torch on the CPU; nothing here touches the GPU or the native library."""
 import functools
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -251,3 +253,375 @@ def tn_operands(K, M, N, dtype, seed=0):
     a = torch.randn(K, M, generator=g).to(dtype)
     b = torch.randn(K, N, generator=g).to(dtype)
     return a, b, a.double().T @ b.double()
+
+
+# =================================================== training path: csrc/grad.hip, csrc/train_ops.hip
+# Bounds are per element: bound_i = c * U32 * A_i (+ OUT_ROUND * |ref_i| for a 16-bit output), A_i the
+# reference's formula on absolute values (the running-error majorant), c the length of the longest
+# sequential f32 chain an element passes through, derived beside each constant below.
+F32_TINY = 2.0 ** -126                                            # below it f32 results lose bits / flush
+
+
+def eps32(eps):
+    """The launchers take eps as a float: the f64 references use the same rounded value."""
+    return float(np.float32(eps))
+
+
+# ------------------------------------------------------------------------ dropout hash
+def dropout_thresh_ref(p):
+    """uint32(double(float32(p)) * 2^24 + 0.5): p is rounded to f32 first (0.1 -> 1677721)."""
+    t = float(np.float32(p)) * 16777216.0 + 0.5
+    return 16777216 if t >= 16777216.0 else (0 if t <= 0.0 else int(t))
+
+
+def dropout_keep_ref(seed, idx, p):
+    """The keep decision of common.h's dropout_keep restated in numpy uint64 (wraparound):
+    z = seed + idx * golden; two xor-shift-multiply rounds of the splitmix64 finaliser; z ^= z >> 31;
+    kept iff the top 24 bits >= thresh.  seed is an int64 (negative seeds wrap), idx any shape."""
+    s = np.array([seed], dtype=np.int64).astype(np.uint64)
+    z = s + np.atleast_1d(np.asarray(idx)).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    z = z ^ (z >> np.uint64(31))
+    return (z >> np.uint64(40)) >= np.uint64(dropout_thresh_ref(p))
+
+
+def dropout_seed_for_draw(draw, idx, low=0x5A5A5A5A5A):
+    """The int64 seed for which element idx's 24-bit uniform draw is exactly `draw` (every step of
+    the hash is a bijection mod 2^64, inverted here in Python integers): a seed that sits on the
+    threshold, or one below it, at a chosen element."""
+    m = (1 << 64) - 1
+    z = ((draw << 40) | low) & m
+    z = z ^ (z >> 31) ^ (z >> 62)
+    z = (z * pow(0x94D049BB133111EB, -1, 1 << 64)) & m
+    z = z ^ (z >> 27) ^ (z >> 54)
+    z = (z * pow(0xBF58476D1CE4E5B9, -1, 1 << 64)) & m
+    z = z ^ (z >> 30) ^ (z >> 60)
+    s = (z - idx * 0x9E3779B97F4A7C15) & m
+    return s - (1 << 64) if s >= (1 << 63) else s
+
+
+def keep_mask(seed, shape, p):
+    """bool tensor of `shape`: element with row-major flat index i is kept iff dropout_keep_ref(seed, i, p).
+    LayerNorm (rows, d): i = r*d + c.  Attention (B, H, Lq, Lk): i = ((b*H + h)*Lq + i)*Lk + j."""
+    n = int(np.prod(shape))
+    return torch.from_numpy(dropout_keep_ref(seed, np.arange(n, dtype=np.uint64), p)).view(*shape)
+
+
+def keep_scale64(p):
+    """1 / (1 - p) of the f32-rounded p, in f64 (the kernels round it once more: 2 u, inside c)."""
+    return 1.0 / (1.0 - float(np.float32(p)))
+
+
+def keep_scale32(p):
+    """The kernels' own f32 value 1.f / (1.f - p)."""
+    return float(np.float32(1) / (np.float32(1) - np.float32(p)))
+
+
+# ------------------------------------------------------------------------------ colsum
+def colsum_chunks(rows):
+    """kinet_colsum_workspace's row chunking: (chunks, rows per chunk)."""
+    chunks = max(1, min(256, rows // 64))
+    return chunks, (rows + chunks - 1) // chunks if rows else 0
+
+
+def colsum_c(rows):
+    """An element passes through at most rc - 1 adds of its chunk's serial loop (the vector kernel's
+    chain is shorter), 1 add of the final kernel's per-thread loop (<= 256 chunks: one each) and the
+    8 levels of its LDS tree."""
+    return colsum_chunks(rows)[1] + 8
+
+
+# ------------------------------------------------------------------- LayerNorm backward
+def ln_c(d, rows_chain):
+    """Chains of the one-wave-per-row LayerNorm kernels (forward and backward, both files), nv =
+    ceil(d / 64) values per lane, every reduction nv adds + 6 shuffle levels:
+      xh = (z - mean) * rstd: mean nv + 6 adds + 1 divide; + 1 subtraction; rstd half the relative
+           error of the variance (nv + 6 adds, 1 square, 1 divide, 1 + eps: (nv + 9) / 2) + 2 for
+           rsqrtf; + 1 product                                          -> 1.5 nv + 15.5
+      dx = rstd * (g - sg/d - xh * sgx/d): xh; the outer rstd (nv + 9) / 2 + 2; sgx = sum g xh:
+           nv + 6 adds + 2 products; 1/d and its product 2; xh * .: 1; 2 subtractions, the outer
+           product, g = dy gamma: 4                                     -> 3 nv + 37
+      dgamma = sum_r dy xh: xh + 1 product + the row chain;  dbeta: the row chain,
+    rows_chain = rows per wave (serial) + 4 waves + 1 + 8 (final per-thread loop and tree)."""
+    nv = (d + 63) // 64
+    return {'xh': 1.5 * nv + 16, 'dx': 3 * nv + 37, 'dg': 1.5 * nv + 17 + rows_chain, 'db': rows_chain}
+
+
+def ln_ref(z, gamma, beta, eps, dy=None, zA=None):
+    """f64 LayerNorm of the rows z (rows, d), its closed-form backward for dy, and the majorants.
+    zA: |z|'s majorant where z is itself a sum (x + r Z s)."""
+    z, gamma = z.double(), gamma.double()
+    zA = z.abs() if zA is None else zA
+    mean = z.mean(-1, keepdim=True)
+    rstd = (((z - mean) ** 2).mean(-1, keepdim=True) + eps32(eps)).rsqrt()
+    xh = (z - mean) * rstd
+    xhA = (zA + zA.mean(-1, keepdim=True)) * rstd
+    out = {'xh': xh, 'xhA': xhA, 'rstd': rstd}
+    if beta is not None:
+        out['y'] = xh * gamma + beta.double()
+        out['yA'] = xhA * gamma.abs() + beta.double().abs()
+    if dy is not None:
+        dy = dy.double()
+        g = dy * gamma
+        gA = g.abs()
+        out['dz'] = rstd * (g - g.mean(-1, keepdim=True) - xh * (g * xh).mean(-1, keepdim=True))
+        out['dzA'] = rstd * (gA + gA.mean(-1, keepdim=True) + xhA * (gA * xhA).mean(-1, keepdim=True))
+        out['dg'], out['dgA'] = (dy * xh).sum(0), (dy.abs() * xhA).sum(0)
+        out['db'], out['dbA'] = dy.sum(0), dy.abs().sum(0)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def ln_case(rows, d, dtype, seed=0, offset=0.0):
+    """Seeded LayerNorm-backward inputs rounded to `dtype` (gamma f32)."""
+    g = torch.Generator().manual_seed(seed + rows * 1031 + d)
+    x = (offset + torch.randn(rows, d, generator=g)).to(dtype)
+    dy = torch.randn(rows, d, generator=g).to(dtype)
+    gamma = torch.rand(d, generator=g) + 0.5
+    beta = torch.randn(d, generator=g)
+    return x, dy, gamma, beta
+
+
+# ------------------------------------------------------------------- GroupNorm backward
+def gn_blocks(HW):
+    """The launcher's HW blocking: (blocks per image, rows per block)."""
+    nb = max(1, min(512, HW // 128))
+    return nb, (HW + nb - 1) // nb
+
+
+def gn_pivot(X):
+    """X (N, HW, G, cg) -> (N, 1, G, 1): the kernels' pivot of every (image, group)."""
+    return X[:, :4, :, :min(X.shape[-1], 8)].mean((1, 3), keepdim=True)
+
+
+R_PIVOT = 2.0 ** -24          # x - pivot and pivot + mean_s each round once at the data's own magnitude
+
+
+def gn_bwd_ref(dy, x, gamma, G, eps):
+    """f64 GroupNorm backward on (N, HW, C) NHWC, with majorants and per-element c.  The kernels sum
+    x, x^2, dy, dy x per channel (rb rows of a block serially -- the scalar kernel; then nb / 4 + 3
+    adds over the blocks), then cg channels per group serially with one gamma product:
+    n = rb + nb/4 + 3 + cg + 2 roundings on every group sum.  The sums are of s = x - pivot, the
+    pivot the mean of the group's first min(cg, 8) channels at the first min(HW, 4) pixels (gn_pivot).  The
+    variance is the one-pass E[s^2] - mean_s^2: its relative error is (n + 3) kappa u, kappa =
+    (E[s^2] + mean_s^2) / (var + eps) evaluated in f64 per group (a few units whatever the data's
+    offset); rstd takes half of it, + 2 for rsqrtf.
+      dx = rstd (g - a/cnt - xh bx/cnt), xh = (x - mean) rstd, bx = rstd (bs - mean a): three factors
+           rstd 1.5 (n + 3) kappa + 6; mean n + 1; bs and mean a: 2 n + 4; 8 single operations
+                                                                       -> (1.5 kappa + 3) (n + 8)
+      dgamma_c = sum_n rstd (sum dy x - mean sum dy): the channel sums rb + nb/4 + 3, mean n + 1,
+           rstd 0.5 (n + 3) kappa + 2, 3 operations, N images           -> below
+      dbeta_c: rb + nb/4 + 3 + N."""
+    N, HW, C = x.shape
+    cg = C // G
+    X, DY = x.double().view(N, HW, G, cg), dy.double().view(N, HW, G, cg)
+    gm = gamma.double().view(1, 1, G, cg)
+    ax = (1, 3)
+    mean = X.mean(ax, keepdim=True)
+    var = ((X - mean) ** 2).mean(ax, keepdim=True)
+    e = eps32(eps)
+    rstd = (var + e).rsqrt()
+    Sx = X - gn_pivot(X)
+    kappa = ((Sx * Sx).mean(ax, keepdim=True) + Sx.mean(ax, keepdim=True) ** 2) / (var + e)
+    xh = (X - mean) * rstd
+    g = DY * gm
+    gA = g.abs()
+    SA = Sx.abs() + R_PIVOT * X.abs()              # |x - pivot| and the rounding of forming it
+    meanA = SA.mean(ax, keepdim=True)
+    xhA = (SA + meanA) * rstd
+    bxA = rstd * ((gA * SA).mean(ax, keepdim=True) + meanA * gA.mean(ax, keepdim=True))
+    nb, rb = gn_blocks(HW)
+    chan = rb + nb // 4 + 3
+    n = chan + cg + 2
+    out = {
+        'dx': (rstd * (g - g.mean(ax, keepdim=True) - xh * (g * xh).mean(ax, keepdim=True))).reshape(N, HW, C),
+        'dxA': (rstd * (gA + gA.mean(ax, keepdim=True) + xhA * bxA)).reshape(N, HW, C),
+        'dx_c': ((1.5 * kappa + 3) * (n + 8)).expand(N, HW, G, cg).reshape(N, HW, C),
+        'dg': (DY * xh).sum((0, 1)).reshape(C),
+        'dgA': (rstd * ((DY.abs() * SA).sum(1, keepdim=True) + meanA * DY.abs().sum(1, keepdim=True))).sum((0, 1)).reshape(C),
+        'dg_c': (0.5 * (n + 3) * kappa + 2 + n + 1).amax(0).expand(1, G, cg).reshape(C) + chan + 3 + N,
+        'db': DY.sum((0, 1)).reshape(C), 'dbA': DY.abs().sum((0, 1)).reshape(C), 'db_c': chan + N,
+    }
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def gn_case(N, HW, C, dtype, seed=0, offset=0.0):
+    g = torch.Generator().manual_seed(seed + N * 7919 + HW * 131 + C)
+    x = (offset + torch.randn(N, HW, C, generator=g)).to(dtype)
+    dy = torch.randn(N, HW, C, generator=g).to(dtype)
+    gamma = torch.rand(C, generator=g) + 0.5
+    return x, dy, gamma
+
+
+# ------------------------------------------------------------------- attention fwd / bwd
+def attn_ref(q, k, v, do, heads, scale, key_mask=None, keep=None, p=0.0, dtype=torch.float64):
+    """Scaled-dot-product attention and its backward in plain torch ops at `dtype` (f64: the
+    reference; f32: torch's own CPU evaluation, the yardstick for the kernels' fast exp).  q, do
+    (B, Lq, E), k, v (B, Lk, E); key_mask (B, Lk) bool, True = masked; softmax over the unmasked keys,
+    P = 0 on a row without one; keep (B, H, Lq, Lk) bool with probability p of a drop.  Returns
+    {o, dq, dk, dv} and, at f64, the majorants {oA, dqA, dkA, dvA}."""
+    B, Lq, E = q.shape
+    D = E // heads
+
+    def sp(t):
+        return t.to(dtype).view(B, -1, heads, D).transpose(1, 2)
+
+    def mg(t):
+        return t.transpose(1, 2).reshape(B, -1, E)
+    Q, K_, V, dO = sp(q), sp(k), sp(v), sp(do)
+    S = Q @ K_.transpose(-1, -2) * scale
+    if key_mask is not None:
+        S = S.masked_fill(key_mask[:, None, None, :], float('-inf'))
+    mx = S.amax(-1, keepdim=True)
+    mx = torch.where(torch.isinf(mx), torch.zeros_like(mx), mx)
+    e = (S - mx).exp()
+    den = e.sum(-1, keepdim=True)
+    P = e / torch.where(den > 0, den, torch.ones_like(den))
+    Zs = torch.ones((), dtype=dtype) if keep is None else keep.to(dtype) * keep_scale64(p)
+    PZ = P * Zs
+    dP = Zs * (dO @ V.transpose(-1, -2))
+    dS = P * (dP - (P * dP).sum(-1, keepdim=True))
+    out = {'o': mg(PZ @ V), 'dv': mg(PZ.transpose(-1, -2) @ dO), 'dq': mg(dS @ K_ * scale),
+           'dk': mg(dS.transpose(-1, -2) @ Q * scale)}
+    if dtype == torch.float64:
+        dPA = Zs * (dO.abs() @ V.abs().transpose(-1, -2))
+        dSA = P * (dPA + (P * dPA).sum(-1, keepdim=True))
+        out.update({'oA': mg(PZ @ V.abs()), 'dvA': mg(PZ.transpose(-1, -2) @ dO.abs()),
+                    'dqA': mg(dSA @ K_.abs() * scale), 'dkA': mg(dSA.transpose(-1, -2) @ Q.abs() * scale)})
+    return out
+
+
+def attn_yardstick(ref, f32, names):
+    """max over the named tensors and their elements of |torch f32 - f64| / A (A > 0)."""
+    worst = 0.0
+    for n in names:
+        A = ref[n + 'A']
+        ok = A > 0
+        if ok.any():
+            worst = max(worst, ((f32[n].double() - ref[n]).abs()[ok] / A[ok]).max().item())
+    return worst
+
+
+@functools.lru_cache(maxsize=None)
+def attn_case(B, heads, D, Lq, Lk, seed=0, qscale=1.0):
+    g = torch.Generator().manual_seed(seed + D * 10007 + Lq * 211 + Lk)
+    E = heads * D
+    q = torch.randn(B, Lq, E, generator=g) * qscale
+    k = torch.randn(B, Lk, E, generator=g)
+    v = torch.randn(B, Lk, E, generator=g)
+    do = torch.randn(B, Lq, E, generator=g)
+    return q, k, v, do
+
+
+# ---------------------------------------------------------------------------- msda_prep
+def msda_prep_ref(offlog, refs, shapes, qmask, M, L, P):
+    """f64 sampling locations (Nb, Lq, M, L, P, 2) and attention weights (Nb, Lq, M, L, P) from the
+    packed row [offsets (m, l, p, xy) | logits (m, l, p)], with majorants and c.
+      attw: softmax over the head's L*P logits, 0 on masked queries.  d = logit - max: 1 rounding,
+            worth |d| u in the exponent; expf 2; numerator and (every term of) the denominator:
+            2 (max|d| + 3); the sum L*P; the divide 1.   Values below F32_TINY lose their bits.
+      loc:  2-d refs: ref + off / shapes[l, xy] (x by shapes[l, 0], y by shapes[l, 1], as the
+            reference module does): 2.  4-d refs: ref_xy + off / P * ref_wh * 0.5: 4."""
+    Nb, Lq = offlog.shape[:2]
+    n = M * L * P
+    o = offlog[..., :2 * n].double().reshape(Nb, Lq, M, L, P, 2)
+    lg = offlog[..., 2 * n:3 * n].double().reshape(Nb, Lq, M, L * P)
+    d = lg - lg.amax(-1, keepdim=True)
+    e = d.exp()
+    a = e / e.sum(-1, keepdim=True)
+    if qmask is not None:
+        a = a.masked_fill(qmask[:, :, None, None], 0.0)
+    attw_c = (2 * (d.abs().amax(-1, keepdim=True) + 3) + L * P + 1).expand_as(a)
+    rf = refs.double()
+    rd = rf.shape[-1]
+    rxy = rf[..., :2][:, :, None, :, None, :]
+    if rd == 2:
+        div = shapes.double()[None, None, None, :, None, :]
+        loc, locA, loc_c = rxy + o / div, rxy.abs() + o.abs() / div, 2
+    else:
+        rwh = rf[..., 2:][:, :, None, :, None, :]
+        loc, locA, loc_c = rxy + o / P * rwh * 0.5, rxy.abs() + (o / P * rwh * 0.5).abs(), 4
+    return {'loc': loc, 'locA': locA.expand_as(loc), 'loc_c': loc_c,
+            'attw': a.view(Nb, Lq, M, L, P), 'attw_c': attw_c.reshape(Nb, Lq, M, L, P)}
+
+
+def msda_prep_bwd_ref(gloc, gattw, attw, offlog, refs, shapes, M, L, P):
+    """Closed-form f64 gradients for the attention weights `attw` as given (0 rows of masked queries
+    pass nothing): d_offlog (Nb, Lq, 3 M L P) in offlog's packing, d_refs (Nb, Lq, L, rd).
+      d_logit = a (g - sum g a) over the head's L*P: the sum L*P, 3 operations.
+      d_off   = d_loc / shape: 1;  4-d: d_loc * 0.5 * wh / P: 3.
+      d_ref   = sum over heads and points of d_loc: M*P;  4-d w, h: of d_loc * 0.5 * (off / P): M*P + 3."""
+    Nb, Lq = offlog.shape[:2]
+    n = M * L * P
+    o = offlog[..., :2 * n].double().reshape(Nb, Lq, M, L, P, 2)
+    gl, ga, a = gloc.double(), gattw.double().reshape(Nb, Lq, M, L * P), attw.double().reshape(Nb, Lq, M, L * P)
+    dlg = a * (ga - (ga * a).sum(-1, keepdim=True))
+    dlgA = a * (ga.abs() + (ga.abs() * a).sum(-1, keepdim=True))
+    rf = refs.double()
+    rd = rf.shape[-1]
+    if rd == 2:
+        div = shapes.double()[None, None, None, :, None, :]
+        doff, off_c = gl / div, 1
+        dref, drefA = gl.sum((2, 4)), gl.abs().sum((2, 4))
+        ref_c = torch.full_like(dref, M * P)
+    else:
+        rwh = rf[..., 2:][:, :, None, :, None, :]
+        doff, off_c = gl * 0.5 * rwh / P, 3
+        t = gl * 0.5 * (o / P)
+        dref = torch.cat([gl.sum((2, 4)), t.sum((2, 4))], -1)
+        drefA = torch.cat([gl.abs().sum((2, 4)), t.abs().sum((2, 4))], -1)
+        ref_c = torch.cat([torch.full_like(dref[..., :2], M * P), torch.full_like(dref[..., :2], M * P + 3)], -1)
+    dol = torch.cat([doff.reshape(Nb, Lq, 2 * n), dlg.reshape(Nb, Lq, n)], -1)
+    dolA = torch.cat([doff.abs().reshape(Nb, Lq, 2 * n), dlgA.reshape(Nb, Lq, n)], -1)
+    dol_c = torch.cat([torch.full((2 * n,), float(off_c)), torch.full((n,), float(L * P + 3))]).double()
+    return {'dol': dol, 'dolA': dolA, 'dol_c': dol_c, 'dref': dref, 'drefA': drefA, 'dref_c': ref_c}
+
+
+def msda_shapes(L):
+    """Non-square level shapes (H != W on every level): dividing x by W instead of shapes[l, 0] shows."""
+    return torch.tensor([[3 + 2 * l, 5 + 3 * l] for l in range(L)], dtype=torch.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def msda_case(Nb, Lq, M, L, P, rd, pad=0, seed=0, logits='randn'):
+    """offlog (Nb, Lq, 3 M L P + pad), refs (Nb, Lq, L, rd), shapes, d_loc, d_attw.  logits: 'randn',
+    'pm80' (+-80: the max subtraction, weights down to exp(-160)) or 'equal' (uniform weights)."""
+    g = torch.Generator().manual_seed(seed + Nb * 7 + Lq * 1009 + M * 101 + L * 11 + P + rd)
+    n = M * L * P
+    offlog = torch.randn(Nb, Lq, 3 * n + pad, generator=g)
+    offlog[..., :2 * n] *= 3
+    if logits == 'pm80':
+        offlog[..., 2 * n:3 * n] = torch.where(torch.rand(Nb, Lq, n, generator=g) < 0.5, -80.0, 80.0)
+    elif logits == 'equal':
+        offlog[..., 2 * n:3 * n] = 1.25
+    refs = torch.rand(Nb, Lq, L, rd, generator=g)
+    gloc = torch.randn(Nb, Lq, M, L, P, 2, generator=g)
+    gattw = torch.randn(Nb, Lq, M, L, P, generator=g)
+    return offlog, refs, msda_shapes(L), gloc, gattw
+
+
+# ---------------------------------------------------------------------- inverse_sigmoid
+def inv_sigmoid_inputs():
+    """The clamp points of SPECIAL_REFS, values around them, and a dense grid over [-0.1, 1.1]."""
+    e = float(np.float32(1e-5))
+    pts = SPECIAL_REFS + [e * 0.5, e * 2, 1 - e * 0.5, 1 - e * 2, 0.25, 0.75, -0.0, 2.0, -1.0, 1e-30]
+    return torch.cat([torch.tensor(pts, dtype=torch.float32), torch.linspace(-0.1, 1.1, 4001)])
+
+
+def inv_sigmoid_fwd_bwd_ref(x, dy, eps=1e-5):
+    """f64 from the f32 inputs, eps rounded to f32.  y = log(x1 / x2), x1 = max(xc, eps), x2 =
+    max(1 - xc, eps), xc = clamp(x, 0, 1); dx through torch's clamp masks (the gradient passes where
+    min <= v <= max).  Bounds: y -- the subtraction and the quotient are 2 roundings of the
+    logarithm's argument (2 u absolute in y), logf 2 ulp of |y|: c = 4 on A = 1 + |y|.
+    dx -- 8 operations, both terms of one sign: c = 8 on A = |dx|."""
+    e = eps32(eps)
+    xv, g = x.double(), dy.double()
+    xc = xv.clamp(0, 1)
+    x1, x2 = xc.clamp(min=e), (1 - xc).clamp(min=e)
+    y = torch.log(x1 / x2)
+    dq = g / (x1 / x2)
+    d = torch.where(xc >= e, dq / x2, torch.zeros_like(dq)) + torch.where(1 - xc >= e, dq * x1 / (x2 * x2), torch.zeros_like(dq))
+    dx = torch.where((xv >= 0) & (xv <= 1), d, torch.zeros_like(d))
+    return y, dx

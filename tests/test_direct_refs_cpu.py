@@ -5,6 +5,7 @@ import math
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 import direct_refs as R
 
@@ -177,3 +178,227 @@ def test_layernorm_vec_eligibility_table():
     f32, bf = torch.float32, torch.bfloat16
     assert [d for d in (8, 36, 90, 256, 288, 512, 1024) if R.layernorm_vec_eligible(f32, d)] == [8, 36, 256]
     assert [d for d in (8, 36, 90, 256, 288, 512, 1024) if R.layernorm_vec_eligible(bf, d)] == [8, 256, 288, 512]
+
+
+# =================================================== training path references (grad.hip, train_ops.hip)
+M64 = (1 << 64) - 1
+
+
+def _keep_bigint(seed, idx, thresh):
+    """common.h's dropout_keep in Python integers, reduced mod 2^64 by hand."""
+    z = ((seed & M64) + idx * 0x9E3779B97F4A7C15) & M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+    z ^= z >> 31
+    return (z >> 40) >= thresh
+
+
+def test_dropout_thresh_rounds_p_to_f32_first():
+    # f32(0.15) = 0.1500000059...: 2516582.5 + 0.5 rounds to ...83; the double 0.15 gives ...82
+    assert R.dropout_thresh_ref(0.15) == 2516583 and int(0.15 * 2 ** 24 + 0.5) == 2516582
+    assert R.dropout_thresh_ref(0.1) == 1677722         # 1677721.625 + 0.5 (the double 0.1 agrees here)
+    assert R.dropout_thresh_ref(0.0) == 0 and R.dropout_thresh_ref(0.5) == 1 << 23
+    assert R.dropout_thresh_ref(0.999) == int(float(np.float32(0.999)) * 2 ** 24 + 0.5)
+
+
+@pytest.mark.parametrize('seed', [0, 1, -1, -(2 ** 63), 2 ** 63 - 1, 123456789])
+def test_dropout_keep_ref_equals_bigint(seed):
+    idx = [0, 1, 2, 63, 2 ** 31 - 1, 2 ** 31, 2 ** 32 - 1, 2 ** 32, 2 ** 32 + 12345, 2 ** 40 + 7, 2 ** 62]
+    for p in (0.1, 0.5, 0.999):
+        got = R.dropout_keep_ref(seed, np.array(idx, dtype=np.uint64), p)
+        want = [_keep_bigint(seed, i, R.dropout_thresh_ref(p)) for i in idx]
+        assert got.tolist() == want
+    dense = R.dropout_keep_ref(seed, np.arange(5000, dtype=np.uint64), 0.3)
+    assert dense.tolist() == [_keep_bigint(seed, i, R.dropout_thresh_ref(0.3)) for i in range(5000)]
+
+
+def test_dropout_seed_for_draw_hits_the_threshold():
+    """The hash is a bijection of the seed: seed_for_draw puts element idx's 24-bit draw on a chosen
+    value, so a test can sit exactly on the threshold (kept) and one below it (dropped)."""
+    for p in (0.1, 0.15, 0.5, 0.999):
+        t = R.dropout_thresh_ref(p)
+        for idx in (0, 5, 2 ** 33 + 1):
+            s_keep, s_drop = R.dropout_seed_for_draw(t, idx), R.dropout_seed_for_draw(t - 1, idx)
+            assert -(2 ** 63) <= s_keep < 2 ** 63
+            assert _keep_bigint(s_keep, idx, t) and not _keep_bigint(s_drop, idx, t)
+            assert R.dropout_keep_ref(s_keep, idx, p)[0] and not R.dropout_keep_ref(s_drop, idx, p)[0]
+
+
+def test_dropout_keep_ref_rate_and_p0():
+    n = 1 << 20
+    assert R.keep_mask(5, (n,), 0.0).all()
+    for p in (0.1, 0.5, 0.999):
+        rate = R.keep_mask(-7, (n,), p).double().mean().item()
+        q = 1 - float(np.float32(p))
+        assert abs(rate - q) < 5 * (q * (1 - q) / n) ** 0.5, (p, rate)
+
+
+def test_keep_mask_flat_index_conventions():
+    rows, d, p = 5, 13, 0.4
+    m = R.keep_mask(11, (rows, d), p)
+    for r, c in [(0, 0), (1, 0), (4, 12), (2, 7)]:
+        assert bool(m[r, c]) == bool(R.dropout_keep_ref(11, r * d + c, p)[0])
+    B, H, Lq, Lk = 2, 3, 4, 5
+    m = R.keep_mask(11, (B, H, Lq, Lk), p)
+    for b, h, i, j in [(0, 0, 0, 0), (1, 2, 3, 4), (1, 0, 2, 1), (0, 2, 0, 3)]:
+        assert bool(m[b, h, i, j]) == bool(R.dropout_keep_ref(11, ((b * H + h) * Lq + i) * Lk + j, p)[0])
+    assert R.keep_scale32(0.5) == 2.0 and abs(R.keep_scale64(0.3) - R.keep_scale32(0.3)) < 3e-7
+
+
+def test_colsum_chunks_restatement():
+    assert R.colsum_chunks(0) == (1, 0) and R.colsum_chunks(63) == (1, 63) and R.colsum_chunks(128) == (2, 64)
+    assert R.colsum_chunks(16389) == (256, 65)          # the 256-chunk cap binds
+    assert R.gn_blocks(127) == (1, 127) and R.gn_blocks(257) == (2, 129) and R.gn_blocks(66000) == (512, 129)
+
+
+@pytest.mark.parametrize('rows,d', [(1, 1), (3, 65), (17, 288)])
+def test_ln_ref_equals_f64_autograd(rows, d):
+    x, dy, gamma, beta = (t.double() for t in R.ln_case(rows, d, torch.float32))
+    xt, gt, bt = x.clone().requires_grad_(), gamma.clone().requires_grad_(), beta.clone().requires_grad_()
+    y = F.layer_norm(xt, (d,), gt, bt, R.eps32(1e-5))
+    y.backward(dy)
+    ref = R.ln_ref(x, gamma, beta, 1e-5, dy=dy)
+    for got, want in [(ref['y'], y.detach()), (ref['dz'], xt.grad), (ref['dg'], gt.grad), (ref['db'], bt.grad)]:
+        assert (got - want).abs().max().item() <= 1e-11 * (1 + want.abs().max().item())
+    for n in ('dz', 'dg', 'db', 'y'):
+        assert (ref[n + 'A'] >= ref[n].abs() * (1 - 1e-12)).all()
+
+
+@pytest.mark.parametrize('shape', [(2, 5, 30, 6), (1, 40, 8, 8), (2, 40, 8, 1), (2, 35, 36, 12)])
+def test_gn_bwd_ref_equals_f64_autograd(shape):
+    N_, HW, C, G = shape
+    x, dy, gamma = (t.double() for t in R.gn_case(N_, HW, C, torch.float32))
+    xt = x.permute(0, 2, 1).contiguous().requires_grad_()
+    gt, bt = gamma.clone().requires_grad_(), torch.zeros(C, dtype=torch.float64, requires_grad=True)
+    F.group_norm(xt, G, gt, bt, R.eps32(1e-5)).backward(dy.permute(0, 2, 1).contiguous())
+    ref = R.gn_bwd_ref(dy, x, gamma, G, 1e-5)
+    assert (ref['dx'] - xt.grad.permute(0, 2, 1)).abs().max().item() <= 1e-11
+    assert (ref['dg'] - gt.grad).abs().max().item() <= 1e-10 and (ref['db'] - bt.grad).abs().max().item() <= 1e-10
+    for n in ('dx', 'dg', 'db'):
+        assert (ref[n + 'A'] >= ref[n].abs() * (1 - 1e-12)).all()
+    assert (ref['dx_c'] >= 4.5 * 8).all()
+
+
+def _f32_formula_err(kind):
+    """The kernels' norm-backward formulas evaluated step by step in f32 torch on the guards' inputs:
+    (its dx / dgamma error, torch's own CPU f32 backward's error), both against the f64 reference."""
+    if kind == 'ln':
+        d = 288
+        x, dy, gamma, beta = R.ln_case(64, d, torch.float32, seed=5, offset=100.0)
+        ref = R.ln_ref(x, gamma, None, 1e-5, dy=dy)
+        xt, gt = x.clone().requires_grad_(), gamma.clone().requires_grad_()
+        F.layer_norm(xt, (d,), gt, beta, 1e-5).backward(dy)
+        mean = x.mean(-1, keepdim=True)
+        rstd = (((x - mean) ** 2).mean(-1, keepdim=True) + 1e-5).rsqrt()
+        xh, g = (x - mean) * rstd, dy * gamma
+        dx = rstd * (g - g.mean(-1, keepdim=True) - xh * (g * xh).mean(-1, keepdim=True))
+        dg = (dy * xh).sum(0)
+        return [((dx.double() - ref['dz']).abs().max().item(), (xt.grad.double() - ref['dz']).abs().max().item()),
+                ((dg.double() - ref['dg']).abs().max().item(), (gt.grad.double() - ref['dg']).abs().max().item())]
+    N_, HW, C, G = 2, 200, 32, 4
+    x, dy, gamma = R.gn_case(N_, HW, C, torch.float32, seed=3, offset=30.0)
+    ref = R.gn_bwd_ref(dy, x, gamma, G, 1e-5)
+    xt, gt = x.permute(0, 2, 1).contiguous().requires_grad_(), gamma.clone().requires_grad_()
+    F.group_norm(xt, G, gt, torch.zeros(C), 1e-5).backward(dy.permute(0, 2, 1).contiguous())
+    cg = C // G
+    X, DY, gm = x.view(N_, HW, G, cg), dy.view(N_, HW, G, cg), gamma.view(1, 1, G, cg)
+    piv = R.gn_pivot(X)
+    S = X - piv
+    ms = S.mean((1, 3), keepdim=True)
+    var = ((S * S).mean((1, 3), keepdim=True) - ms * ms).clamp(min=0)           # one pass, as the kernel
+    rstd = (var + 1e-5).rsqrt()
+    a = (DY * gm).mean((1, 3), keepdim=True)
+    bx = rstd * ((DY * gm * S).mean((1, 3), keepdim=True) - ms * a)
+    dx = (rstd * (DY * gm - a - (X - (piv + ms)) * rstd * bx)).reshape(N_, HW, C)
+    dg = (rstd * ((DY * S).sum(1, keepdim=True) - ms * DY.sum(1, keepdim=True))).sum((0, 1)).reshape(C)
+    return [((dx.double() - ref['dx']).abs().max().item(), (xt.grad.permute(0, 2, 1).double() - ref['dx']).abs().max().item()),
+            ((dg.double() - ref['dg']).abs().max().item(), (gt.grad.double() - ref['dg']).abs().max().item())]
+
+
+@pytest.mark.parametrize('kind', ['ln', 'gn'])
+def test_norm_backward_guard_yardstick_is_attainable(kind):
+    """The guards bound the kernels by 4x torch's CPU f32 error: an f32 evaluation of the kernels' own
+    formulas sits inside that on the same inputs, so the yardstick asks nothing a correct f32 kernel
+    cannot give."""
+    for (formula, torch_f32), name in zip(_f32_formula_err(kind), ('dx', 'dgamma')):
+        print(f'{kind} guard {name}: f32 formula err {formula:.3e}, torch CPU f32 err {torch_f32:.3e}')
+        assert formula <= 4 * torch_f32, (kind, name, formula, torch_f32)
+
+
+@pytest.mark.parametrize('mask,p', [('none', 0.0), ('some', 0.0), ('some', 0.5), ('batch', 0.0)])
+def test_attn_ref_equals_f64_autograd(mask, p):
+    B, H, D, Lq, Lk = 2, 2, 5, 7, 9
+    q, k, v, do = (t.double() for t in R.attn_case(B, H, D, Lq, Lk))
+    km = None
+    if mask != 'none':
+        km = torch.zeros(B, Lk, dtype=torch.bool)
+        km[0, 3:6] = True
+        km[1, -2:] = True
+        if mask == 'batch':
+            km[1] = True
+    keep = R.keep_mask(3, (B, H, Lq, Lk), p) if p > 0 else None
+    scale = D ** -0.5
+    ref = R.attn_ref(q, k, v, do, H, scale, km, keep, p)
+    leaves = [t.clone().requires_grad_() for t in (q, k, v)]
+    Q, K_, V = (t.view(B, -1, H, D).transpose(1, 2) for t in leaves)
+    S = Q @ K_.transpose(-1, -2) * scale
+    if km is not None:
+        S = S.masked_fill(km[:, None, None, :], float('-inf'))
+    P = S.softmax(-1)
+    if mask == 'batch':     # a fully masked row: softmax is 0/0 there, the operation defines P = 0
+        S2 = S.masked_fill(km.all(-1)[:, None, None, None], 0.0)
+        P = S2.softmax(-1) * (~km.all(-1))[:, None, None, None]
+    if keep is not None:
+        P = P * keep.double() * R.keep_scale64(p)
+    o = (P @ V).transpose(1, 2).reshape(B, Lq, H * D)
+    o.backward(do)
+    for n, want in zip(('o', 'dq', 'dk', 'dv'), [o.detach()] + [t.grad for t in leaves]):
+        assert (ref[n] - want).abs().max().item() <= 1e-12, n
+        assert (ref[n + 'A'] >= ref[n].abs() * (1 - 1e-12)).all()
+    if mask == 'batch':
+        assert all((ref[n][1] == 0).all() and (ref[n + 'A'][1] == 0).all() for n in ('dq', 'dk', 'dv'))
+    if mask == 'none' and p == 0:
+        sd = F.scaled_dot_product_attention(*(t.detach() for t in (Q, K_, V))).transpose(1, 2).reshape(B, Lq, H * D)
+        assert (ref['o'] - sd).abs().max().item() <= 1e-12
+    f32 = R.attn_ref(q.float(), k.float(), v.float(), do.float(), H, scale, km, keep, p, dtype=torch.float32)
+    assert f32['dq'].dtype == torch.float32 and R.attn_yardstick(ref, f32, ['dq', 'dk', 'dv']) < 1e-5
+
+
+@pytest.mark.parametrize('rd', [2, 4])
+@pytest.mark.parametrize('M,L,P', [(2, 3, 2), (4, 2, 4)])
+def test_msda_prep_refs_equal_f64_autograd(rd, M, L, P):
+    Nb, Lq = 2, 5
+    offlog, refs, shapes, gloc, gattw = R.msda_case(Nb, Lq, M, L, P, rd)
+    qm = torch.zeros(Nb, Lq, dtype=torch.bool)
+    qm[0, 1] = qm[1, 4] = True
+    n = M * L * P
+    ol, rf = offlog.double().requires_grad_(), refs.double().requires_grad_()
+    # the module's own expressions (ms_deform_attn.py), in f64
+    off = ol[..., :2 * n].view(Nb, Lq, M, L, P, 2)
+    aw = ol[..., 2 * n:].view(Nb, Lq, M, L * P).softmax(-1).view(Nb, Lq, M, L, P)
+    aw = aw.masked_fill(qm[:, :, None, None, None], 0.0)
+    if rd == 2:
+        loc = rf[:, :, None, :, None, :] + off / shapes.double()[None, None, None, :, None, :]
+    else:
+        loc = rf[:, :, None, :, None, :2] + off / P * rf[:, :, None, :, None, 2:] * 0.5
+    ref = R.msda_prep_ref(offlog, refs, shapes, qm, M, L, P)
+    assert (ref['loc'] - loc.detach()).abs().max().item() <= 1e-13
+    assert (ref['attw'] - aw.detach()).abs().max().item() <= 1e-15
+    assert shapes[:, 0].ne(shapes[:, 1]).all()
+    ((loc * gloc.double()).sum() + (aw * gattw.double()).sum()).backward()
+    b = R.msda_prep_bwd_ref(gloc, gattw, ref['attw'], offlog, refs, shapes, M, L, P)
+    assert (b['dol'] - ol.grad).abs().max().item() <= 1e-13 and (b['dref'] - rf.grad).abs().max().item() <= 1e-13
+    assert (b['dolA'] >= b['dol'].abs() * (1 - 1e-12)).all() and (b['drefA'] >= b['dref'].abs() * (1 - 1e-12)).all()
+
+
+def test_inv_sigmoid_ref_equals_f64_autograd():
+    x = R.inv_sigmoid_inputs()
+    dy = torch.randn(x.numel(), generator=torch.Generator().manual_seed(6))
+    y, dx = R.inv_sigmoid_fwd_bwd_ref(x, dy)
+    xt = x.double().requires_grad_()
+    e = R.eps32(1e-5)
+    xc = xt.clamp(min=0, max=1)
+    yt = torch.log(xc.clamp(min=e) / (1 - xc).clamp(min=e))
+    yt.backward(dy.double())
+    assert torch.equal(y, yt.detach()) and (dx - xt.grad).abs().max().item() <= 1e-9 * dx.abs().max().item()
+    assert (R.inverse_sigmoid_ref(x, e) - y).abs().max().item() == 0
