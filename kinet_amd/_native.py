@@ -92,6 +92,11 @@ _SIGS = {
     'kinet_msda_prep_backward': [P] * 4 + [I64] + [P] * 4 + [I64, I, I, I, I, P],
     'kinet_inverse_sigmoid': [P, P, I64, F, P],
     'kinet_inverse_sigmoid_backward': [P, P, P, I64, F, P],
+    'kinet_two_stage_proposals': [P, I, P, P, P, I, I, P],
+    'kinet_topk_rows': [P, I64, I64, I, I, I, P, P],
+    'kinet_two_stage_queries': [P, P, P, P, P, I, I, I, I, P],
+    'kinet_two_stage_fill_rows': [P, P, P, I64, I, I, P],
+    'kinet_two_stage_boxes': [P, P, P, P, I64, P],
     'kinet_last_error': [],
     'kinet_version': [],
 }

@@ -767,6 +767,95 @@ def box_refine(tmp, ref, valid_ratios=None, want_input=True, out=None):
     return nref, rin
 
 
+# ------------------------------------------------------------- two-stage proposal stage
+TOPK_MAX_K = 1024   # include/kinet_two_stage.h
+
+
+def two_stage_proposals(shapes, mask, batch, device):
+    """gen_encoder_output_proposals' shape / mask part (kinet_two_stage_proposals): shapes the
+    host list of level (H, W); mask (B, S) bool / uint8 or None -> (proposals (B, S, 4) f32 in
+    logit space, +inf on padded / out-of-range rows; keep (B, S) uint8)."""
+    import ctypes
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    S = sum(h * w for h, w in shapes)
+    m = None
+    if mask is not None:
+        N.require_gpu(mask)
+        m = mask.reshape(batch, S).to(torch.uint8).contiguous()
+    prop = torch.empty((batch, S, 4), dtype=torch.float32, device=device)
+    keep = torch.empty((batch, S), dtype=torch.uint8, device=device)
+    hw = (ctypes.c_int * (2 * len(shapes)))(*[v for s in shapes for v in s])
+    N.call('kinet_two_stage_proposals', hw, len(shapes), N.ptr(m), N.ptr(prop), N.ptr(keep), batch, S,
+           N.stream(device))
+    return prop, keep
+
+
+def topk_rows(scores, k):
+    """Indices (rows, k) int64 of the k largest entries of each row of an f32 matrix, read in
+    place through its strides (e.g. channel 0 of (B, S, C) logits): descending, NaN first, ties
+    by ascending index == torch.sort(descending=True, stable=True)[1][:, :k].  No host sync."""
+    N.require_gpu(scores)
+    if scores.dim() != 2 or scores.dtype != torch.float32:
+        raise RuntimeError('topk_rows: scores must be a 2-d float32 matrix')
+    rows, S = scores.shape
+    out = torch.empty((rows, k), dtype=torch.int64, device=scores.device)
+    N.call('kinet_topk_rows', N.ptr(scores), scores.stride(0), scores.stride(1), rows, S, int(k), N.ptr(out),
+           N.stream(scores.device), work={'family': 'topk', 'bytes': 4 * rows * S * 4})
+    return out
+
+
+_proposal_dim_t = {}
+
+
+def proposal_dim_t(device):
+    """get_proposal_pos_embed's dim_t (deformable_transformer.py:82-83), evaluated with torch on
+    the host as the reference does; one table per device."""
+    device = torch.device(device)
+    t = _proposal_dim_t.get(device)
+    if t is None:
+        d = torch.arange(128, dtype=torch.float32)
+        d = 10000 ** (2 * torch.div(d, 2, rounding_mode='floor') / 128)
+        t = _proposal_dim_t[device] = d.to(device)
+    return t
+
+
+def two_stage_queries(coord_unact, idx, out_dtype, dim_t=None):
+    """coord_unact (B, S, 4) f32, idx (B, k) int64 -> (reference_points (B, k, 4) f32 =
+    sigmoid(gathered), proposal position embedding (B, k, 512) in out_dtype)."""
+    N.require_gpu(coord_unact, idx)
+    B, S, _ = coord_unact.shape
+    k = idx.shape[1]
+    cu = coord_unact.float().contiguous()
+    ix = idx.contiguous()
+    dim_t = proposal_dim_t(cu.device) if dim_t is None else dim_t
+    ref = torch.empty((B, k, 4), dtype=torch.float32, device=cu.device)
+    pos = torch.empty((B, k, 512), dtype=out_dtype, device=cu.device)
+    N.call('kinet_two_stage_queries', N.ptr(cu), N.ptr(ix), N.ptr(dim_t), N.ptr(ref), N.ptr(pos), B, S, k,
+           N.dtype_code(out_dtype), N.stream(cu.device))
+    return ref, pos
+
+
+def two_stage_fill_rows(y, keep, row):
+    """In place: y[r] = row for every row r of y (..., d) with keep[r] == 0."""
+    N.require_gpu(y, keep, row)
+    d = y.shape[-1]
+    if not y.is_contiguous() or not keep.is_contiguous() or row.dtype != y.dtype:
+        raise RuntimeError('two_stage_fill_rows: contiguous y / keep and a row of the same dtype required')
+    N.call('kinet_two_stage_fill_rows', N.ptr(y), N.ptr(keep), N.ptr(row), y.numel() // d, d, N.dtype_code(y.dtype),
+           N.stream(y.device))
+    return y
+
+
+def two_stage_boxes(tmp, proposals):
+    """(coord_unact = tmp + proposals, boxes = sigmoid(coord_unact)), all (B, S, 4) f32."""
+    N.require_gpu(tmp, proposals)
+    t = tmp.float().contiguous()
+    p = proposals.contiguous()
+    unact, boxes = torch.empty_like(p), torch.empty_like(p)
+    N.call('kinet_two_stage_boxes', N.ptr(t), N.ptr(p), N.ptr(unact), N.ptr(boxes), p.numel() // 4, N.stream(p.device))
+    return unact, boxes
+
+
 # ------------------------------------------------------------------------------ MSDA
 _tile_orders = {}
 

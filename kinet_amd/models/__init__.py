@@ -9,7 +9,8 @@ src/trackformer/models/__init__.py:16-125.
 families are built: the deformable image branch (:51-71, the hot path), the KineT kinematic
 branch (`args.kine`, :72-107, kinet_amd/models/kinet.py) and vanilla DETR (:111-125, the
 reference's default `deformable: false`; kinet_amd/models/detr.py, inference only).  The
-segmentation heads (`masks`) raise.
+deformable branch also builds the two-stage variant (`two_stage: true`, inference only; the
+proposal stage runs on csrc/two_stage.hip).  The segmentation heads (`masks`) raise.
 """
 import torch
 
@@ -40,6 +41,11 @@ def build_model(args):
         raise NotImplementedError('segmentation heads are outside the hot path')
     if not args.deformable:
         return _build_detr(args, num_classes)
+    if args.two_stage and (args.tracking or args.multi_frame_attention):
+        # the reference's two-stage branch builds its queries from the proposals alone and drops
+        # the track queries (deformable_transformer.py:180-194)
+        raise NotImplementedError('two_stage with tracking / multi_frame_attention is not built: the two-stage '
+                                  'branch of the reference ignores track queries')
     backbone = build_backbone(args)
     matcher = None
     try:

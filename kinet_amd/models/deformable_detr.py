@@ -57,8 +57,10 @@ class DeformableDETR(nn.Module):
                  aux_loss=True, with_box_refine=False, two_stage=False, overflow_boxes=False,
                  multi_frame_attention=False, multi_frame_encoding=False, merge_frame_features=False):
         super().__init__()
-        if two_stage:
-            raise NotImplementedError('two_stage is not on the configured hot path')
+        if two_stage and multi_frame_attention:
+            raise NotImplementedError('two_stage with multi_frame_attention is not built')
+        if two_stage and not transformer.two_stage:
+            raise ValueError('two_stage detector on a one-stage transformer')
         if merge_frame_features:
             raise NotImplementedError('merge_frame_features is false in every configured path')
         # DETR base attributes (detr.py:34-53), same registration order
@@ -68,7 +70,14 @@ class DeformableDETR(nn.Module):
         hidden_dim = transformer.d_model
         self.class_embed = nn.Linear(hidden_dim, num_classes + 1)
         self.bbox_embed = MLP(hidden_dim, hidden_dim, 4, 3)
-        self.query_embed = nn.Embedding(num_queries, hidden_dim * 2)
+        # two-stage: the queries come from the encoder's proposals and no query_embed is read; the
+        # reference still carries the DETR base's d-wide embedding (detr.py:40, replaced only
+        # `if not two_stage`, deformable_detr.py:53-54), so its checkpoints hold that key
+        self.query_embed = nn.Embedding(num_queries, hidden_dim if two_stage else hidden_dim * 2)
+        if two_stage:
+            # the reference's registration order (detr.py:43 registers input_proj before the
+            # backbone; replaced below, which keeps the slot): state_dict order equals its own
+            self.input_proj = nn.Identity()
         self.backbone = backbone
         self.aux_loss = aux_loss
         # DeformableDETR (deformable_detr.py:48-117)
@@ -103,7 +112,8 @@ class DeformableDETR(nn.Module):
         for proj in self.input_proj:
             nn.init.xavier_uniform_(proj[0].weight, gain=1)
             nn.init.constant_(proj[0].bias, 0)
-        num_pred = transformer.decoder.num_layers
+        # two-stage: one more head pair, the proposal generator's (:92-96)
+        num_pred = transformer.decoder.num_layers + (1 if two_stage else 0)
         if with_box_refine:
             self.class_embed = _get_clones(self.class_embed, num_pred)
             self.bbox_embed = _get_clones(self.bbox_embed, num_pred)
@@ -114,6 +124,10 @@ class DeformableDETR(nn.Module):
             self.class_embed = nn.ModuleList([self.class_embed for _ in range(num_pred)])
             self.bbox_embed = nn.ModuleList([self.bbox_embed for _ in range(num_pred)])
             self.transformer.decoder.bbox_embed = None
+        if two_stage:
+            self.transformer.decoder.class_embed = self.class_embed
+            for box_embed in self.bbox_embed:
+                nn.init.constant_(box_embed.layers[-1].bias.data[2:], 0.0)
         self.compute_dtype = torch.float32
         self._geo_cache = {}
 
@@ -212,6 +226,10 @@ class DeformableDETR(nn.Module):
         if not isinstance(samples, NestedTensor):
             samples = nested_tensor_from_tensor_list(samples)
         if not fast_path(self):
+            if self.two_stage:
+                raise NotImplementedError('two-stage Deformable DETR runs the inference path only (eval mode under '
+                                          'torch.no_grad()); its training forward and the enc_outputs losses are '
+                                          'not built')
             return self._forward_reference(samples, targets, prev_features)
         dt = self.compute_dtype
         device = samples.tensors.device
@@ -262,8 +280,16 @@ class DeformableDETR(nn.Module):
                 off += h * w
             self._project_frame(fn, src, offs)
 
-        hs, memory, init_reference, inter_references, _, _ = self.transformer.forward_flat(
-            src, geo['lvl_pos'], geo, self.query_embed.weight, targets)
+        if self.two_stage:
+            # the proposals' box head: bbox_embed[num_layers] (the reference reads it through
+            # decoder.bbox_embed, which it sets to None without box refinement -- its forward raises
+            # there, deformable_transformer.py:185; the shared head is what that line means)
+            hs, memory, init_reference, inter_references, enc_class, _ = self.transformer.forward_flat(
+                src, geo['lvl_pos'], geo, None, targets,
+                proposal_bbox_embed=self.bbox_embed[self.transformer.decoder.num_layers])
+        else:
+            hs, memory, init_reference, inter_references, _, _ = self.transformer.forward_flat(
+                src, geo['lvl_pos'], geo, self.query_embed.weight, targets)
 
         nl = hs.shape[0]
         n_cls = self.class_embed[0].weight.shape[0]
@@ -280,6 +306,8 @@ class DeformableDETR(nn.Module):
         out = {'pred_logits': outputs_class[-1], 'pred_boxes': outputs_coord[-1], 'hs_embed': hs[-1].float()}
         if self.aux_loss:
             out['aux_outputs'] = self._set_aux_loss(outputs_class, outputs_coord)
+        if self.two_stage:
+            out['enc_outputs'] = {'pred_logits': enc_class, 'pred_boxes': self.transformer.enc_outputs_coord}
         memory_slices = []
         o = 0
         for (h, w) in geo['shapes']:

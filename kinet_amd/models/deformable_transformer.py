@@ -17,6 +17,10 @@ Two execution paths with identical arithmetic:
     probability dropout, ...; forward and backward HIP kernels) with MSDeformAttnFunction
     (HIP forward / backward) at the operator boundary; torch supplies only glue (dropout
     masks outside attention, adds, reshapes).
+Two-stage (`two_stage=True`, :52-56, :77-122, :180-194), inference path only: the encoder-output
+proposals, the per-frame top-k of the encoder class logits and the queries built from the selected
+boxes run on the kernels of csrc/two_stage.hip without a host sync (`_proposal_queries`); the
+last forward's selected token indices stay in `topk_proposals`.
 Reference quirks kept on purpose: 2-d sampling offsets divided by
 (H, W) applied to (x, y); multi-frame memory concatenated [current, prev] while shapes,
 masks and valid ratios stay [prev, current].
@@ -336,9 +340,14 @@ class DeformableTransformer(nn.Module):
                  dec_n_points=4, enc_n_points=4, two_stage=False, two_stage_num_proposals=300,
                  multi_frame_attention_separate_encoder=False):
         super().__init__()
-        if two_stage:
-            raise NotImplementedError('two-stage Deformable DETR is not on the configured hot path '
-                                      '(two_stage: false in every BASELINE config)')
+        if two_stage and d_model != 256:
+            # the reference's proposal embedding is 4 x 128 = 512 wide whatever d_model is and
+            # feeds Linear(2d, 2d) (:55, :77-90, :193): its first forward fails for d != 256
+            raise NotImplementedError(f'two_stage needs hidden_dim 256 (got {d_model}): the 512-wide proposal '
+                                      f'position embedding feeds pos_trans = Linear(2d, 2d)')
+        if two_stage and not 1 <= two_stage_num_proposals <= K.TOPK_MAX_K:
+            raise NotImplementedError(f'two_stage selects 1..{K.TOPK_MAX_K} proposals (num_queries = '
+                                      f'{two_stage_num_proposals})')
         self.d_model = d_model
         self.nhead = nhead
         self.two_stage = two_stage
@@ -353,7 +362,15 @@ class DeformableTransformer(nn.Module):
                                                           num_feature_levels, nhead, dec_n_points)
         self.decoder = DeformableTransformerDecoder(decoder_layer, num_decoder_layers, return_intermediate_dec)
         self.level_embed = nn.Parameter(torch.Tensor(num_feature_levels, d_model))
-        self.reference_points = nn.Linear(d_model, 2)
+        if two_stage:
+            self.enc_output = nn.Linear(d_model, d_model)
+            self.enc_output_norm = nn.LayerNorm(d_model)
+            self.pos_trans = nn.Linear(d_model * 2, d_model * 2)
+            self.pos_trans_norm = nn.LayerNorm(d_model * 2)
+            self.topk_proposals = None        # (B, k) int64: the last forward's selected proposals
+            self.enc_outputs_coord = None     # (B, S, 4) f32: sigmoid of its enc_outputs_coord_unact
+        else:
+            self.reference_points = nn.Linear(d_model, 2)
         self._reset_parameters()
 
     def _reset_parameters(self):
@@ -363,8 +380,9 @@ class DeformableTransformer(nn.Module):
         for m in self.modules():
             if isinstance(m, MSDeformAttn):
                 m._reset_parameters()
-        xavier_uniform_(self.reference_points.weight.data, gain=1.0)
-        constant_(self.reference_points.bias.data, 0.)
+        if not self.two_stage:
+            xavier_uniform_(self.reference_points.weight.data, gain=1.0)
+            constant_(self.reference_points.bias.data, 0.)
         normal_(self.level_embed)
 
     @staticmethod
@@ -391,14 +409,15 @@ class DeformableTransformer(nn.Module):
         valid_ratios = torch.stack([self.get_valid_ratio(m) for m in masks], 1)
         return src_flatten, mask_flatten, lvl_pos_embed_flatten, spatial_shapes, valid_ratios
 
-    def forward(self, srcs, masks, pos_embeds, query_embed=None, targets=None, padded=None):
+    def forward(self, srcs, masks, pos_embeds, query_embed=None, targets=None, padded=None,
+                proposal_bbox_embed=None):
         src_flatten, mask_flatten, lvl_pos, shapes, valid_ratios = self.prepare_inputs(srcs, masks, pos_embeds)
         if fast_path(self):
             dt = srcs[0].dtype
             src_flatten = src_flatten.to(dt).contiguous()
             lvl_pos = lvl_pos.to(dt).contiguous()
         geo = self.geometry(shapes, valid_ratios, mask_flatten, src_flatten.device, padded)
-        return self.forward_flat(src_flatten, lvl_pos, geo, query_embed, targets)
+        return self.forward_flat(src_flatten, lvl_pos, geo, query_embed, targets, proposal_bbox_embed)
 
     def geometry(self, shapes, valid_ratios, mask_flatten, device, padded=None):
         """Everything that depends only on the level shapes and padding masks.  padded: whether
@@ -429,7 +448,48 @@ class DeformableTransformer(nn.Module):
                                tok=slice(0, None), order=K.encoder_tile_order(geo['shapes'], device),
                                ref=DeformableTransformerEncoder.get_reference_points(geo['shapes'], valid_ratios,
                                                                                      device))]
+        if self.two_stage and fast_path(self):
+            # the encoder-output proposals and the rows they keep depend on shapes and masks only
+            geo['proposals'], geo['keep'] = K.two_stage_proposals(geo['shapes'], geo['pad_mask'],
+                                                                  valid_ratios.shape[0], device)
         return geo
+
+    def _invalid_row(self, dt):
+        """enc_output_norm(enc_output(0)): the output row of every token whose input the reference
+        zeroes (:118-121), from the same GEMM + LayerNorm launch as the other rows; cached per
+        parameter version and compute dtype."""
+        eo, en = self.enc_output, self.enc_output_norm
+
+        def make(w, b, g, beta):
+            zero = torch.zeros((1, w.shape[1]), dtype=dt, device=w.device)
+            return K.linear(zero, w, b, ln=(g, beta, en.eps)).reshape(-1).contiguous()
+        return K.cached_multi([eo.weight, eo.bias, en.weight, en.bias], ('two_stage_invalid_row', dt), make)
+
+    def _proposal_queries(self, memory, geo, proposal_bbox_embed=None):
+        """The two-stage branch of deformable_transformer.py:180-194 on the HIP kernels of
+        csrc/two_stage.hip: (query_pos, tgt, reference_points, enc_outputs_class,
+        enc_outputs_coord_unact); no host sync.  proposal_bbox_embed: the box head of the
+        proposals; None = decoder.bbox_embed[num_layers] as the reference reads it (:185), which
+        exists only with box refinement (without it the reference sets decoder.bbox_embed = None,
+        deformable_detr.py:108, and its forward raises; the detector passes its shared head)."""
+        if proposal_bbox_embed is None:
+            proposal_bbox_embed = self.decoder.bbox_embed[self.decoder.num_layers]
+        c = self.d_model
+        eo, en = self.enc_output, self.enc_output_norm
+        nl = self.decoder.num_layers
+        output_memory = K.linear(memory, eo.weight, eo.bias, ln=(en.weight, en.bias, en.eps))
+        K.two_stage_fill_rows(output_memory, geo['keep'], self._invalid_row(memory.dtype))
+        ce = self.decoder.class_embed[nl]
+        enc_outputs_class = K.linear(output_memory, ce.weight, ce.bias, out_dtype=torch.float32)
+        tmp = mlp_fast(proposal_bbox_embed, output_memory)
+        enc_outputs_coord_unact, self.enc_outputs_coord = K.two_stage_boxes(tmp, geo['proposals'])
+        self.topk_proposals = K.topk_rows(enc_outputs_class[..., 0], self.two_stage_num_proposals)
+        reference_points, pos = K.two_stage_queries(enc_outputs_coord_unact, self.topk_proposals, memory.dtype)
+        pt, pn = self.pos_trans, self.pos_trans_norm
+        pos_trans_out = K.layernorm(K.linear(pos, pt.weight, pt.bias), pn.weight, pn.bias, pn.eps)
+        query_pos = pos_trans_out[..., :c].contiguous()
+        tgt = pos_trans_out[..., c:].contiguous()
+        return query_pos, tgt, reference_points, enc_outputs_class, enc_outputs_coord_unact
 
     def _query_inputs(self, query_embed, bs, dt):
         """(query_pos, tgt, reference_points) for `bs` frames without track queries, cached per
@@ -447,9 +507,13 @@ class DeformableTransformer(nn.Module):
 
     share_frame_pos = True   # forward_flat: unpadded frames read one shared position embedding (A/B, tests)
 
-    def forward_flat(self, src_flatten, lvl_pos_embed_flatten, geo, query_embed=None, targets=None):
+    def forward_flat(self, src_flatten, lvl_pos_embed_flatten, geo, query_embed=None, targets=None,
+                     proposal_bbox_embed=None):
         """deformable_transformer.py:159-257 on flattened inputs."""
-        assert query_embed is not None
+        assert self.two_stage or query_embed is not None
+        if self.two_stage and not fast_path(self):
+            raise NotImplementedError('two-stage Deformable DETR runs the inference path only (eval mode under '
+                                      'torch.no_grad()); its training forward and the enc_outputs losses are not built')
         pad = geo['pad_mask']
         # no frame padded: every frame's position embedding is the same function of the level
         # shapes, so the encoder's projections read frame 0's rows for all frames (x_add of one
@@ -475,7 +539,13 @@ class DeformableTransformer(nn.Module):
         bs, _, c = memory.shape
         query_attn_mask = None
         tracking = targets is not None and 'track_query_hs_embeds' in targets[0]
-        if fast_path(self) and not tracking:
+        enc_outputs_class = enc_outputs_coord_unact = None
+        if self.two_stage:
+            # the reference's two-stage branch builds the queries from the proposals alone (:180-194)
+            tracking = False
+            query_embed_, tgt, reference_points, enc_outputs_class, enc_outputs_coord_unact = \
+                self._proposal_queries(memory, geo, proposal_bbox_embed)
+        elif fast_path(self) and not tracking:
             # inference without track queries: the object queries, their positional half and
             # the initial reference points depend only on parameters -> cached per parameter
             # version, dtype and batch size (no per-forward casts / copies / GEMM)
@@ -504,10 +574,12 @@ class DeformableTransformer(nn.Module):
             query_embed_ = query_embed_.to(dt).contiguous()
         hs, inter_references = self.decoder(tgt, reference_points, memory, geo['spatial_shapes'],
                                             geo['valid_ratios'], query_embed_, pad, query_attn_mask)
-        return hs, memory, init_reference_out, inter_references, None, None
+        return hs, memory, init_reference_out, inter_references, enc_outputs_class, enc_outputs_coord_unact
 
 
 def build_deforamble_transformer(args):
+    if args.two_stage and args.multi_frame_attention:
+        raise NotImplementedError('two_stage with multi_frame_attention is not built')
     num_feature_levels = args.num_feature_levels
     if args.multi_frame_attention:
         num_feature_levels *= 2
