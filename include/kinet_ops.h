@@ -20,8 +20,10 @@ int kinet_layernorm(const void* x, const void* r, const float* gamma, const floa
  * x (N, HW, C) contiguous; y written at y + n*y_batch_stride + p*C + c (so a level can land
  * inside the flattened multi-level src buffer, deformable_transformer.py:145-153).
  * `stats`: caller-provided scratch of kinet_groupnorm_workspace(N, HW, C, groups, dtype) floats;
- * its first 2*N*groups floats hold (sum, sumsq) per image x group on return.  Every reduction
- * runs in a fixed order (no float atomics): reruns are bit-identical. */
+ * its first 2*N*groups floats hold (sum, sumsq) of x - pivot per image x group on return and the
+ * next N*groups the pivots (the rule of the backward: the mean of the group's first <= 8 channels
+ * at its first <= 4 pixels), so mean = pivot + sum / count.  Every reduction runs in a fixed order
+ * (no float atomics): reruns are bit-identical. */
 long kinet_groupnorm_workspace(int N, int HW, int C, int groups, int dtype);
 int kinet_groupnorm(const void* x, const float* gamma, const float* beta, void* y,
                     int N, int HW, int C, int groups, int y_batch_stride, float eps, int dtype,

@@ -147,6 +147,35 @@ __device__ __forceinline__ float group_reduce(float x) {
     return x;
 }
 
+// GroupNorm on (N, HW, C) NHWC, forward (ops.hip) and backward (grad.hip): every sum is taken of
+// x - pivot, the pivot of (image, group) being the mean of the group's first (up to 8) channels at
+// its first (up to 4) pixels: the one-pass variance E[x^2] - mean^2 (and the backward's
+// dy.x - mean dy) cancels against the data's offset otherwise (x = 30 + randn: 3 digits lost).
+// Every kernel forms the pivot with this same serial sum, so they agree bit for bit.
+// c: any channel of the group, cg = C / groups.
+template <typename T>
+__device__ __forceinline__ float gn_pivot(const T* x, int n, int HW, int C, int cg, int c) {
+    const T* p = x + (long)n * HW * C + (c / cg) * cg;
+    const int m = min(cg, 8), np = min(HW, 4);
+    // all 32 loads in flight at once, then one serial sum: a loop over the live samples waits out
+    // a memory latency per element, and so does a load under its own condition (the compiler
+    // gives each a branch and a wait), so the dead samples re-read a live one and are zeroed
+    float v[4][8];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float t = to_f32(p[(long)min(q, np - 1) * C + min(k, m - 1)]);
+            v[q][k] = (q < np && k < m) ? t : 0.f;
+        }
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += v[q][k];
+    return s / (float)(m * np);
+}
+
 // number of workgroups that fill the chip for a grid-stride kernel (256 CUs x 8)
 constexpr int kMaxGridStride = 2048;
 

@@ -523,26 +523,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
 // x, dy: (N, HW, C) NHWC.  Every sum is taken of x - pivot, the pivot of (image, group) being the
 // mean of the group's first (up to 8) channels at its first (up to 4) pixels: the one-pass
 // variance E[x^2] - mean^2 and dy.x - mean dy cancel against the data's offset otherwise
-// (x = 30 + randn: 3 digits lost).  Every kernel forms the pivot with the same serial sum, so
-// they agree bit for bit.
-template <typename T>
-__device__ __forceinline__ float gn_pivot(const T* x, int n, int HW, int C, int cg, int c) {
-    const T* p = x + (long)n * HW * C + (c / cg) * cg;
-    const int m = min(cg, 8), np = min(HW, 4);
-    // all 32 (predicated) loads in flight at once, then one serial sum: a loop over the live
-    // samples waits out a memory latency per element
-    float v[4][8];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[q][k] = (q < np && k < m) ? ld(p + (long)q * C + k) : 0.f;
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s += v[q][k];
-    return s / (float)(m * np);
-}
+// (x = 30 + randn: 3 digits lost).  Every kernel forms the pivot with the same serial sum
+// (gn_pivot in common.h, shared with the forward kernels of ops.hip), so they agree bit for bit.
 
 // pass 1 per (image, HW block): per-channel sums of dy, dy*x, x, x^2 (x shifted by the pivot)
 template <typename T>

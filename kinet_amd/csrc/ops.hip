@@ -113,21 +113,28 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const T* __restrict_
 // GroupNorm on NHWC: per-block partial (sum, sumsq) per image x group, a fixed-order
 // finalize, then apply.  No float atomics anywhere: every reduction runs in a fixed order, so
 // reruns (and graph replays, and two batches in flight) are bit-identical.
-// Workspace (floats): stats [N][2*groups] then partials [N][nblk][2*groups].
+// The sums are of s = x - pivot (gn_pivot in common.h, the backward's rule: raw sums lose
+// mean^2 / var of the one-pass variance's digits); the stats blocks of pixel range 0 leave the
+// pivots in the workspace and the apply kernels use mean = pivot + mean_s.
+// Workspace (floats): stats [N][2*groups], pivots [N][groups], then partials [N][nblk][2*groups].
 // ---------------------------------------------------------------------------------
 template <typename T>
-__global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, float* __restrict__ part, int HW,
-                                                       int C, int groups, int pix_per_block) {
+__global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, float* __restrict__ part,
+                                                       float* __restrict__ piv, int HW, int C, int groups,
+                                                       int pix_per_block) {
     // thread t sums channels t, t+256, ... over this block's pixel range (coalesced rows); the
     // per-channel sums are parked in LDS and each group summed in channel order
     extern __shared__ float red[];   // [2][C]
     const int n = blockIdx.y;
     const int p0 = blockIdx.x * pix_per_block;
     const int p1 = min(HW, p0 + pix_per_block);
+    const int cpg = C / groups;
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        const float pv = gn_pivot(x, n, HW, C, cpg, c);
+        if (blockIdx.x == 0 && c % cpg == 0) piv[(long)n * groups + c / cpg] = pv;
         float s = 0.f, q = 0.f;
         for (int p = p0; p < p1; ++p) {
-            const float t = to_f32(x[((long)n * HW + p) * C + c]);
+            const float t = to_f32(x[((long)n * HW + p) * C + c]) - pv;
             s += t;
             q += t * t;
         }
@@ -135,7 +142,6 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
         red[C + c] = q;
     }
     __syncthreads();
-    const int cpg = C / groups;
     float* out = part + ((long)n * gridDim.x + blockIdx.x) * 2 * groups;
     for (int g = threadIdx.x; g < groups; g += blockDim.x) {
         float s = 0.f, q = 0.f;
@@ -183,6 +189,7 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
 
 template <typename T>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, const float* __restrict__ stats,
+                                                       const float* __restrict__ piv,
                                                        const float* __restrict__ g, const float* __restrict__ b,
                                                        T* __restrict__ y, int N, int HW, int C, int groups,
                                                        long y_bs, float eps) {
@@ -195,8 +202,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
         const int n = (int)(np / HW);
         const long p = np - (long)n * HW;
         const int grp = c / cpg;
-        const float mean = stats[(long)n * 2 * groups + 2 * grp] / cnt;
-        const float var = fmaxf(stats[(long)n * 2 * groups + 2 * grp + 1] / cnt - mean * mean, 0.f);
+        const float ms = stats[(long)n * 2 * groups + 2 * grp] / cnt;   // of x - pivot
+        const float var = fmaxf(stats[(long)n * 2 * groups + 2 * grp + 1] / cnt - ms * ms, 0.f);
+        const float mean = piv[(long)n * groups + grp] + ms;
         const float v = (to_f32(x[i]) - mean) * rsqrtf(var + eps) * g[c] + b[c];
         st(y + (long)n * y_bs + p * C + c, v);
     }
@@ -208,21 +216,33 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
 // groups of 9) a vector may span two groups, so the partials are kept per channel and summed per
 // group over (slot, channel) in a fixed order, and the apply looks the group up per element.
 template <typename T, bool STRADDLE = false>
-__global__ __launch_bounds__(256) void gn_stats_vec_kernel(const T* __restrict__ x, float* __restrict__ part, int HW,
-                                                           int C, int groups, int pix_per_block) {
+__global__ __launch_bounds__(256) void gn_stats_vec_kernel(const T* __restrict__ x, float* __restrict__ part,
+                                                           float* __restrict__ piv, int HW, int C, int groups,
+                                                           int pix_per_block) {
     constexpr int V = 16 / (int)sizeof(T);
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
     __shared__ float red[2][STRADDLE ? 256 * V : 256];   // partials, summed per group in a fixed order
+    __shared__ float pvs[256];                           // one pivot per group (groups <= C / V <= 256)
     const int n = blockIdx.y;
     const int p0 = blockIdx.x * pix_per_block;
     const int p1 = min(HW, p0 + pix_per_block);
     const int CV = C / V, nslot = 256 / CV;
     const int cv = threadIdx.x % CV, slot = threadIdx.x / CV;
+    const int cpg = C / groups;
     float* out = part + ((long)n * gridDim.x + blockIdx.x) * 2 * groups;
+    for (int g = threadIdx.x; g < groups; g += blockDim.x) {
+        const float pv = gn_pivot(x, n, HW, C, cpg, g * cpg);
+        pvs[g] = pv;
+        if (blockIdx.x == 0) piv[(long)n * groups + g] = pv;
+    }
+    __syncthreads();
     if constexpr (STRADDLE) {
-        float s[V], q[V];
+        float s[V], q[V], pv[V];
 #pragma unroll
-        for (int j = 0; j < V; ++j) s[j] = q[j] = 0.f;
+        for (int j = 0; j < V; ++j) {
+            s[j] = q[j] = 0.f;
+            pv[j] = pvs[(cv * V + j) / cpg];
+        }
         if (slot < nslot) {
             const T* xb = x + (long)n * HW * C + cv * V;
             for (int p = p0 + slot; p < p1; p += nslot) {
@@ -230,7 +250,7 @@ __global__ __launch_bounds__(256) void gn_stats_vec_kernel(const T* __restrict__
                 const T* e = reinterpret_cast<const T*>(&v);
 #pragma unroll
                 for (int j = 0; j < V; ++j) {
-                    const float t = to_f32(e[j]);
+                    const float t = to_f32(e[j]) - pv[j];
                     s[j] += t;
                     q[j] += t * t;
                 }
@@ -242,7 +262,6 @@ __global__ __launch_bounds__(256) void gn_stats_vec_kernel(const T* __restrict__
             }
         }
         __syncthreads();
-        const int cpg = C / groups;
         for (int g = threadIdx.x; g < groups; g += blockDim.x) {
             float gs = 0.f, gq = 0.f;
             for (int sl = 0; sl < nslot; ++sl)
@@ -257,13 +276,14 @@ __global__ __launch_bounds__(256) void gn_stats_vec_kernel(const T* __restrict__
     }
     float s = 0.f, q = 0.f;
     if (slot < nslot) {
+        const float pv = pvs[cv * V / cpg];   // the vector's V channels are one group
         const T* xb = x + (long)n * HW * C + cv * V;
         for (int p = p0 + slot; p < p1; p += nslot) {
             const u4 v = *reinterpret_cast<const u4*>(xb + (long)p * C);
             const T* e = reinterpret_cast<const T*>(&v);
 #pragma unroll
             for (int j = 0; j < V; ++j) {
-                const float t = to_f32(e[j]);
+                const float t = to_f32(e[j]) - pv;
                 s += t;
                 q += t * t;
             }
@@ -287,6 +307,7 @@ __global__ __launch_bounds__(256) void gn_stats_vec_kernel(const T* __restrict__
 
 template <typename T, bool STRADDLE = false>
 __global__ __launch_bounds__(256) void gn_apply_vec_kernel(const T* __restrict__ x, const float* __restrict__ stats,
+                                                           const float* __restrict__ piv,
                                                            const float* __restrict__ g, const float* __restrict__ b,
                                                            T* __restrict__ y, int HW, int C, int groups, long y_bs,
                                                            float eps) {
@@ -300,8 +321,9 @@ __global__ __launch_bounds__(256) void gn_apply_vec_kernel(const T* __restrict__
     const int p = i / CV, c0 = (i - p * CV) * V;
     const int cpg = C / groups, grp = c0 / cpg;
     const float cnt = (float)HW * cpg;
-    const float mean = stats[(long)n * 2 * groups + 2 * grp] / cnt;
-    const float var = fmaxf(stats[(long)n * 2 * groups + 2 * grp + 1] / cnt - mean * mean, 0.f);
+    const float ms = stats[(long)n * 2 * groups + 2 * grp] / cnt;   // of x - pivot
+    const float var = fmaxf(stats[(long)n * 2 * groups + 2 * grp + 1] / cnt - ms * ms, 0.f);
+    const float mean = piv[(long)n * groups + grp] + ms;
     const float rstd = rsqrtf(var + eps);
     const u4 v = *reinterpret_cast<const u4*>(x + ((long)n * HW + p) * C + c0);
     const T* e = reinterpret_cast<const T*>(&v);
@@ -311,8 +333,9 @@ __global__ __launch_bounds__(256) void gn_apply_vec_kernel(const T* __restrict__
         // the vector's second group (if it reaches one): channels from its first channel on
         const int split = (grp + 1) * cpg - c0;
         const int grp2 = min(grp + 1, groups - 1);
-        const float mean2 = stats[(long)n * 2 * groups + 2 * grp2] / cnt;
-        const float var2 = fmaxf(stats[(long)n * 2 * groups + 2 * grp2 + 1] / cnt - mean2 * mean2, 0.f);
+        const float ms2 = stats[(long)n * 2 * groups + 2 * grp2] / cnt;
+        const float var2 = fmaxf(stats[(long)n * 2 * groups + 2 * grp2 + 1] / cnt - ms2 * ms2, 0.f);
+        const float mean2 = piv[(long)n * groups + grp2] + ms2;
         const float rstd2 = rsqrtf(var2 + eps);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
@@ -637,7 +660,7 @@ bool gn_vec_ok(const void* x, const void* y, int HW, int C, int groups, int y_ba
 }
 long gn_workspace(int N, int HW, int groups, int ppb) {
     const long nblk = (HW + ppb - 1) / ppb;
-    return 2L * N * groups * (1 + nblk);
+    return (long)N * groups * (3 + 2 * nblk);   // stats, pivots, partials
 }
 }  // namespace
 
@@ -659,7 +682,8 @@ extern "C" int kinet_groupnorm(const void* x, const float* gamma, const float* b
     const bool vec = gn_vec_ok(x, y, HW, C, groups, y_batch_stride, N, dtype);
     const int ppb = vec ? 128 : 64;
     const int nblk = (HW + ppb - 1) / ppb;
-    float* part = stats + 2L * N * groups;
+    float* piv = stats + 2L * N * groups;
+    float* part = piv + (long)N * groups;
     const dim3 g1(nblk, N);
     if (vec) {
         const int V = dtype == KINET_F32 ? 4 : 8;
@@ -667,11 +691,11 @@ extern "C" int kinet_groupnorm(const void* x, const float* gamma, const float* b
         const bool straddle = (C / groups) % V != 0;
 #define GNV(TT, SD)                                                                                              \
     do {                                                                                                         \
-        hipLaunchKernelGGL((gn_stats_vec_kernel<TT, SD>), g1, dim3(256), 0, s, (const TT*)x, part, HW, C, groups, \
-                           ppb);                                                                                 \
+        hipLaunchKernelGGL((gn_stats_vec_kernel<TT, SD>), g1, dim3(256), 0, s, (const TT*)x, part, piv, HW, C,   \
+                           groups, ppb);                                                                         \
         hipLaunchKernelGGL(gn_finalize_kernel, dim3(N), dim3(256), 0, s, (const float*)part, stats, nblk, groups); \
-        hipLaunchKernelGGL((gn_apply_vec_kernel<TT, SD>), g2, dim3(256), 0, s, (const TT*)x, stats, gamma, beta, \
-                           (TT*)y, HW, C, groups, (long)y_batch_stride, eps);                                    \
+        hipLaunchKernelGGL((gn_apply_vec_kernel<TT, SD>), g2, dim3(256), 0, s, (const TT*)x, stats,              \
+                           (const float*)piv, gamma, beta, (TT*)y, HW, C, groups, (long)y_batch_stride, eps);    \
     } while (0)
         if (straddle) {
             if (dtype == KINET_BF16) GNV(bf16_t, true);
@@ -688,12 +712,13 @@ extern "C" int kinet_groupnorm(const void* x, const float* gamma, const float* b
     }
     KINET_CHECK_ARG(C <= 8192, "groupnorm: C up to 8192 on the scalar path");
     DISPATCH_T(dtype, hipLaunchKernelGGL((gn_stats_kernel<T>), g1, dim3(256), 2 * C * sizeof(float), s,
-                                         (const T*)x, part, HW, C, groups, ppb));
+                                         (const T*)x, part, piv, HW, C, groups, ppb));
     hipLaunchKernelGGL(gn_finalize_kernel, dim3(N), dim3(256), 0, s, (const float*)part, stats, nblk, groups);
     KINET_LAUNCH_CHECK();
     const long total = (long)N * HW * C;
     DISPATCH_T(dtype, hipLaunchKernelGGL((gn_apply_kernel<T>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)x,
-                                         stats, gamma, beta, (T*)y, N, HW, C, groups, (long)y_batch_stride, eps));
+                                         stats, (const float*)piv, gamma, beta, (T*)y, N, HW, C, groups,
+                                         (long)y_batch_stride, eps));
     KINET_LAUNCH_CHECK();
     return KINET_OK;
 }

@@ -455,6 +455,150 @@ def gn_case(N, HW, C, dtype, seed=0, offset=0.0):
     return x, dy, gamma
 
 
+# -------------------------------------------------------------------- GroupNorm forward
+def gn_fwd_path(dtype, C, G, aligned=True, y_stride=None, HW=1):
+    """Restatement of kinet_groupnorm's dispatch (gn_vec_ok and the straddle condition): 'scalar',
+    'vector' or 'straddle'.  V = 16 bytes of `dtype`; the vector kernels need whole vectors per row
+    (C % V == 0), groups of at least V channels (a vector reaches at most two groups), C / V <= 256
+    (one thread per vector of a row), an output batch stride of whole vectors (y_stride, default
+    packed = a multiple of C), 16-byte aligned x and y (`aligned`) and HW * C / V < 2^31; a group
+    size that is no multiple of V makes vectors straddle two groups."""
+    if dtype == torch.float64:
+        return 'scalar'
+    V = 4 if dtype == torch.float32 else 8
+    y_stride = HW * C if y_stride is None else y_stride
+    cg = C // G
+    if not (C % V == 0 and cg >= V and C // V <= 256 and y_stride % V == 0 and aligned and HW * (C // V) < 2 ** 31):
+        return 'scalar'
+    return 'straddle' if cg % V else 'vector'
+
+
+def gn_fwd_chain(path, dtype, HW, C, G):
+    """Serial f32 adds behind one group sum on `path`:
+      scalar:   a thread sums one channel over its block's pixels (ppb = 64), then the group's cg
+                channel sums serially;
+      vector:   a thread sums the V elements of its vector over every nslot-th pixel of the block
+                (ppb = 128, nslot = 256 / (C/V) row groups), then nslot * (cg/V) thread sums serially;
+      straddle: the same per channel (no V), then nslot * cg channel sums serially;
+      finalize: tpo = 256 / (2 G) threads (1 above 256 outputs) each sum every tpo-th block partial,
+                then the tpo thread sums serially."""
+    V = 4 if dtype == torch.float32 else 8
+    cg = C // G
+    ppb = 64 if path == 'scalar' else 128
+    rows = min(HW, ppb)
+    nblk = (HW + ppb - 1) // ppb
+    if path == 'scalar':
+        block = rows + cg
+    else:
+        nslot = 256 // (C // V)
+        per_thread = (rows + nslot - 1) // nslot
+        block = per_thread * V + nslot * (cg // V) if path == 'vector' else per_thread + nslot * cg
+    tpo = 256 // (2 * G) if 2 * G <= 256 else 1
+    return block + (nblk + tpo - 1) // tpo + tpo
+
+
+def gn_fwd_ref(x, gamma, beta, G, eps, path):
+    """f64 GroupNorm forward on (N, HW, C) NHWC: {'y', 'yA', 'y_c'}, |kernel - y| <= y_c u yA.
+    The kernel sums s = x - pivot and s^2 per (image, group) (gn_pivot, the backward's rule) with
+    n = gn_fwd_chain + 2 roundings (the square, the division by the count) on either sum, and
+      mean = pivot + mean_s, var = E[s^2] - mean_s^2, y = (x - mean) rstd gamma + beta.
+    x - mean: mean_s carries n + 1 roundings of its own majorant; forming pivot + mean_s rounds once
+      at the data's magnitude |mean|, not the shifted one, and so may x - pivot where the two are
+      not within a factor 2: 2 u |mean|, which no count on a shifted majorant covers -- it enters yA
+      as 2 |mean| / c, so that c u yA holds exactly 2 u |mean| rstd |gamma| of it; the subtraction 1.
+    rstd: the one-pass variance has relative error (n + 3) kappa u, kappa = (E[s^2] + mean_s^2) /
+      (var + eps) in f64 per group (a few units whatever the data's offset -- with raw sums it is
+      ~ 2 mean^2 / var); rstd takes half, + 2 for rsqrtf.
+    The two products and the add of beta: 3.     -> c = n + 2 + 0.5 (n + 3) kappa + 2 + 3."""
+    N, HW, C = x.shape
+    cg = C // G
+    X = x.double().view(N, HW, G, cg)
+    gm, bt = gamma.double().view(1, 1, G, cg), beta.double().view(1, 1, G, cg)
+    ax = (1, 3)
+    mean = X.mean(ax, keepdim=True)
+    var = ((X - mean) ** 2).mean(ax, keepdim=True)
+    e = eps32(eps)
+    rstd = (var + e).rsqrt()
+    Sx = X - gn_pivot(X)
+    kappa = ((Sx * Sx).mean(ax, keepdim=True) + Sx.mean(ax, keepdim=True) ** 2) / (var + e)
+    n = gn_fwd_chain(path, x.dtype, HW, C, G) + 2
+    c = n + 7 + 0.5 * (n + 3) * kappa
+    SA = Sx.abs()
+    A = (SA + SA.mean(ax, keepdim=True) + 2 * mean.abs() / c) * rstd * gm.abs() + bt.abs()
+    return {'y': ((X - mean) * rstd * gm + bt).reshape(N, HW, C), 'yA': A.reshape(N, HW, C),
+            'y_c': c.expand(N, HW, G, cg).reshape(N, HW, C)}
+
+
+@functools.lru_cache(maxsize=None)
+def gn_fwd_case(N, HW, C, dtype, seed=0, offset=0.0):
+    """Seeded GroupNorm-forward inputs: x rounded to `dtype`, gamma and beta f32."""
+    g = torch.Generator().manual_seed(seed + N * 7919 + HW * 131 + C)
+    x = (offset + torch.randn(N, HW, C, generator=g)).to(dtype)
+    return x, torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g)
+
+
+@functools.lru_cache(maxsize=None)
+def gn_fwd_torch_f32(N, HW, C, G, seed, offset):
+    """torch's CPU f32 group_norm on gn_fwd_case's f32 inputs, as (N, HW, C): the guards' yardstick."""
+    x, gamma, beta = gn_fwd_case(N, HW, C, torch.float32, seed, offset)
+    return torch.nn.functional.group_norm(x.permute(0, 2, 1).contiguous(), G, gamma, beta, 1e-5).permute(0, 2, 1)
+
+
+_F32, _BF16, _F16 = torch.float32, torch.bfloat16, torch.float16
+_ALL = (_F32, _BF16, _F16)
+# (N, HW, C, G), dtypes, the path expected by reading the launcher.
+# scalar: C % V != 0; groups of 3; the ppb = 64 edges with groups of 1; one pixel; 2 G = 320 > 256 (the
+# finalize's second `base` pass); 2 G = 256 over 10 blocks of 64 (tpo = 1: the finalize's unrolled 8 and a
+# tail of 2).  (1, 1, 8, 2): groups of 4 are one f32 vector each, and half a 16-bit one.
+GN_FWD_SCALAR = [((2, 5, 30, 6), _ALL), ((2, 35, 36, 12), _ALL), ((1, 63, 8, 8), _ALL), ((1, 64, 8, 8), _ALL),
+                 ((1, 65, 8, 8), _ALL), ((1, 1, 8, 2), (_BF16, _F16)), ((1, 1, 6, 2), _ALL),
+                 ((1, 40, 320, 160), _ALL), ((1, 600, 256, 128), _ALL)]
+# vector: one pixel; the ppb = 128 edges; the model's shape class; C/V = 256 (one slot) with 2 G = 256
+# (tpo = 1); tpo = 1 over 11 blocks (unrolled 8 and a tail of 3); tpo = 128; 34 blocks on tpo = 32 threads
+GN_FWD_VECTOR = [((1, 1, 8, 2), (_F32,)), ((2, 127, 32, 4), _ALL), ((2, 128, 32, 4), _ALL), ((2, 129, 32, 4), _ALL),
+                 ((3, 273, 256, 32), _ALL), ((1, 300, 1024, 128), (_F32,)), ((1, 1400, 512, 128), (_F32,)),
+                 ((1, 40, 8, 1), _ALL), ((1, 4300, 32, 4), _ALL)]
+# straddle: the model's class (groups of 9); 2 G = 12 does not divide 256; groups of 9 in 16-bit vectors of
+# 8, the split on every position 1..7
+GN_FWD_STRADDLE = [((1, 300, 288, 32), _ALL), ((2, 35, 36, 6), (_F32,)), ((1, 129, 72, 8), (_BF16, _F16))]
+
+
+def gn_fwd_cases(path):
+    table = {'scalar': GN_FWD_SCALAR, 'vector': GN_FWD_VECTOR, 'straddle': GN_FWD_STRADDLE}[path]
+    return [(s, d) for s, ds in table for d in ds]
+
+
+GN_GUARD = [(2, 273, 256, 32, 'vector'), (1, 300, 288, 32, 'straddle'), (2, 200, 36, 12, 'scalar')]
+GN_GUARD_SEED, GN_GUARD_OFFSET = 3, 30.0
+
+
+# ------------------------------------------------------- fused LayerNorm epilogues
+def ln_epilogue_ref(pre64, gamma, beta, eps):
+    """Row-wise f64 LayerNorm of the pre-activation pre64 (rows, d): {'y', 'yA', 'y_c'}.  The fused
+    epilogues are two-pass (the mean, then the sum of (v - mean)^2), each reduction at most d serial
+    adds however the row is spread over lanes:
+      v - mean: the mean d + 1 roundings of mean |v|, the subtraction 1;  rstd: half of the variance's
+      d + 3 (the squares are of the already centred values: no cancellation), + 2 for rsqrtf;  the
+      two products and the add of beta 3                             -> c = 1.5 d + 9
+    on yA = (|v - mean| + mean |v|) rstd |gamma| + |beta|: the mean's error is relative to the row's
+    magnitude, so a row of 100 + O(1) has a majorant ~100x its values, as it must."""
+    v = pre64.double()
+    d = v.shape[-1]
+    mean = v.mean(-1, keepdim=True)
+    rstd = (((v - mean) ** 2).mean(-1, keepdim=True) + eps32(eps)).rsqrt()
+    gm, bt = gamma.double(), beta.double()
+    return {'y': (v - mean) * rstd * gm + bt,
+            'yA': ((v - mean).abs() + v.abs().mean(-1, keepdim=True)) * rstd * gm.abs() + bt.abs(),
+            'y_c': 1.5 * d + 9, 'rstd': rstd}
+
+
+def ln_epilogue_yardstick(pre64, gamma, beta, eps=1e-5):
+    """(y64, max error of torch's CPU f32 layer_norm of the f32-rounded pre-activation against it)."""
+    y = ln_epilogue_ref(pre64, gamma, beta, eps)['y']
+    t = torch.nn.functional.layer_norm(pre64.float(), (pre64.shape[-1],), gamma.float(), beta.float(), eps)
+    return y, (t.double() - y).abs().max().item()
+
+
 # ------------------------------------------------------------------- attention fwd / bwd
 def attn_ref(q, k, v, do, heads, scale, key_mask=None, keep=None, p=0.0, dtype=torch.float64):
     """Scaled-dot-product attention and its backward in plain torch ops at `dtype` (f64: the

@@ -402,3 +402,163 @@ def test_inv_sigmoid_ref_equals_f64_autograd():
     yt.backward(dy.double())
     assert torch.equal(y, yt.detach()) and (dx - xt.grad).abs().max().item() <= 1e-9 * dx.abs().max().item()
     assert (R.inverse_sigmoid_ref(x, e) - y).abs().max().item() == 0
+
+
+# -------------------------------------------- GroupNorm forward / fused LayerNorm epilogues
+GN_FWD_TABLE = [(s, d, p) for p in ('scalar', 'vector', 'straddle') for s, d in R.gn_fwd_cases(p)]
+
+
+@pytest.mark.parametrize('shape,dtype,path', GN_FWD_TABLE, ids=lambda v: str(v).replace('torch.', '').replace(' ', ''))
+def test_gn_fwd_path_table(shape, dtype, path):
+    N_, HW, C, G = shape
+    assert R.gn_fwd_path(dtype, C, G, HW=HW) == path
+    assert R.gn_fwd_path(dtype, C, G, aligned=False, HW=HW) == 'scalar'
+    assert R.gn_fwd_chain(path, dtype, HW, C, G) >= 3
+
+
+def test_gn_fwd_path_conditions():
+    f32, bf16 = torch.float32, torch.bfloat16
+    assert R.gn_fwd_path(torch.float64, 32, 4) == 'scalar'
+    assert R.gn_fwd_path(f32, 32, 4, y_stride=129 * 32 + 64, HW=129) == 'vector'
+    assert R.gn_fwd_path(f32, 32, 4, y_stride=129 * 32 + 3, HW=129) == 'scalar'
+    assert R.gn_fwd_path(bf16, 32, 4, y_stride=129 * 32 + 4, HW=129) == 'scalar'       # V = 8
+    assert R.gn_fwd_path(f32, 1028, 4) == 'scalar' and R.gn_fwd_path(f32, 1024, 4) == 'vector'   # C / V <= 256
+    assert R.gn_fwd_path(bf16, 2048, 4) == 'vector' and R.gn_fwd_path(bf16, 2056, 4) == 'scalar'
+    assert R.gn_fwd_path(f32, 24, 8) == 'scalar' and R.gn_fwd_path(f32, 24, 4) == 'straddle'     # groups of 3, 6
+    for N_, HW, C, G, path in R.GN_GUARD:
+        assert R.gn_fwd_path(f32, C, G, HW=HW) == path
+    # the chains, by hand: (2, 35, 36, 12) scalar: 35 pixels + 3 channels, 1 block on tpo = 10 threads
+    assert R.gn_fwd_chain('scalar', f32, 35, 36, 12) == 35 + 3 + 1 + 10
+    # (3, 273, 256, 32) f32 vector: nslot = 4, 32 pixels x 4 elements, 4 slots x 2 vectors; 3 blocks on tpo = 4
+    assert R.gn_fwd_chain('vector', f32, 273, 256, 32) == 32 * 4 + 4 * 2 + 1 + 4
+    # (1, 300, 288, 32) f32 straddle: nslot = 3, 43 pixels, 3 slots x 9 channels; 3 blocks on tpo = 4
+    assert R.gn_fwd_chain('straddle', f32, 300, 288, 32) == 43 + 27 + 1 + 4
+    # (1, 40, 320, 160) scalar: 40 + 2, one block, tpo = 1
+    assert R.gn_fwd_chain('scalar', f32, 40, 320, 160) == 40 + 2 + 1 + 1
+
+
+@pytest.mark.parametrize('shape', [(2, 5, 30, 6), (1, 40, 8, 8), (2, 40, 8, 1), (2, 35, 36, 6), (1, 1, 8, 2)])
+def test_gn_fwd_ref_equals_f64_group_norm(shape):
+    N_, HW, C, G = shape
+    x, gamma, beta = (t.double() for t in R.gn_fwd_case(N_, HW, C, torch.float32))
+    want = F.group_norm(x.permute(0, 2, 1).contiguous(), G, gamma, beta, R.eps32(1e-5)).permute(0, 2, 1)
+    ref = R.gn_fwd_ref(x.float(), gamma, beta, G, 1e-5, R.gn_fwd_path(torch.float32, C, G, HW=HW))
+    assert (ref['y'] - want).abs().max().item() <= 1e-11
+    assert (ref['yA'] >= ref['y'].abs() * (1 - 1e-12)).all() and (ref['y_c'] >= 10).all()
+
+
+@pytest.mark.parametrize('rows,d,offset', [(5, 256, 0.0), (7, 200, 100.0), (3, 288, 100.0)])
+def test_ln_epilogue_ref_equals_f64_layer_norm(rows, d, offset):
+    g = torch.Generator().manual_seed(rows + d)
+    pre = offset + torch.randn(rows, d, generator=g, dtype=torch.float64)
+    gamma, beta = torch.rand(d, generator=g) + 0.5, torch.randn(d, generator=g)
+    ref = R.ln_epilogue_ref(pre, gamma, beta, 1e-5)
+    want = F.layer_norm(pre, (d,), gamma.double(), beta.double(), R.eps32(1e-5))
+    assert (ref['y'] - want).abs().max().item() <= 1e-11
+    assert (ref['yA'] >= ref['y'].abs() * (1 - 1e-12)).all()
+    y, t = R.ln_epilogue_yardstick(pre, gamma, beta)
+    assert torch.equal(y, ref['y']) and 0 < t < 1e-4
+
+
+def _gn_fwd_emulate(x, gamma, beta, G, eps, ppb, shifted):
+    """kinet_groupnorm's arithmetic in f32 numpy: per block of ppb pixels the per-channel serial sums of
+    s and s^2, the group's channels in order, the blocks in order; mean = pivot + mean_s, the one-pass
+    variance E[s^2] - mean_s^2.  s = x - pivot (the pivot formed as gn_pivot, in f32) or, shifted =
+    False, the raw x."""
+    f = np.float32
+    N_, HW, C = x.shape
+    cg = C // G
+    X = x.numpy().astype(f).reshape(N_, HW, G, cg)
+    if shifted:
+        m, npx = min(cg, 8), min(HW, 4)
+        piv = (np.cumsum(X[:, :npx, :, :m].transpose(0, 2, 1, 3).reshape(N_, G, npx * m), axis=-1, dtype=f)[..., -1]
+               / f(m * npx)).reshape(N_, 1, G, 1)
+    else:
+        piv = np.zeros((N_, 1, G, 1), f)
+    S = X - piv
+    s = np.zeros((N_, G), f)
+    q = np.zeros((N_, G), f)
+    for p0 in range(0, HW, ppb):
+        blk = S[:, p0:p0 + ppb]
+        cs = np.cumsum(blk, axis=1, dtype=f)[:, -1]                      # (N, G, cg): a channel's pixels
+        cq = np.cumsum(blk * blk, axis=1, dtype=f)[:, -1]
+        s = s + np.cumsum(cs, axis=-1, dtype=f)[..., -1]                 # the group's channels, then the blocks
+        q = q + np.cumsum(cq, axis=-1, dtype=f)[..., -1]
+    cnt = f(HW * cg)
+    ms = s / cnt
+    var = np.maximum(q / cnt - ms * ms, f(0))
+    rstd = (f(1) / np.sqrt(var + f(eps))).astype(f).reshape(N_, 1, G, 1)
+    mean = piv + ms.reshape(N_, 1, G, 1)
+    y = (X - mean) * rstd * gamma.numpy().astype(f).reshape(1, 1, G, cg) + beta.numpy().astype(f).reshape(1, 1, G, cg)
+    assert y.dtype == f
+    return torch.from_numpy(y.reshape(N_, HW, C))
+
+
+@pytest.mark.parametrize('N_,HW,C,G,path', R.GN_GUARD)
+def test_gn_fwd_guard_discriminates_raw_from_shifted_sums(N_, HW, C, G, path):
+    """On the guard's inputs (x = 30 + randn) an f32 emulation of the one-pass variance of raw sums
+    misses the guard's bound, 4x torch's CPU f32 error, and the same emulation summing x - pivot
+    (gn_pivot) meets it: the guard tells the two apart, and asks nothing f32 cannot give."""
+    x, gamma, beta = R.gn_fwd_case(N_, HW, C, torch.float32, R.GN_GUARD_SEED, R.GN_GUARD_OFFSET)
+    ref = R.gn_fwd_ref(x, gamma, beta, G, 1e-5, path)
+    t = (R.gn_fwd_torch_f32(N_, HW, C, G, R.GN_GUARD_SEED, R.GN_GUARD_OFFSET).double() - ref['y']).abs().max().item()
+    ppb = 64 if path == 'scalar' else 128
+    raw = (_gn_fwd_emulate(x, gamma, beta, G, 1e-5, ppb, False).double() - ref['y']).abs()
+    shifted = (_gn_fwd_emulate(x, gamma, beta, G, 1e-5, ppb, True).double() - ref['y']).abs()
+    print(f'gn fwd guard ({N_}, {HW}, {C}, {G}) {path}: torch CPU f32 err {t:.3e}, bound {4 * t:.3e}, raw sums '
+          f'{raw.max().item():.3e}, shifted sums {shifted.max().item():.3e}')
+    assert raw.max().item() > 4 * t
+    assert shifted.max().item() <= 4 * t
+    # the shifted emulation also sits inside the per-element bound of gn_fwd_ref
+    assert (shifted <= ref['y_c'] * R.U32 * ref['yA']).all()
+
+
+def _lane_sum(a):
+    """Row sums in f32 the way a wavefront takes them: lane l adds elements l, l + 64, ... serially, then
+    the 64 lane sums combine in a 6-level tree."""
+    f = np.float32
+    rows, d = a.shape
+    nv = -(-d // 64)
+    lanes = np.cumsum(np.pad(a, ((0, 0), (0, nv * 64 - d))).reshape(rows, nv, 64), axis=1, dtype=f)[:, -1]
+    while lanes.shape[1] > 1:
+        h = lanes.shape[1] // 2
+        lanes = lanes[:, :h] + lanes[:, h:]
+    assert lanes.dtype == f
+    return lanes
+
+
+def _ln_emulate(pre64, gamma, beta, eps, one_pass):
+    """A row LayerNorm in f32 numpy with a wavefront's sums: two-pass (mean, then the sum of
+    (v - mean)^2) or one-pass (the sums of v and v^2)."""
+    f = np.float32
+    v = pre64.numpy().astype(f)
+    d = f(v.shape[-1])
+    mean = _lane_sum(v) / d
+    if one_pass:
+        var = np.maximum(_lane_sum(v * v) / d - mean * mean, f(0))
+    else:
+        var = _lane_sum((v - mean) * (v - mean)) / d
+    y = (v - mean) * (f(1) / np.sqrt(var + f(eps))).astype(f) * gamma.numpy().astype(f) + beta.numpy().astype(f)
+    assert y.dtype == f
+    return torch.from_numpy(y)
+
+
+@pytest.mark.parametrize('d', [256, 288, 200])
+def test_ln_epilogue_bounds_discriminate_one_pass_from_two_pass(d):
+    """Rows of 100 + O(1): an f32 one-pass LayerNorm misses both the f32 bound (4x torch's CPU f32
+    error) and the f16 bound (one output rounding of the f64 result + the same 4x term), even before
+    its own output rounding; the two-pass form meets the f32 bound, and its f16 rounding the f16 one."""
+    g = torch.Generator().manual_seed(d)
+    pre = 100.0 + torch.randn(37, d, generator=g, dtype=torch.float64) * 1.5
+    gamma, beta = torch.rand(d, generator=g) + 0.5, torch.randn(d, generator=g)
+    y, t = R.ln_epilogue_yardstick(pre, gamma, beta)
+    one = _ln_emulate(pre, gamma, beta, 1e-5, True)
+    two = _ln_emulate(pre, gamma, beta, 1e-5, False)
+    e1, e2 = (one.double() - y).abs(), (two.double() - y).abs()
+    print(f'ln epilogue d={d} offset 100: torch CPU f32 err {t:.3e}, bound {4 * t:.3e}, one-pass {e1.max().item():.3e}, '
+          f'two-pass {e2.max().item():.3e}')
+    assert e2.max().item() <= 4 * t < e1.max().item()
+    tol16 = R.OUT_ROUND[torch.float16] * y.abs() + 4 * t
+    assert (e1 > tol16).any()
+    assert ((one.half().double() - y).abs() > tol16).any()
+    assert ((two.half().double() - y).abs() <= tol16).all()
