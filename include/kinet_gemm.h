@@ -118,6 +118,15 @@ int kinet_conv2d_splitk(const void* X, const void* Wt, void* Y, int batch, int H
 int kinet_stem_conv_image(const float* img, const void* w_packed, const float* scale, const float* bias,
                           void* Y, int N, int H, int W, int dtype, kinet_stream_t stream);
 
+/* The stem above followed by torchvision's maxpool (3x3 / stride 2 / pad 1, backbone.py:102's
+ * ResNet body) in one launch: the conv map is never written.  Y NHWC (N, Hp, Wp, 64) with
+ * Ho = (H-1)/2+1, Hp = (Ho-1)/2+1 (Wo, Wp alike), bit-identical to kinet_maxpool2d_3x3s2 of
+ * kinet_stem_conv_image's output.  A workgroup walks a 62-conv-column strip downwards over
+ * `seg_tiles` 4-row tiles carrying the conv row the next tile's pool window needs; seg_tiles = 0
+ * lets the launcher choose (the value only moves work between workgroups, never the result). */
+int kinet_stem_pool_image(const float* img, const void* w_packed, const float* scale, const float* bias, void* Y,
+                          int N, int H, int W, int dtype, int seg_tiles, kinet_stream_t stream);
+
 /* Diagnostic kernel-selection knob (no reference counterpart; used by the kernel
  * benchmarks to A/B GEMM kernels in one process).  bit 1: allow the 512-thread
  * 256x256-tile LDS-DMA kernel for large-M problems; bit 2: never use the

@@ -52,6 +52,7 @@ _SIGS = {
     'kinet_ffn_pack_attn': [P, P, P, P, I, I, I, P],
     'kinet_attn_out_ffn_fused': [P, I, P, I, P, P, P, P, F, P, P, P, P, F, P, I, I, I, I, I, P],
     'kinet_stem_conv_image': [P, P, P, P, P, I, I, I, I, P],
+    'kinet_stem_pool_image': [P, P, P, P, P, I, I, I, I, I, P],
     'kinet_bottleneck_pack': [P, P, P, P, P, I, I, I, I, P],
     'kinet_bottleneck_pair': [P, I, P, P, P, P, P, P, I, I, I, I, I, P],
     'kinet_bottleneck_pack_ds': [P, P, P, P, P, P, P, I, I, I, I, P],

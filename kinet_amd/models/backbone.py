@@ -70,6 +70,10 @@ FUSE_DOWNSAMPLE = True
 # 16-bit stem straight from the f32 image (kinet_stem_conv_image); False: pack_image_kwfold +
 # the folded conv (A/B: bench.py --stem-image 0)
 STEM_FROM_IMAGE = True
+# With STEM_FROM_IMAGE: the stem and the 3x3 / 2 max-pool as one launch (kinet_stem_pool_image),
+# the conv map is never written; False runs kinet_stem_conv_image + kinet_maxpool2d_3x3s2
+# (bit-identical; A/B: tools/stem_pool_ab.py, profiles/stem_pool_ab.txt)
+FUSE_STEM_POOL = True
 
 
 def conv_bn(x, conv, bn, relu, residual=None, cin_pad=None):
@@ -252,6 +256,9 @@ class ResNetBody(nn.Module):
         kh, kw = c1.kernel_size
         cg = (3 * kw + 7) // 8 * 8
         scale, bias = self.bn1.folded()
+        if STEM_FROM_IMAGE and FUSE_STEM_POOL and dtype in (torch.bfloat16, torch.float16):
+            x = K.stem_pool_image(img_nchw, K.pack_stem_weight(c1.weight, dtype, cg), scale, bias, dtype)
+            return forward_layer_nhwc(self.layer1, x, None, next_block)
         if STEM_FROM_IMAGE and dtype in (torch.bfloat16, torch.float16):
             # the folded rows built in LDS from the f32 image (no packed copy of the image)
             x = K.stem_conv_image(img_nchw, K.pack_stem_weight(c1.weight, dtype, cg), scale, bias, dtype)
