@@ -142,6 +142,26 @@ int kinet_stem_pool_image(const float* img, const void* w_packed, const float* s
  * NOT reach the backward kernels launched through autograd (only forward / direct calls). */
 int kinet_gemm_set_flags(int flags);
 
+/* Diagnostic tile override of the tiled kernel (0, 0 = heuristic), per calling thread: 32x64,
+ * {64,128}x{64,128}, and the 8-wave 256x128 / 128x256 / 256x256 LDS-DMA tiles, which exist for
+ * 16-bit operands without A2 only -- a launch that has no instantiation of the forced tile
+ * returns KINET_ERR_ARG before any kernel starts.  Ignored by the fused-LayerNorm launches. */
+int kinet_gemm_force_tile(int bm, int bn);
+
+/* Which kernel served the calling thread's last GEMM / convolution call (host-side record, no
+ * reference counterpart; tests assert through it that the kernel they mean to test ran):
+ * (family << 20) | (bm << 10) | bn.  family: 0 none yet, 1 tiled (gemm_kernel), 2 tiled with
+ * LDS-DMA staging (flag 16 and the 128x320 LayerNorm tile), 3 the 8-wave LDS-DMA tiles,
+ * 4 resident-weight GEMM, 5 resident-weight conv, 6 direct 3x3 64 -> 64 conv, 7 stem conv,
+ * 8 split-K (bm, bn: the tile of the partial-sum grid).  bm, bn: the tile of the last grid
+ * launched by the tiled families, 0 for the special-cased kernels. */
+int kinet_gemm_last_kernel(void);
+
+/* C / R alignment: the fused epilogue moves 4 output elements per access whenever ldc (and ldr)
+ * are multiples of 4, so kinet_gemm(_ex), kinet_gemm_headmajor* and kinet_conv2d(_ex) return
+ * KINET_ERR_ARG for a C (or R) that is not aligned to 4 output elements in that case; other
+ * strides, and the split-K forms (element-wise finalize), need element alignment only. */
+
 /* Launch-fill policy (no reference counterpart), process-wide.  1 = "solo": the caller keeps one
  * batch in flight, so no other stream's work fills CUs a launch leaves idle -- shapes whose
  * default tiles cover under 60 % of one round of workgroups per CU (config 5's stage-3 3x3

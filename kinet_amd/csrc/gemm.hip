@@ -50,6 +50,15 @@ int kinet_solo_launch = 0;                 // declared in common.h (kinet_set_so
 namespace {
 // diagnostic tile override for gemm_kernel (kinet_gemm_force_tile; 0 = heuristic)
 thread_local int force_bm = 0, force_bn = 0;
+// the kernel family and tile of the calling thread's last launch (kinet_gemm_last_kernel): host
+// side only, written by dispatch<> / run_splitk / launch()'s run, read by tests and tools
+enum { FAM_NONE = 0, FAM_TILED, FAM_TILED_DMA, FAM_DMA8, FAM_RW, FAM_RW_CONV, FAM_CONV3X3, FAM_STEM, FAM_SPLITK };
+thread_local int last_family = FAM_NONE, last_bm = 0, last_bn = 0;
+inline void record_kernel(int family, int bm, int bn) {
+    last_family = family;
+    last_bm = bm;
+    last_bn = bn;
+}
 
 
 template <int BM, int BN>
@@ -526,6 +535,12 @@ int launch(const GemmArgs& a, hipStream_t stream) {
         bn = bn8;
     }
     if (force_bm && !ln) {
+        // the 256-row / 256-column tiles exist as 8-wave LDS-DMA kernels only: 16-bit operands, no
+        // load-time A2 add (anything else fell through to the 64x64 kernel on a grid sized for
+        // the forced tile, which left most rows unwritten)
+        KINET_CHECK_ARG((force_bm != 256 && force_bn != 256) || (sizeof(T) == 2 && a.A2 == nullptr),
+                        "gemm: forced tile %dx%d needs 16-bit operands and no A2 (no such instantiation)", force_bm,
+                        force_bn);
         bm = force_bm;
         bn = force_bn;
     }
@@ -545,10 +560,14 @@ int launch(const GemmArgs& a, hipStream_t stream) {
         if constexpr (sizeof(T) == 2) {
             if (ln && tbm == 128 && tbn == 320) {
                 hipLaunchKernelGGL((gemm_dma_kernel<T, TO, 128, 320, 2, 2, CONV, true, 2>), grid, block, 0, stream, g, nNt);
+                record_kernel(FAM_TILED_DMA, tbm, tbn);
                 KINET_LAUNCH_CHECK();
                 return KINET_OK;
             }
-            if (g.A2 == nullptr && (tbm == 256 || tbn == 256)) {
+            // (128x256 or 256 rows -- NOT the 32x256 / 64x256 LayerNorm tiles of the 4-wave kernel:
+            // they came here too, and ran the 256x256 kernel on a grid sized for 32- or 64-row tiles,
+            // 7 of 8 (3 of 4) workgroups multiplying zeros past the last row)
+            if (g.A2 == nullptr && (tbm == 256 || (tbm == 128 && tbn == 256))) {
                 const dim3 blk(512);
                 if (ln)
                     hipLaunchKernelGGL((gemm_dma_kernel<T, TO, 256, 256, 2, 4, CONV, true, 2>), grid, blk, 0, stream, g, nNt);
@@ -558,6 +577,7 @@ int launch(const GemmArgs& a, hipStream_t stream) {
                     hipLaunchKernelGGL((gemm_dma_kernel<T, TO, 256, 128, 4, 2, CONV, false>), grid, blk, 0, stream, g, nNt);
                 else
                     hipLaunchKernelGGL((gemm_dma_kernel<T, TO, 128, 256, 2, 4, CONV, false>), grid, blk, 0, stream, g, nNt);
+                record_kernel(FAM_DMA8, ln ? 256 : tbm, ln ? 256 : tbn);
                 KINET_LAUNCH_CHECK();
                 return KINET_OK;
             }
@@ -580,8 +600,14 @@ int launch(const GemmArgs& a, hipStream_t stream) {
         else if (tbm == 128 && tbn == 128) L_(128, 128, 2, 2, false);
         else if (tbm == 128 && tbn == 64) L_(128, 64, 2, 2, false);
         else if (tbm == 64 && tbn == 128) L_(64, 128, 2, 2, false);
-        else L_(64, 64, 2, 2, false);
+        else if (tbm == 64 && tbn == 64) L_(64, 64, 2, 2, false);
+        else {
+            set_error("gemm: no %dx%d tile for these operands", tbm, tbn);
+            return KINET_ERR_ARG;
+        }
 #undef L_
+        record_kernel(dma ? FAM_TILED_DMA : FAM_TILED, ln ? (tbm == 32 ? 32 : 64) : tbm,
+                      ln ? (tbn == 256 ? 256 : 320) : tbn);
         KINET_LAUNCH_CHECK();
         return KINET_OK;
     };
@@ -633,18 +659,22 @@ int launch(const GemmArgs& a, hipStream_t stream) {
 template <bool CONV>
 int dispatch(const GemmArgs& a, int in_dtype, int out_dtype, hipStream_t s) {
     if (!CONV && a.kchunk == 0 && !(kinet_gemm_flags & 4) && launch_rw(a, in_dtype, out_dtype, s)) {
+        record_kernel(FAM_RW, 0, 0);
         KINET_LAUNCH_CHECK();
         return KINET_OK;
     }
     if (CONV && !(kinet_gemm_flags & 1024) && out_dtype == in_dtype && launch_conv3x3_c64(a, in_dtype, s)) {
+        record_kernel(FAM_CONV3X3, 0, 0);
         KINET_LAUNCH_CHECK();
         return KINET_OK;
     }
     if (CONV && !(kinet_gemm_flags & 32) && out_dtype == in_dtype && launch_stem_conv(a, in_dtype, s)) {
+        record_kernel(FAM_STEM, 0, 0);
         KINET_LAUNCH_CHECK();
         return KINET_OK;
     }
     if (CONV && a.kchunk == 0 && !(kinet_gemm_flags & 4) && out_dtype == in_dtype && launch_rw_conv(a, in_dtype, s)) {
+        record_kernel(FAM_RW_CONV, 0, 0);
         KINET_LAUNCH_CHECK();
         return KINET_OK;
     }
@@ -753,11 +783,28 @@ int run_splitk(const GemmArgs& user, int in_dtype, int out_dtype, float* ws, int
     else if (out_dtype == KINET_F16) { F_(f16_t); }
     else { F_(float); }
 #undef F_
+    last_family = FAM_SPLITK;   // (bm, bn stay those of the partial-tile grid)
     KINET_LAUNCH_CHECK();
     return KINET_OK;
 }
 
 bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+// C / R alignment contract of the fused epilogue (epilogue_rows, ResRows): whenever the row
+// strides allow it the epilogue moves 4 output elements per lane in one access -- the stores and
+// the in-loop residual loads when ldc % 4 == 0 (and ldr % 4 == 0 with a residual), the residual
+// rows loaded ahead when ldr % 4 == 0 and N % 4 == 0 -- and those accesses are only defined for
+// pointers aligned to 4 output elements (16 bytes f32, 8 bytes bf16 / f16).  A pointer that is not
+// is refused here, before any kernel starts; other strides take the element-wise path, which
+// needs element alignment only.  (The split-K finalize pass is element-wise throughout.)
+bool epilogue_aligned(const void* C, const void* R, int N, int ldc, int ldr, int out_dtype) {
+    const uintptr_t mask = 4 * (uintptr_t)dtype_size(out_dtype) - 1;
+    const bool vec_c = (ldc & 3) == 0 && (R == nullptr || (ldr & 3) == 0);
+    const bool vec_r = R != nullptr && (ldr & 3) == 0 && ((N & 3) == 0 || (ldc & 3) == 0);
+    if (vec_c && ((uintptr_t)C & mask)) return false;
+    if (vec_r && ((uintptr_t)R & mask)) return false;
+    return true;
+}
 
 }  // namespace
 }  // namespace kinet
@@ -781,6 +828,8 @@ extern "C" int kinet_gemm_ex(const void* A, const void* A2, const void* B, void*
     KINET_CHECK_ARG(lda >= K && ldb >= K && ldc >= N, "gemm: leading dims too small");
     KINET_CHECK_ARG(aligned16(A) && aligned16(B) && (A2 == nullptr || aligned16(A2)), "gemm: A, A2 and B must be 16-byte aligned");
     KINET_CHECK_ARG(R == nullptr || ldr >= N, "gemm: ldr < N");
+    KINET_CHECK_ARG(epilogue_aligned(C, R, N, ldc, ldr, out_dtype),
+                    "gemm: C and R must be aligned to 4 output elements when ldc / ldr are multiples of 4");
     KINET_CHECK_ARG((ln_gamma == nullptr) == (ln_beta == nullptr), "gemm: LayerNorm needs both gamma and beta");
     KINET_CHECK_ARG(ln_gamma == nullptr || relu == 0, "gemm: LayerNorm and ReLU are exclusive");
     GemmArgs a{};
@@ -822,6 +871,7 @@ extern "C" int kinet_gemm_headmajor_ex(const void* A, const void* A2, const void
     KINET_CHECK_ARG(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= K && ldb >= K, "gemm_headmajor: bad K/lda/ldb");
     KINET_CHECK_ARG(aligned16(A) && aligned16(B) && (A2 == nullptr || aligned16(A2)),
                     "gemm_headmajor: A, A2 and B must be 16-byte aligned");
+    KINET_CHECK_ARG(epilogue_aligned(C, nullptr, N, N, 0, out_dtype), "gemm_headmajor: C must be aligned to 4 output elements");
     GemmArgs a{};
     a.A = A; a.A2 = A2; a.B = B; a.C = C; a.bias = bias; a.row_mask = row_mask; a.a2_rows = a2_rows;
     a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = N;
@@ -849,6 +899,8 @@ extern "C" int kinet_gemm_headmajor_split(const void* A, const void* B, void* C,
                     "gemm_headmajor_split: N = heads*head_dim + heads*tail_dim, dims multiples of 4");
     KINET_CHECK_ARG(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= K && ldb >= K, "gemm_headmajor_split: bad K/lda/ldb");
     KINET_CHECK_ARG(aligned16(A) && aligned16(B), "gemm_headmajor_split: A and B must be 16-byte aligned");
+    KINET_CHECK_ARG(epilogue_aligned(C, nullptr, N, N, 0, out_dtype),
+                    "gemm_headmajor_split: C must be aligned to 4 output elements");
     GemmArgs a{};
     a.A = A; a.B = B; a.C = C; a.bias = bias; a.row_mask = row_mask;
     a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = N;
@@ -897,6 +949,8 @@ extern "C" int kinet_gemm_force_tile(int bm, int bn) {
     force_bn = bn;
     return KINET_OK;
 }
+
+extern "C" int kinet_gemm_last_kernel(void) { return (last_family << 20) | (last_bm << 10) | last_bn; }
 
 extern "C" int kinet_set_solo_launch(int on) {
     const int old = kinet_solo_launch;
@@ -959,6 +1013,8 @@ extern "C" int kinet_conv2d_ex(const void* X, const void* Wt, void* Y, int batch
     int rc = conv_args(a, X, Wt, Y, batch, Hin, Win, Cin, Hout, Wout, Cout, KH, KW, stride_h, pad_h, stride_w, pad_w,
                        in_dtype, scale, bias, R, ldr, relu, ldy);
     if (rc) return rc;
+    KINET_CHECK_ARG(epilogue_aligned(Y, R, Cout, ldy, ldr, in_dtype),
+                    "conv2d: Y and R must be aligned to 4 elements when ldy / ldr are multiples of 4");
     // a 1x1 stride-1 convolution over NHWC rows is the plain GEMM Y = X W^T (lda = Cin)
     if (a.lda) return dispatch<false>(a, in_dtype, in_dtype, (hipStream_t)stream);
     return dispatch<true>(a, in_dtype, in_dtype, (hipStream_t)stream);

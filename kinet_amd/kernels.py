@@ -124,6 +124,25 @@ def ksplit_for(M, N, K, ln=False):
     return ks if ks >= 2 else 1
 
 
+GEMM_FAMILIES = ('none', 'tiled', 'tiled-dma', 'dma8', 'rw', 'rw_conv', 'conv3x3', 'stem', 'splitk')
+
+
+def gemm_last_kernel():
+    """(family, bm, bn) of the kernel that served this thread's last GEMM / convolution call
+    (include/kinet_gemm.h kinet_gemm_last_kernel); bm = bn = 0 for the special-cased kernels."""
+    v = N.lib().kinet_gemm_last_kernel()
+    return GEMM_FAMILIES[v >> 20], (v >> 10) & 1023, v & 1023
+
+
+def _epilogue_operand(r, ld):
+    """A residual the fused epilogue can read 4 elements at a time (include/kinet_gemm.h "C / R
+    alignment"): a view that starts off a 4-element boundary with a row stride that is a multiple
+    of 4 is copied (a misaligned out= view cannot be fixed up here: the launcher refuses it)."""
+    if ld % 4 == 0 and r.data_ptr() % (4 * r.element_size()):
+        return r.contiguous() if not r.is_contiguous() else r.clone()
+    return r
+
+
 KINET_F32_X3 = 4   # include/kinet_common.h
 
 
@@ -186,6 +205,7 @@ def linear(x, weight, bias=None, relu=False, residual=None, row_mask=None, out_d
             r = r.contiguous()
         if r.dtype != odt:
             r = r.to(odt)
+        r = _epilogue_operand(r, r.stride(0))
         ldr = r.stride(0)
     mask = None
     if row_mask is not None:
@@ -447,7 +467,7 @@ def conv2d_nhwc(x, w_packed, stride, pad, scale=None, bias=None, relu=False, res
     ldy = out.stride(2) if out.dim() == 4 else out.stride(-2)
     r = None
     if residual is not None:
-        r = residual
+        r = _epilogue_operand(residual, Cout)
     e = x.element_size()
     work = {'family': 'conv', 'flops': 2.0 * B * Ho * Wo * Cout * KH * KW * Cin,
             'shape': (B, H, W, Cin, Cout, KH, sh),

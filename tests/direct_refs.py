@@ -1,6 +1,7 @@
 """High-precision restatements of the small kernels' operations, shared by
 test_ops_direct_gpu.py / test_grad_prims_gpu.py / test_grad_norm_attn_gpu.py /
-test_train_ops_direct_gpu.py and checked on the CPU by test_direct_refs_cpu.py.
+test_train_ops_direct_gpu.py / test_gemm_tiles_direct_gpu.py and checked on the CPU by
+test_direct_refs_cpu.py.
 Plain torch on the CPU; nothing here touches the GPU or the native library."""
 import functools
 import math
@@ -769,3 +770,173 @@ def inv_sigmoid_fwd_bwd_ref(x, dy, eps=1e-5):
     d = torch.where(xc >= e, dq / x2, torch.zeros_like(dq)) + torch.where(1 - xc >= e, dq * x1 / (x2 * x2), torch.zeros_like(dq))
     dx = torch.where((xv >= 0) & (xv <= 1), d, torch.zeros_like(d))
     return y, dx
+
+
+# ======================================= tiled GEMM / implicit convolution (csrc/gemm.hip)
+# Two operand classes.  EXACT: small dyadic values whose every f32 partial sum is exact in any
+# order, so the expected output is the f64 result rounded ONCE to the output type and the kernel
+# must match it bit for bit -- a dropped, doubled or misplaced K chunk, tap, row or column is a
+# hard failure.  GENERIC: randn operands under a per-element running-error bound.
+#
+# Exact class: x in {-1, -1/2, 0, 1/2, 1}, W in {0, +-1/8, +-1/4}: products are multiples of 1/16
+# of magnitude <= 1/4, a sum of K <= 2048 of them is a multiple of 1/16 below 2^9 (13 bits);
+# scale in {1/2, 1, 2}, bias multiples of 1/4 in [-1, 1], residual multiples of 1/4 in [-2, 2]:
+# acc * scale + bias + res is a multiple of 1/32 below 2^11 (16 bits) -- all exact in f32.
+# W is drawn sparse (more zeros the longer K is) so that the sums stay small: a 16-bit output must
+# still resolve ONE dropped product (exact_headroom).
+_EXACT_ACC_STD = 1.25     # target standard deviation of the accumulators
+
+
+def x3_bound(a64, b64):
+    """KINET_F32_X3 (three bf16 MFMA passes): per-product error <= ~2^-16 |a||b| (hi/lo split of both
+    operands, lo*lo dropped), plus f32 accumulation: 4e-5 * (|A| @ |B|) elementwise."""
+    return 4e-5 * (a64.abs() @ b64.abs()) + 1e-6
+
+
+def exact_x(shape, g):
+    """Multiples of 1/2 in [-1, 1], uniform over the five values (f32)."""
+    return torch.randint(-2, 3, shape, generator=g).float() / 2
+
+
+def exact_w(shape, K, g):
+    """Multiples of 1/8 in [-1/4, 1/4] (f32): +-1/8 with probability q each, +-1/4 with q/4 each;
+    var(w) = q/16, var(x) = 1/2, so the accumulator's variance is K q / 32 = _EXACT_ACC_STD^2."""
+    q = min(0.2, 32 * _EXACT_ACC_STD ** 2 / K)
+    u = torch.rand(shape, generator=g)
+    w = torch.zeros(shape)
+    for lo, hi, v in ((0, q, 1), (q, 2 * q, -1), (2 * q, 2.25 * q, 2), (2.25 * q, 2.5 * q, -2)):
+        w[(u >= lo) & (u < hi)] = v
+    return w / 8
+
+
+def exact_epilogue(N, g):
+    """(scale, bias) f32 of length N: scale in {1/2, 1, 2}, bias multiples of 1/4 in [-1, 1]."""
+    scale = torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (N,), generator=g)]
+    bias = torch.randint(-4, 5, (N,), generator=g).float() / 4
+    return scale, bias
+
+
+def exact_res(shape, g):
+    """Multiples of 1/4 in [-2, 2] (f32; exact in bf16 and f16 too)."""
+    return torch.randint(-8, 9, shape, generator=g).float() / 4
+
+
+def generic_operands(xshape, wshape, K, dtype, g):
+    """randn rounded to the compute type; W scaled by K^-1/2 (f32 tensors holding `dtype` values)."""
+    x = torch.randn(xshape, generator=g).to(dtype).float()
+    w = (torch.randn(wshape, generator=g) / K ** 0.5).to(dtype).float()
+    return x, w
+
+
+def generic_epilogue(N, g):
+    return 0.5 + torch.rand(N, generator=g), torch.randn(N, generator=g)
+
+
+def epilogue64(acc64, scale=None, bias=None, res=None, relu=False, row_mask=None):
+    """The kernels' epilogue in f64 on (M, N): relu?(acc * scale + bias + res), masked rows -> 0.
+    Returns (value, |acc * scale| + |bias| + |res|) -- the second is the bound's majorant."""
+    v = acc64 if scale is None else acc64 * scale.double()
+    a = v.abs()
+    if bias is not None:
+        v, a = v + bias.double(), a + bias.double().abs()
+    if res is not None:
+        v, a = v + res.double(), a + res.double().abs()
+    if relu:
+        v = v.clamp(min=0)
+    if row_mask is not None:
+        v = torch.where(row_mask.reshape(-1, 1), torch.zeros_like(v), v)
+    return v, a
+
+
+def gemm_generic_bound(absprod, K, majorant, ref, out_dtype, scale=None, x3=False):
+    """Per-element bound of the tiled kernel's output on generic operands:
+      accumulation, any order of K exact products in f32 (gamma_K, +64 for split-K slices):
+        1.01 (K + 64) u (|A| @ |B|^T)   [tn_exact_bound for the NT product], or x3_bound for
+        KINET_F32_X3 (absprod then is its own bound), carried through |scale|;
+      the epilogue's three f32 operations: 4 u (|acc scale| + |bias| + |res|);
+      the output rounding: OUT_ROUND[dtype] |ref|."""
+    acc = absprod if x3 else 1.01 * (K + 64) * U32 * absprod
+    if scale is not None:
+        acc = acc * scale.double().abs()
+    return acc + 4 * U32 * majorant + OUT_ROUND[out_dtype] * ref.abs() + 1e-30
+
+
+_MANT = {torch.float32: 23, torch.bfloat16: 7, torch.float16: 10}
+
+
+def exact_headroom(pre64, scale, out_dtype):
+    """True where one dropped product (1/16 in the accumulator, scale/16 in the output) moves the
+    exact-class result by at least one ulp of the output type at that magnitude -- so it cannot
+    hide inside the single output rounding.  pre64: the epilogue value before rounding."""
+    mag = pre64.abs().clamp(min=2.0 ** -20)
+    ulp = torch.exp2(torch.floor(torch.log2(mag)) - _MANT[out_dtype])
+    step = (torch.ones(pre64.shape[-1], dtype=torch.float64) if scale is None else scale.double().abs()) / 16
+    return ulp <= step
+
+
+def conv64(x_nhwc, w_ohwi, stride, pad):
+    """F.conv2d in f64 of NHWC x and (Cout, KH, KW, Cin) weights -> (B*Ho*Wo, Cout)."""
+    y = F.conv2d(x_nhwc.double().permute(0, 3, 1, 2), w_ohwi.double().permute(0, 3, 1, 2), stride=_pair(stride),
+                 padding=_pair(pad))
+    return y.permute(0, 2, 3, 1).reshape(-1, w_ohwi.shape[0])
+
+
+# The case tables (shared by the GPU module and the CPU checks of the references).
+GEMM_TILES = [(32, 64), (64, 64), (64, 128), (128, 64), (128, 128)]
+GEMM_K16 = (8, 56, 64, 72, 136, 200)      # 1, 1, 1, 2, 3, 4 K-steps of 64: tails, odd / even counts
+GEMM_K32 = (8, 24, 32, 40, 72, 104)       # the same counts of 32-element steps (f32 / x3)
+
+
+def gemm_shapes(bm, bn):
+    """(M, N) around one tile's edges; the last four: scalar store / load paths, a 15-block grid."""
+    return [(1, 4), (bm - 1, bn + 4), (bm, bn), (bm + 1, bn - 4), (2 * bm + 3, 2 * bn + 8), (bm + 1, bn + 1), (5, 3),
+            (bm, 2 * bn - 2), (3 * bm - 1, 5 * bn - 4)]
+
+
+def gemm_table(bm, bn, four_byte):
+    """(M, N, K): every shape with two K of the cycle, so each K meets three shapes."""
+    ks = GEMM_K32 if four_byte else GEMM_K16
+    return [(M, N, ks[(i + j) % 6]) for i, (M, N) in enumerate(gemm_shapes(bm, bn)) for j in (0, 3)]
+
+
+@functools.lru_cache(maxsize=None)
+def gemm_case(M, N, K, dtype, cls, seed=0):
+    """(x (M, K), w (N, K), acc64 (M, N), |x| @ |w|^T) of the exact or the generic class; x, w are f32
+    tensors holding values of `dtype`."""
+    g = torch.Generator().manual_seed(seed * 1000003 + M * 7919 + N * 131 + K + (0 if cls == 'exact' else 5))
+    if cls == 'exact':
+        x, w = exact_x((M, K), g), exact_w((N, K), K, g)
+    else:
+        x, w = generic_operands((M, K), (N, K), K, dtype, g)
+    xd, wd = x.double(), w.double()
+    return x, w, xd @ wd.T, xd.abs() @ wd.abs().T
+
+
+# name: (KH, KW), (sh, sw), (ph, pw), batch, H, W, Cin, Cout
+CONV_CASES = {
+    'C1': ((3, 3), (1, 1), (1, 1), 2, 5, 7, 64, 72),       # a tile spanning two images
+    'C2': ((3, 3), (2, 2), (1, 1), 1, 9, 6, 128, 64),      # the permuted K-step order (two chunks per tap)
+    'C3': ((7, 7), (2, 2), (3, 3), 2, 11, 13, 8, 64),      # non-uniform taps, K = 392 with a tail
+    'C4': ((1, 1), (2, 2), (0, 0), 2, 7, 9, 64, 132),      # strided 1x1
+    'C5a': ((3, 1), (2, 1), (1, 0), 1, 9, 10, 24, 40),
+    'C5b': ((1, 3), (1, 2), (0, 1), 1, 9, 10, 24, 40),
+    'C5c': ((7, 1), (2, 1), (3, 0), 1, 9, 10, 24, 40),
+    'C6a': ((3, 3), (1, 1), (1, 1), 2, 1, 2, 16, 24),      # image smaller than the filter
+    'C6b': ((3, 3), (1, 1), (1, 1), 2, 2, 1, 16, 24),
+    'C7': ((3, 3), (1, 1), (2, 2), 1, 4, 5, 16, 24),       # pad wider than the centre tap's reach
+    'C7b': ((3, 3), (1, 1), (3, 3), 1, 4, 5, 16, 24),      # ... border windows that are ALL padding
+    'C8': ((1, 1), (1, 1), (0, 0), 2, 5, 7, 64, 72),       # the plain-GEMM route (lda = Cin)
+}
+
+
+@functools.lru_cache(maxsize=None)
+def conv_case(name, dtype, cls):
+    """(x NHWC, w (Cout, KH, KW, Cin), acc64 (M, Cout), |x| * |w|) of the exact or generic class."""
+    (KH, KW), stride, pad, B, H, W, Cin, Cout = CONV_CASES[name]
+    K = KH * KW * Cin
+    g = torch.Generator().manual_seed(sum(map(ord, name)) * 97 + (0 if cls == 'exact' else 5))
+    if cls == 'exact':
+        x, w = exact_x((B, H, W, Cin), g), exact_w((Cout, KH, KW, Cin), K, g)
+    else:
+        x, w = generic_operands((B, H, W, Cin), (Cout, KH, KW, Cin), K, dtype, g)
+    return x, w, conv64(x, w, stride, pad), conv64(x.abs(), w.abs(), stride, pad)

@@ -562,3 +562,144 @@ def test_ln_epilogue_bounds_discriminate_one_pass_from_two_pass(d):
     assert (e1 > tol16).any()
     assert ((one.half().double() - y).abs() > tol16).any()
     assert ((two.half().double() - y).abs() <= tol16).all()
+
+
+# ======================================= tiled GEMM / implicit convolution (csrc/gemm.hip)
+def _f32_chunked(x, w, step, reverse):
+    """x @ w.T in f32, K taken in chunks of `step` accumulated sequentially, forwards or backwards."""
+    K = x.shape[1]
+    acc = torch.zeros(x.shape[0], w.shape[0])
+    starts = list(range(0, K, step))
+    for k0 in (reversed(starts) if reverse else starts):
+        acc = acc + x[:, k0:k0 + step] @ w[:, k0:k0 + step].T
+        assert acc.dtype == torch.float32
+    return acc
+
+
+@pytest.mark.parametrize('M,N,K', [(33, 68, 72), (131, 124, 200), (95, 316, 104), (8, 1100, 1024), (5, 91, 2048)])
+def test_gemm_exact_class_is_exact_in_f32(M, N, K):
+    """The exact class: the operands lie on the grids the GPU module's docstring states, f32 sums of
+    the products in two different orders both equal the f64 result, so does the f32 epilogue, and a
+    16-bit output resolves one dropped product at every element."""
+    x, w, acc, _ = R.gemm_case(M, N, K, torch.float32, 'exact')
+    assert ((x * 2) == (x * 2).round()).all() and x.abs().max() <= 1
+    assert ((w * 8) == (w * 8).round()).all() and w.abs().max() <= 0.25
+    for dt in (torch.bfloat16, torch.float16):                 # representable in every compute type
+        assert (x.to(dt).float() == x).all() and (w.to(dt).float() == w).all()
+    # no (output column, 8-element K chunk) class is all zeros everywhere: a dropped chunk shows
+    assert (w.view(N, K // 8, 8).abs().sum(-1) > 0).float().mean() > 0.3
+    assert acc.abs().max() < 2 ** 9
+    fwd, bwd = _f32_chunked(x, w, 8, False), _f32_chunked(x, w, 24, True)
+    assert (fwd.double() == acc).all() and (bwd.double() == acc).all() and ((x @ w.T).double() == acc).all()
+    g = torch.Generator().manual_seed(N)
+    scale, bias = R.exact_epilogue(N, g)
+    res = R.exact_res((M, N), g)
+    assert set(scale.tolist()) <= {0.5, 1.0, 2.0} and ((bias * 4) == (bias * 4).round()).all()
+    assert ((res * 4) == (res * 4).round()).all() and res.abs().max() <= 2
+    assert (res.bfloat16().float() == res).all() and (res.half().float() == res).all()
+    pre, _ = R.epilogue64(acc, scale, bias, res)
+    assert ((fwd * scale + bias + res).double() == pre).all()          # the epilogue's three f32 operations
+    for dt in (torch.float32, torch.bfloat16, torch.float16):
+        assert R.exact_headroom(pre, scale, dt).all()
+        assert R.exact_headroom(acc, None, dt).all()
+        # ... and the criterion means what it says: one product less changes the rounded output
+        less, _ = R.epilogue64(acc - 1.0 / 16, scale, bias, res)
+        assert (less.to(dt) != pre.to(dt)).all()
+    # the criterion does reject a magnitude where bf16 would swallow the product
+    assert not R.exact_headroom(torch.tensor([[40.0]], dtype=torch.float64), None, torch.bfloat16).all()
+
+
+def test_conv_exact_class_is_exact_in_f32():
+    for name in R.CONV_CASES:
+        (KH, KW), stride, pad, B, H, W, Cin, Cout = R.CONV_CASES[name]
+        x, w, acc, _ = R.conv_case(name, torch.float32, 'exact')
+        cols = R.unfold_nhwc(x, KH, KW, stride, pad)
+        wk = w.reshape(Cout, -1)
+        assert ((cols @ wk.T).double() == acc).all()           # f32 im2col product == F.conv2d in f64
+        assert (_f32_chunked(cols, wk, 8, True).double() == acc).all()
+        assert R.exact_headroom(acc, None, torch.bfloat16).all()
+    # C7b: the outermost ring of output windows lies wholly in the padding
+    acc = R.conv_case('C7b', torch.float32, 'exact')[2].view(8, 9, -1)
+    assert (acc[0] == 0).all() and (acc[-1] == 0).all() and (acc[:, 0] == 0).all() and (acc[:, -1] == 0).all()
+    assert (R.conv_case('C7', torch.float32, 'exact')[2].view(6, 7, -1)[0, 0] != 0).any()
+
+
+def test_x_add_exact_operand_needs_rounding():
+    """The x_add case of the GPU module: the bf16 sum needs rounding (a truncating add differs), the
+    rounded operand times exact-class W is still exact in f32."""
+    g = torch.Generator().manual_seed(3)
+    x = R.exact_x((33, 72), g)
+    x2 = torch.randint(-7, 8, (33, 72), generator=g).float() / 512
+    w = R.exact_w((68, 72), 72, g)
+    assert (x2.bfloat16().float() == x2).all()
+    s = x + x2
+    rne = s.bfloat16().float()
+    trunc = (s.view(torch.int32) & -65536).view(torch.float32)
+    assert (rne != s).any() and (rne != trunc).any()
+    a = rne.double()
+    acc = a @ w.double().T
+    assert ((rne @ w.T).double() == acc).all() and (_f32_chunked(rne, w, 8, True).double() == acc).all()
+    assert ((trunc @ w.T).double() != acc).any()
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16], ids=str)
+@pytest.mark.parametrize('M,N,K', [(67, 136, 200), (131, 124, 72), (95, 316, 104)])
+def test_gemm_generic_bound_holds_for_torch_f32_and_rejects_defects(M, N, K, dtype):
+    """torch's own f32 matmul + f32 epilogue + one output rounding stays inside the generic bound;
+    the last 8-element K chunk dropped, and (f32 path) operands truncated to bf16, leave it."""
+    x, w, acc, ap = R.gemm_case(M, N, K, dtype, 'generic')
+    assert (x.to(dtype).float() == x).all() and (w.to(dtype).float() == w).all()
+    g = torch.Generator().manual_seed(K)
+    scale, bias = R.generic_epilogue(N, g)
+    res = torch.randn(M, N, generator=g).to(dtype).float()
+    pre, maj = R.epilogue64(acc, scale, bias, res, relu=True)
+    bound = R.gemm_generic_bound(ap, K, maj, pre, dtype, scale)
+
+    def f32_path(xx, ww):
+        return torch.relu((xx @ ww.T) * scale + bias + res).to(dtype).double()
+    err = (f32_path(x, w) - pre).abs()
+    print(f'generic bound ({M}, {N}, {K}) {dtype}: torch f32 worst err / bound {(err / bound).max().item():.3f}')
+    assert (err <= bound).all()
+    dropped = (f32_path(x[:, :K - 8], w[:, :K - 8]) - pre).abs()
+    assert (dropped > bound).float().mean() > 0.25
+    if dtype == torch.float32:
+        trunc = (f32_path(x.bfloat16().float(), w.bfloat16().float()) - pre).abs()
+        assert (trunc > bound).float().mean() > 0.25
+        # KINET_F32_X3's own bound is wider than the exact path's, and torch f32 is inside it too
+        xb = R.gemm_generic_bound(R.x3_bound(x.double(), w.double().T), K, maj, pre, dtype, scale, x3=True)
+        assert (bound <= xb).all() and (err <= xb).all() and (trunc > xb).any()
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=str)
+@pytest.mark.parametrize('name', ['C1', 'C3'])
+def test_conv_generic_bound_rejects_a_shifted_tap(name, dtype):
+    """One filter tap reading its input one pixel to the right leaves the generic bound; torch's f32
+    convolution stays inside it."""
+    (KH, KW), stride, pad, B, H, W, Cin, Cout = R.CONV_CASES[name]
+    x, w, acc, ap = R.conv_case(name, dtype, 'generic')
+    K = KH * KW * Cin
+    pre, maj = R.epilogue64(acc)
+    bound = R.gemm_generic_bound(ap, K, maj, pre, dtype)
+    xn, wn = x.permute(0, 3, 1, 2), w.permute(0, 3, 1, 2)
+    good = F.conv2d(xn, wn, stride=stride, padding=pad).permute(0, 2, 3, 1).reshape(-1, Cout)
+    assert ((good.to(dtype).double() - pre).abs() <= bound).all()
+    tap = torch.zeros_like(wn)
+    tap[:, :, KH // 2, KW // 2] = wn[:, :, KH // 2, KW // 2]
+    bad = F.conv2d(xn, wn - tap, stride=stride, padding=pad) + F.conv2d(torch.roll(xn, -1, 3), tap, stride=stride, padding=pad)
+    bad = bad.permute(0, 2, 3, 1).reshape(-1, Cout)
+    assert ((bad.to(dtype).double() - pre).abs() > bound).float().mean() > 0.25
+
+
+def test_gemm_table_covers_the_k_cycle():
+    for bm, bn in R.GEMM_TILES:
+        for four in (False, True):
+            t = R.gemm_table(bm, bn, four)
+            ks = R.GEMM_K32 if four else R.GEMM_K16
+            step = 32 if four else 64
+            assert sorted(-(-k // step) for k in ks) == [1, 1, 1, 2, 3, 4]
+            for k in ks:
+                assert len({(M, N) for M, N, kk in t if kk == k}) >= 2
+            assert {(M, N) for M, N, _ in t} == set(R.gemm_shapes(bm, bn)) and len(R.gemm_shapes(bm, bn)) == 9
+            assert all(k % 8 == 0 and k <= 392 for k in ks)
+    # the 15-block grid of the XCD remap (15 = 8 + 7: both branches of the bijection)
+    assert all(-(-(3 * bm - 1) // bm) * -(-(5 * bn - 4) // bn) == 15 for bm, bn in R.GEMM_TILES)

@@ -807,10 +807,7 @@ def x3_precision():
     torch.set_float32_matmul_precision(prev)
 
 
-def _x3_bound(a64, b64):
-    # per-product error <= ~2^-16 |a||b| (hi/lo split of both operands, lo*lo dropped), plus
-    # f32 accumulation: bound by 4e-5 * (|A| @ |B|) elementwise
-    return 4e-5 * (a64.abs() @ b64.abs()) + 1e-6
+from direct_refs import x3_bound as _x3_bound   # noqa: E402  (shared with test_gemm_tiles_direct_gpu.py)
 
 
 @pytest.mark.parametrize('M,N,Kd', [(37, 91, 256), (1000, 1024, 256), (513, 256, 1024), (4200, 384, 2048),
