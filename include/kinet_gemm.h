@@ -142,11 +142,40 @@ int kinet_stem_pool_image(const float* img, const void* w_packed, const float* s
  * NOT reach the backward kernels launched through autograd (only forward / direct calls). */
 int kinet_gemm_set_flags(int flags);
 
-/* Diagnostic tile override of the tiled kernel (0, 0 = heuristic), per calling thread: 32x64,
- * {64,128}x{64,128}, and the 8-wave 256x128 / 128x256 / 256x256 LDS-DMA tiles, which exist for
- * 16-bit operands without A2 only -- a launch that has no instantiation of the forced tile
- * returns KINET_ERR_ARG before any kernel starts.  Ignored by the fused-LayerNorm launches. */
+/* How a tiled launch is chosen.  One host-side planner (csrc/gemm_plan.h) holds every tile
+ * heuristic: from the sizes, the operand class, the calling thread's flags and forced tile, the
+ * launch-fill policy and the device's compute-unit count it yields one or two launches, each an
+ * entry of the one table of kernel instantiations plus a row range.  The launcher reads kernel,
+ * workgroup size, grid and the kinet_gemm_last_kernel record from that entry alone; a tile the
+ * table has no entry for, for these operands, is KINET_ERR_ARG before any kernel starts. */
+
+/* Diagnostic tile override of the tiled kernel (0, 0 = heuristic), per calling thread: any tile of
+ * the planner's table without the LayerNorm epilogue -- 32x64, {64,128}x{64,128}, and the 8-wave
+ * 256x128 / 128x256 / 256x256 LDS-DMA tiles, which exist for 16-bit operands without A2 only: a
+ * launch that has no instantiation of the forced tile returns KINET_ERR_ARG before any kernel
+ * starts.  Ignored by the fused-LayerNorm launches. */
 int kinet_gemm_force_tile(int bm, int bn);
+
+/* The planner's answer for a described problem, without touching a device (no reference
+ * counterpart; works on a machine without a GPU): what kinet_gemm(_ex), kinet_gemm_headmajor* or
+ * kinet_conv2d(_ex) would launch once the call reaches the tiled kernel, i.e. when none of the
+ * special-cased kernels of kinet_gemm_last_kernel (families 4-7) takes it.  conv: an implicit
+ * convolution with K = KH*KW*Cin (a 1x1 stride-1 convolution is a plain GEMM: conv = 0); ln: fused
+ * LayerNorm; a2: an A2 operand; kchunk: the K-slice length of a split-K launch, else 0; hm_rows:
+ * rows_per_batch of a head-major store, else 0; in_dtype: a kinet_dtype; cus: the compute-unit
+ * count to plan for (256 on MI355X).  Reads the calling thread's kinet_gemm_set_flags /
+ * kinet_gemm_force_tile and the launch-fill policy like a real call.  *n_launches = 0 (M or N is
+ * 0), 1 or 2; launches[3*i .. 3*i+2] = {kernel in the packing of kinet_gemm_last_kernel, first
+ * row, number of row tiles} of launch i (room for 6 ints).  The launches cover rows [0, M) once,
+ * in order.  KINET_ERR_ARG where the real call returns it for want of a tile. */
+int kinet_gemm_plan(int M, int N, int K, int Cin, int conv, int ln, int a2, int kchunk, int hm_rows,
+                    int in_dtype, int cus, int* n_launches, int* launches);
+
+/* Split-K factor the Python layer uses for a GEMM / convolution of these sizes (ln: fused
+ * LayerNorm): > 1 for K >= 1024 problems whose tile grid fills the compute units less than twice
+ * over, else 1.  It looks at the planner's base 4-wave tile of a plain GEMM only, not at the full
+ * plan. */
+int kinet_gemm_ksplit(int M, int N, int K, int ln);
 
 /* Which kernel served the calling thread's last GEMM / convolution call (host-side record, no
  * reference counterpart; tests assert through it that the kernel they mean to test ran):

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <type_traits>
 #include <stdint.h>
 #include <stdio.h>
@@ -98,8 +99,10 @@ __device__ __forceinline__ void mfma_window_pad() {
 }
 
 // launch-fill policy (kinet_set_solo_launch, defined in gemm.hip): 1 = one batch in flight, so
-// launches size their tiles to fill the chip on their own; 0 = throughput mode (default)
-extern int kinet_solo_launch;
+// launches size their tiles to fill the chip on their own; 0 = throughput mode (default).
+// Process-wide, set by one thread and read by every launching thread: relaxed atomic accesses
+extern std::atomic<int> kinet_solo_launch;
+inline bool solo_launch() { return kinet_solo_launch.load(std::memory_order_relaxed) != 0; }
 
 // compute units of the current device (read once; 256 on MI355X) -- launchers size their
 // grids in rounds of one workgroup per CU

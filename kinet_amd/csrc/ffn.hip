@@ -1323,7 +1323,7 @@ int launch_pair(const PairArgs& a, int D, int DB, hipStream_t s) {
             const long t2 = (a.M + 255) / 256, t1 = (a.M + 127) / 128;
             const double e2 = (double)t2 / (double)(((t2 + cus - 1) / cus) * cus);
             const double e1 = (double)t1 / (double)(((t1 + cus - 1) / cus) * cus);
-            const bool one = (ffn_debug & 128) || (!(ffn_debug & 256) && kinet_solo_launch && e1 > 1.5 * e2);
+            const bool one = (ffn_debug & 128) || (!(ffn_debug & 256) && solo_launch() && e1 > 1.5 * e2);
             if (D == 128) {
                 if (one) launch_pair_cfg<T, 128, 1, 8, 1>(a, s);
                 else launch_pair_cfg<T, 128, 2, 8, 1>(a, s);

@@ -27,10 +27,12 @@
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "../../include/kinet_gemm.h"
 #include "common.h"
 #include "gemm_common.h"
+#include "gemm_plan.h"
 
 namespace kinet {
 namespace {
@@ -46,13 +48,12 @@ namespace {
 // test / A-B selection knobs (kinet_gemm_set_flags, kinet_gemm_force_tile): per calling thread,
 // never read by default paths except as "0 = automatic"
 thread_local int kinet_gemm_flags = 0;   // declared in gemm_common.h (read by grad.hip too)
-int kinet_solo_launch = 0;                 // declared in common.h (kinet_set_solo_launch)
+std::atomic<int> kinet_solo_launch{0};     // declared in common.h (kinet_set_solo_launch)
 namespace {
 // diagnostic tile override for gemm_kernel (kinet_gemm_force_tile; 0 = heuristic)
 thread_local int force_bm = 0, force_bn = 0;
 // the kernel family and tile of the calling thread's last launch (kinet_gemm_last_kernel): host
-// side only, written by dispatch<> / run_splitk / launch()'s run, read by tests and tools
-enum { FAM_NONE = 0, FAM_TILED, FAM_TILED_DMA, FAM_DMA8, FAM_RW, FAM_RW_CONV, FAM_CONV3X3, FAM_STEM, FAM_SPLITK };
+// side only, written by dispatch<> / run_splitk / launch(), read by tests and tools
 thread_local int last_family = FAM_NONE, last_bm = 0, last_bn = 0;
 inline void record_kernel(int family, int bm, int bn) {
     last_family = family;
@@ -472,188 +473,49 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs p, const in
 }
 
 #include "gemm_dma.h"   // gemm_dma_kernel: the same tiles staged by LDS-DMA through a 3-slot ring
+
+template <typename T> constexpr int op_class = sizeof(T) == 2 ? OPS_16 : std::is_same<T, f32x3_t>::value ? OPS_X3 : OPS_F32;
+
+// Launch entry I of kGemmTiles (gemm_plan.h) if `tile` names it.  These are the only launches of
+// gemm_kernel / gemm_dma_kernel, so the table is the list of their instantiations.
+template <typename T, typename TO, bool CONV, int I>
+void launch_entry(int tile, dim3 grid, hipStream_t stream, const GemmArgs& g, int nNt) {
+    constexpr GemmTile t = kGemmTiles[I];
+    if constexpr ((t.ops & op_class<T>) != 0) {
+        if (tile != I) return;
+        if constexpr (t.stages == 0)
+            hipLaunchKernelGGL((gemm_kernel<T, TO, t.bm, t.bn, t.wm, t.wn, CONV, t.ln>), grid, dim3(t.threads()), 0, stream, g, nNt);
+        else
+            hipLaunchKernelGGL((gemm_dma_kernel<T, TO, t.bm, t.bn, t.wm, t.wn, CONV, t.ln, t.stages>), grid,
+                               dim3(t.threads()), 0, stream, g, nNt);
+    }
+}
+template <typename T, typename TO, bool CONV, int... I>
+void launch_tile(int tile, dim3 grid, hipStream_t stream, const GemmArgs& g, int nNt, std::integer_sequence<int, I...>) {
+    (launch_entry<T, TO, CONV, I>(tile, grid, stream, g, nNt), ...);
+}
+
+// Plan the problem (gemm_plan.h: every tile heuristic lives there), then run each planned launch:
+// grid, block, kernel and the record all come from the launch's one table entry.
 template <typename T, typename TO, bool CONV>
 int launch(const GemmArgs& a, hipStream_t stream) {
-    if (a.M == 0 || a.N == 0) return KINET_OK;
-    const bool ln = a.ln_g != nullptr;
-    int bm, bn;
-    if (ln) {
-        KINET_CHECK_ARG(a.N <= 320, "gemm: fused LayerNorm needs N <= 320 (got %d)", a.N);
-        bm = a.M <= 8192 ? 32 : 64;     // small M (decoder queries): more workgroups
-        bn = a.N <= 256 ? 256 : 320;
-        // rows of 257..320 (d = 288, configs 3-5) at encoder sizes: 128 x 320 LDS-DMA tiles --
-        // the 64 x 320 register-staged tile re-reads the whole 320 x K weight through its
-        // staging registers for every 64 rows (~100 TF/s at M = 172k)
-        if (sizeof(T) == 2 && a.N > 256 && a.M >= 8192 && a.A2 == nullptr && a.kchunk == 0) bm = 128;
-    } else if (a.kchunk && a.M <= 4096) {
-        bm = bn = 64;                   // split-K slices of a small-M, long-K problem
-    } else if (a.M <= 4096 && a.N <= 1024) {
-        bm = 32;                        // decoder-sized GEMMs: more workgroups
-        bn = 64;
-    } else {
-        // 64x128 (128x64 for N <= 64): fastest main-loop tile on every 3x3 / K >= 512 conv and
-        // GEMM shape of the detector at batch 8 (tools/sweep_conv.py) -- more tiles per CU-round
-        // than 128x128 and no worse per flop
-        bn = a.N <= 64 ? 64 : 128;
-        bm = a.N <= 64 ? 128 : 64;
-        // big square-ish problems: the 128x128 tile's lower operand traffic per flop wins
-        const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-        if (a.N >= 512 && t128 >= 2048) bm = bn = 128;
-        // 3x3 convs (K >= 9*128) with >= ~2 rounds of 128x128 tiles over the 512 resident
-        // slots: 3-6 % faster than 64x128 at batch 16 (tools/sweep_conv.py 16), neutral at 8
-        if (CONV && a.K >= 1152 && a.N >= 128 && t128 >= 1000) bm = bn = 128;
-        // KINET_F32_X3 with N just past a multiple of 128 (d = 288 of the config-4 training
-        // GEMMs): 128 x 64 tiles waste 10 % of the columns instead of 25 % -- x3 (44446, 288,
-        // 1024) 157 -> 132 us, (44446, 288, 288) 60 -> 51 us (profiles/r05x_x3_tiles.log);
-        // flag 33554432 keeps the default (A/B)
-        if (std::is_same<T, f32x3_t>::value && a.N > 64 && a.N % 128 != 0 && a.N % 128 <= 64 &&
-            !(kinet_gemm_flags & 33554432)) {
-            bm = 128;
-            bn = 64;
-        }
-    }
-    // 8-wave LDS-DMA tiles (one workgroup per CU: 256 slots per round): chosen for long-K
-    // problems whose rounds of tiles are well filled (a square 4096^3 bf16 GEMM: 1115 TF/s
-    // on 256x256 vs 456 on the 4-wave 128x128 tile, tools/gemm_probe.py); on the detector's
-    // conv / GEMM shapes their last, partly filled round costs more than the faster main loop
-    // gains (DESIGN.md "GEMM / conv kernel"), so those keep the 4-wave tiles.  Flag 2 forces
-    // them wherever eligible.
-    int bm8 = 0, bn8 = 0;
-    // (not for head-major stores: only gemm_kernel's epilogue writes them)
-    if (sizeof(T) == 2 && a.A2 == nullptr && a.kchunk == 0 && a.hm_rows == 0 && a.M >= 4096 && a.N >= 128 &&
-        (!ln || a.N <= 256)) {
-        const int tn = (a.N > 128 || ln) ? 256 : 128;
-        const long t = (long)((a.M + 255) / 256) * ((a.N + tn - 1) / tn);
-        const double eff = (double)a.M * a.N / ((double)((t + 255) / 256) * 256.0 * 256.0 * tn);
-        if ((kinet_gemm_flags & 2) || (!ln && a.K >= 1024 && eff >= 0.9)) {
-            bm8 = 256;
-            bn8 = tn;
-        }
-    }
-    if (bm8) {
-        bm = bm8;
-        bn = bn8;
-    }
-    if (force_bm && !ln) {
-        // the 256-row / 256-column tiles exist as 8-wave LDS-DMA kernels only: 16-bit operands, no
-        // load-time A2 add (anything else fell through to the 64x64 kernel on a grid sized for
-        // the forced tile, which left most rows unwritten)
-        KINET_CHECK_ARG((force_bm != 256 && force_bn != 256) || (sizeof(T) == 2 && a.A2 == nullptr),
-                        "gemm: forced tile %dx%d needs 16-bit operands and no A2 (no such instantiation)", force_bm,
-                        force_bn);
-        bm = force_bm;
-        bn = force_bn;
-    }
-    // LDS-DMA staging (opt-in, flag 16): measured 0-10 % slower than the register-staged
-    // kernel on the detector's conv / GEMM shapes at batch 8 (tools/sweep_conv.py), so the
-    // register path stays the default; A2 (load-time add) needs the register path anyway
-    // (not for KINET_F32_X3: its operands are split into bf16 hi / lo on the way into LDS)
-    const bool dma = a.A2 == nullptr && (kinet_gemm_flags & 16) && !std::is_same<T, f32x3_t>::value;
+    const GemmProblem p{a.M, a.N, a.K, a.Cin, CONV, a.ln_g != nullptr, a.A2 != nullptr, a.kchunk, a.hm_rows, op_class<T>,
+                        kinet_gemm_flags, force_bm, force_bn, solo_launch(), cu_count()};
+    GemmPlan plan;
+    if (int rc = gemm_plan(p, plan)) return rc;
     const int nslice = a.kchunk ? (a.K + a.kchunk - 1) / a.kchunk : 1;
-    // one launch of the tile grid over rows [g.m_begin, g.m_begin + mtiles * BM)
-    auto run = [&](const GemmArgs& g, int tbm, int tbn, long mtiles) -> int {
-        const int nNt = (g.N + tbn - 1) / tbn;
-        const long nblk = mtiles * nNt;
-        KINET_CHECK_ARG(nblk < (1L << 31), "gemm: too many tiles");
-        dim3 grid((unsigned)nblk, (unsigned)nslice), block(256);
-        // 8-wave LDS-DMA tiles (16-bit operands, no load-time A2 add; LayerNorm on 256-wide rows)
-        if constexpr (sizeof(T) == 2) {
-            if (ln && tbm == 128 && tbn == 320) {
-                hipLaunchKernelGGL((gemm_dma_kernel<T, TO, 128, 320, 2, 2, CONV, true, 2>), grid, block, 0, stream, g, nNt);
-                record_kernel(FAM_TILED_DMA, tbm, tbn);
-                KINET_LAUNCH_CHECK();
-                return KINET_OK;
-            }
-            // (128x256 or 256 rows -- NOT the 32x256 / 64x256 LayerNorm tiles of the 4-wave kernel:
-            // they came here too, and ran the 256x256 kernel on a grid sized for 32- or 64-row tiles,
-            // 7 of 8 (3 of 4) workgroups multiplying zeros past the last row)
-            if (g.A2 == nullptr && (tbm == 256 || (tbm == 128 && tbn == 256))) {
-                const dim3 blk(512);
-                if (ln)
-                    hipLaunchKernelGGL((gemm_dma_kernel<T, TO, 256, 256, 2, 4, CONV, true, 2>), grid, blk, 0, stream, g, nNt);
-                else if (tbm == 256 && tbn == 256)
-                    hipLaunchKernelGGL((gemm_dma_kernel<T, TO, 256, 256, 2, 4, CONV, false, 2>), grid, blk, 0, stream, g, nNt);
-                else if (tbm == 256)
-                    hipLaunchKernelGGL((gemm_dma_kernel<T, TO, 256, 128, 4, 2, CONV, false>), grid, blk, 0, stream, g, nNt);
-                else
-                    hipLaunchKernelGGL((gemm_dma_kernel<T, TO, 128, 256, 2, 4, CONV, false>), grid, blk, 0, stream, g, nNt);
-                record_kernel(FAM_DMA8, ln ? 256 : tbm, ln ? 256 : tbn);
-                KINET_LAUNCH_CHECK();
-                return KINET_OK;
-            }
-        }
-#define L_(BM_, BN_, WM_, WN_, LN_)                                                                             \
-    do {                                                                                                        \
-        if constexpr (!std::is_same<T, f32x3_t>::value) {                                                     \
-            if (dma) { hipLaunchKernelGGL((gemm_dma_kernel<T, TO, BM_, BN_, WM_, WN_, CONV, LN_>), grid, block, 0, \
-                                          stream, g, nNt); break; }                                             \
-        }                                                                                                       \
-        hipLaunchKernelGGL((gemm_kernel<T, TO, BM_, BN_, WM_, WN_, CONV, LN_>), grid, block, 0, stream, g, \
-                                nNt);                                                                           \
-    } while (0)
-        if (ln) {
-            if (tbm == 32 && tbn == 256) L_(32, 256, 1, 4, true);
-            else if (tbm == 32) L_(32, 320, 1, 4, true);
-            else if (tbn == 256) L_(64, 256, 1, 4, true);
-            else L_(64, 320, 1, 4, true);
-        } else if (tbm == 32) L_(32, 64, 2, 2, false);
-        else if (tbm == 128 && tbn == 128) L_(128, 128, 2, 2, false);
-        else if (tbm == 128 && tbn == 64) L_(128, 64, 2, 2, false);
-        else if (tbm == 64 && tbn == 128) L_(64, 128, 2, 2, false);
-        else if (tbm == 64 && tbn == 64) L_(64, 64, 2, 2, false);
-        else {
-            set_error("gemm: no %dx%d tile for these operands", tbm, tbn);
-            return KINET_ERR_ARG;
-        }
-#undef L_
-        record_kernel(dma ? FAM_TILED_DMA : FAM_TILED, ln ? (tbm == 32 ? 32 : 64) : tbm,
-                      ln ? (tbn == 256 ? 256 : 320) : tbn);
+    for (int i = 0; i < plan.n; ++i) {
+        const GemmLaunch& l = plan.launch[i];
+        const GemmTile& t = kGemmTiles[l.tile];
+        const int nNt = (a.N + t.bn - 1) / t.bn;
+        GemmArgs g = a;
+        g.m_begin = l.m_begin;
+        launch_tile<T, TO, CONV>(l.tile, dim3((unsigned)l.m_tiles * nNt, (unsigned)nslice), stream, g, nNt,
+                                 std::make_integer_sequence<int, kNumGemmTiles>{});
+        record_kernel(t.family, t.bm, t.bn);
         KINET_LAUNCH_CHECK();
-        return KINET_OK;
-    };
-    // Multi-tap convolutions (3x3, 7x1): whole rounds of one-per-CU 8-wave 256-row tiles (the
-    // faster main loop: half the LDS reads per MFMA and half the L2 bytes per flop of the
-    // 4-wave tiles), then the rows left over -- less than a round -- on the 4-wave tiles in a
-    // second launch, instead of a partly filled last round of 8-wave tiles (flag 64: off)
-    if constexpr (sizeof(T) == 2) {
-        if (CONV && !ln && a.A2 == nullptr && a.kchunk == 0 && !force_bm && !bm8 && !(kinet_gemm_flags & 64) &&
-            a.K > a.Cin && a.N >= 256 && a.M >= 8192) {
-            // (256x256 tiles only: at N = 128 the 8-wave 256x128 tile measured no faster per
-            // round than the 4-wave 128x128 one, tools/gemm_probe.py)
-            const int tn = 256;
-            const int nN8 = (a.N + tn - 1) / tn;
-            const long mt_all = (a.M + 255) / 256;
-            long mfull = (mt_all * nN8 / 256) * 256 / nN8;   // m-tiles that fill whole rounds
-            if (mfull > mt_all) mfull = mt_all;
-            // less than one round but at least half of one: a single partial round of 8-wave
-            // tiles still beats the 4-wave grid (layer-4 3x3 at batch 16: 119 vs 128 us)
-            if (mfull == 0 && mt_all * nN8 >= 128) {
-                // ... unless one batch is in flight (kinet_set_solo_launch), it fills less than 60 %
-                // of the CUs and 128 x 256 tiles (twice as many, same 8-wave main loop, same sums)
-                // fill them better: config 5's stage-3 3x3 convs (M = 32,640, N = 256: 128 vs 255
-                // tiles) 74.8 -> 48.5 us alone (profiles/r06aa_config5_shapes.txt), but -1 % on 3
-                // streams, whose other batches fill the idle CUs (profiles/r06ab_solo_launch_ab.txt)
-                const long t128 = (long)((a.M + 127) / 128) * nN8;
-                if (kinet_solo_launch && mt_all * nN8 * 10 < 256L * 6 && t128 <= 256)
-                    return run(a, 128, 256, (a.M + 127) / 128);
-                mfull = mt_all;
-            }
-            // a remainder of more than a quarter round: the partly filled last round of 8-wave
-            // tiles beats the 4-wave tail (layer-3 3x3 at batch 24: 394 m-tiles = 256 + 138,
-            // 140 vs 151 us, profiles/r05f2_conv24.log); flag 8388608 keeps the split (A/B)
-            if (mfull >= 1 && (mt_all - mfull) * nN8 > 64 && !(kinet_gemm_flags & 8388608)) mfull = mt_all;
-            if (mfull >= 1) {
-                int rc = run(a, 256, tn, mfull);
-                if (rc) return rc;
-                const long rem = a.M - mfull * 256;
-                if (rem <= 0) return KINET_OK;
-                GemmArgs g = a;
-                g.m_begin = (int)(mfull * 256);
-                return run(g, 64, 128, (rem + 63) / 64);   // less than a round: the smaller tile
-            }
-        }
     }
-    return run(a, bm, bn, (a.M + bm - 1) / bm);
+    return KINET_OK;
 }
 
 template <bool CONV>
@@ -819,29 +681,54 @@ extern "C" int kinet_gemm_headmajor_ex(const void* A, const void* A2, const void
                                        const uint8_t* row_mask, int rows_per_batch, int head_dim, int a2_rows,
                                        kinet_stream_t stream);
 
+// The checks and the GemmArgs fill shared by the four GEMM entry points (conv_args is the
+// convolutions'), in each entry's own words: fn = its name in the messages; hm = a head-major entry
+// (N > 0 columns, C contiguous, terser messages); with_a2 = the entry takes an A2.  The checks of
+// one entry alone (head-major divisibility, a2_rows, C / R alignment, the split-K workspace) stay
+// with that entry.
+static int gemm_args(GemmArgs& a, const char* fn, bool hm, bool with_a2, const void* A, const void* A2, const void* B,
+                     void* C, int M, int N, int K, int lda, int ldb, int ldc, int in_dtype, const float* scale,
+                     const float* bias, const void* R, int ldr, int relu, const float* ln_gamma, const float* ln_beta,
+                     float ln_eps, const uint8_t* row_mask) {
+    const bool k8 = K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0;
+    if (hm) {
+        KINET_CHECK_ARG(M >= 0 && N > 0 && K > 0, "%s: invalid sizes", fn);
+        KINET_CHECK_ARG(k8 && lda >= K && ldb >= K, "%s: bad K/lda/ldb", fn);
+    } else {
+        KINET_CHECK_ARG(M >= 0 && N >= 0 && K > 0, "%s: invalid sizes M=%d N=%d K=%d", fn, M, N, K);
+        // (kinet_gemm_ex's message carries the values, kinet_gemm_splitk's does not)
+        KINET_CHECK_ARG(k8 || !with_a2, "%s: K, lda, ldb must be multiples of 8 (K=%d lda=%d ldb=%d)", fn, K, lda, ldb);
+        KINET_CHECK_ARG(k8, "%s: K, lda, ldb must be multiples of 8", fn);
+        KINET_CHECK_ARG(lda >= K && ldb >= K && ldc >= N, "%s: leading dims too small", fn);
+    }
+    KINET_CHECK_ARG(aligned16(A) && aligned16(B) && (A2 == nullptr || aligned16(A2)), "%s: A%s and B must be 16-byte aligned",
+                    fn, with_a2 ? ", A2" : "");
+    KINET_CHECK_ARG(R == nullptr || ldr >= N, "%s: ldr < N", fn);
+    KINET_CHECK_ARG((ln_gamma == nullptr) == (ln_beta == nullptr), "%s: LayerNorm needs both gamma and beta", fn);
+    KINET_CHECK_ARG(ln_gamma == nullptr || relu == 0, "%s: LayerNorm and ReLU are exclusive", fn);
+    a.A = A; a.A2 = A2; a.B = B; a.C = C; a.R = R; a.scale = scale; a.bias = bias; a.row_mask = row_mask;
+    a.ln_g = ln_gamma; a.ln_b = ln_beta; a.ln_eps = ln_eps;
+    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = hm ? N : ldc; a.ldr = ldr; a.relu = relu;
+    const long long es = (long long)dtype_size(in_dtype);
+    const long long ab = M > 0 ? ((long long)(M - 1) * lda + K) * es : 0;
+    const long long bb = N > 0 ? ((long long)(N - 1) * ldb + K) * es : 0;
+    KINET_CHECK_ARG(ab < (1LL << 31) && bb < (1LL << 31), "%s: operand larger than 2 GiB%s", fn,
+                    !hm && with_a2 ? " (split the call)" : "");
+    a.a_bytes = (int)ab;
+    a.b_bytes = (int)bb;
+    return KINET_OK;
+}
+
 extern "C" int kinet_gemm_ex(const void* A, const void* A2, const void* B, void* C, int M, int N, int K, int lda,
                              int ldb, int ldc, int in_dtype, const float* scale, const float* bias, const void* R,
                              int ldr, int relu, const float* ln_gamma, const float* ln_beta, float ln_eps,
                              int out_dtype, const uint8_t* row_mask, kinet_stream_t stream) {
-    KINET_CHECK_ARG(M >= 0 && N >= 0 && K > 0, "gemm: invalid sizes M=%d N=%d K=%d", M, N, K);
-    KINET_CHECK_ARG(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0, "gemm: K, lda, ldb must be multiples of 8 (K=%d lda=%d ldb=%d)", K, lda, ldb);
-    KINET_CHECK_ARG(lda >= K && ldb >= K && ldc >= N, "gemm: leading dims too small");
-    KINET_CHECK_ARG(aligned16(A) && aligned16(B) && (A2 == nullptr || aligned16(A2)), "gemm: A, A2 and B must be 16-byte aligned");
-    KINET_CHECK_ARG(R == nullptr || ldr >= N, "gemm: ldr < N");
+    GemmArgs a{};
+    if (int rc = gemm_args(a, "gemm", false, true, A, A2, B, C, M, N, K, lda, ldb, ldc, in_dtype, scale, bias, R, ldr,
+                           relu, ln_gamma, ln_beta, ln_eps, row_mask))
+        return rc;
     KINET_CHECK_ARG(epilogue_aligned(C, R, N, ldc, ldr, out_dtype),
                     "gemm: C and R must be aligned to 4 output elements when ldc / ldr are multiples of 4");
-    KINET_CHECK_ARG((ln_gamma == nullptr) == (ln_beta == nullptr), "gemm: LayerNorm needs both gamma and beta");
-    KINET_CHECK_ARG(ln_gamma == nullptr || relu == 0, "gemm: LayerNorm and ReLU are exclusive");
-    GemmArgs a{};
-    a.A = A; a.A2 = A2; a.B = B; a.C = C; a.R = R; a.scale = scale; a.bias = bias; a.row_mask = row_mask;
-    a.ln_g = ln_gamma; a.ln_b = ln_beta; a.ln_eps = ln_eps;
-    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldr = ldr; a.relu = relu;
-    const long long es = (long long)dtype_size(in_dtype);
-    const long long ab = M > 0 ? ((long long)(M - 1) * lda + K) * es : 0;
-    const long long bb = N > 0 ? ((long long)(N - 1) * ldb + K) * es : 0;
-    KINET_CHECK_ARG(ab < (1LL << 31) && bb < (1LL << 31), "gemm: operand larger than 2 GiB (split the call)");
-    a.a_bytes = (int)ab;
-    a.b_bytes = (int)bb;
     if (R != nullptr) {
         const long long rb = ((long long)(M > 0 ? M - 1 : 0) * ldr + N) * (long long)dtype_size(out_dtype);
         KINET_CHECK_ARG(rb < (1LL << 31), "gemm: residual larger than 2 GiB (split the call)");
@@ -865,23 +752,15 @@ extern "C" int kinet_gemm_headmajor_ex(const void* A, const void* A2, const void
                     "gemm_headmajor: a2_rows must be 0 or >= 32 dividing M (got %d)", a2_rows);
     KINET_CHECK_ARG(out_dtype == in_dtype || (in_dtype == KINET_BF16 && out_dtype == KINET_F16),
                     "gemm_headmajor: out_dtype must equal in_dtype (or f16 from bf16)");
-    KINET_CHECK_ARG(M >= 0 && N > 0 && K > 0, "gemm_headmajor: invalid sizes");
+    GemmArgs a{};
+    if (int rc = gemm_args(a, "gemm_headmajor", true, true, A, A2, B, C, M, N, K, lda, ldb, 0, in_dtype, nullptr, bias,
+                           nullptr, 0, 0, nullptr, nullptr, 0.f, row_mask))
+        return rc;
     KINET_CHECK_ARG(rows_per_batch > 0 && M % rows_per_batch == 0, "gemm_headmajor: M must be batch*rows_per_batch");
     KINET_CHECK_ARG(head_dim > 0 && head_dim % 4 == 0 && N % head_dim == 0, "gemm_headmajor: N must be a multiple of head_dim (%% 4)");
-    KINET_CHECK_ARG(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= K && ldb >= K, "gemm_headmajor: bad K/lda/ldb");
-    KINET_CHECK_ARG(aligned16(A) && aligned16(B) && (A2 == nullptr || aligned16(A2)),
-                    "gemm_headmajor: A, A2 and B must be 16-byte aligned");
     KINET_CHECK_ARG(epilogue_aligned(C, nullptr, N, N, 0, out_dtype), "gemm_headmajor: C must be aligned to 4 output elements");
-    GemmArgs a{};
-    a.A = A; a.A2 = A2; a.B = B; a.C = C; a.bias = bias; a.row_mask = row_mask; a.a2_rows = a2_rows;
-    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = N;
+    a.a2_rows = a2_rows;
     a.hm_rows = rows_per_batch; a.hm_d = head_dim; a.hm_batch = M / rows_per_batch;
-    const long long es = (long long)dtype_size(in_dtype);
-    const long long ab = M > 0 ? ((long long)(M - 1) * lda + K) * es : 0;
-    const long long bb = ((long long)(N - 1) * ldb + K) * es;
-    KINET_CHECK_ARG(ab < (1LL << 31) && bb < (1LL << 31), "gemm_headmajor: operand larger than 2 GiB");
-    a.a_bytes = (int)ab;
-    a.b_bytes = (int)bb;
     return dispatch<false>(a, in_dtype, out_dtype, (hipStream_t)stream);
 }
 
@@ -891,27 +770,19 @@ extern "C" int kinet_gemm_headmajor_split(const void* A, const void* B, void* C,
                                           kinet_stream_t stream) {
     KINET_CHECK_ARG(out_dtype == in_dtype || (in_dtype == KINET_BF16 && out_dtype == KINET_F16),
                     "gemm_headmajor_split: out_dtype must equal in_dtype (or f16 from bf16)");
-    KINET_CHECK_ARG(M >= 0 && N > 0 && K > 0, "gemm_headmajor_split: invalid sizes");
+    GemmArgs a{};
+    if (int rc = gemm_args(a, "gemm_headmajor_split", true, false, A, nullptr, B, C, M, N, K, lda, ldb, 0, in_dtype, nullptr,
+                           bias, nullptr, 0, 0, nullptr, nullptr, 0.f, row_mask))
+        return rc;
     KINET_CHECK_ARG(rows_per_batch > 0 && M % rows_per_batch == 0, "gemm_headmajor_split: M must be batch*rows_per_batch");
     KINET_CHECK_ARG(head_dim > 0 && head_dim % 4 == 0 && tail_dim > 0 && tail_dim % 4 == 0 && split_cols > 0 &&
                         split_cols % head_dim == 0 && split_cols < N && (N - split_cols) % tail_dim == 0 &&
                         split_cols / head_dim == (N - split_cols) / tail_dim,
                     "gemm_headmajor_split: N = heads*head_dim + heads*tail_dim, dims multiples of 4");
-    KINET_CHECK_ARG(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= K && ldb >= K, "gemm_headmajor_split: bad K/lda/ldb");
-    KINET_CHECK_ARG(aligned16(A) && aligned16(B), "gemm_headmajor_split: A and B must be 16-byte aligned");
     KINET_CHECK_ARG(epilogue_aligned(C, nullptr, N, N, 0, out_dtype),
                     "gemm_headmajor_split: C must be aligned to 4 output elements");
-    GemmArgs a{};
-    a.A = A; a.B = B; a.C = C; a.bias = bias; a.row_mask = row_mask;
-    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = N;
     a.hm_rows = rows_per_batch; a.hm_d = head_dim; a.hm_batch = M / rows_per_batch;
     a.hm_split = split_cols; a.hm_d2 = tail_dim;
-    const long long es = (long long)dtype_size(in_dtype);
-    const long long ab = M > 0 ? ((long long)(M - 1) * lda + K) * es : 0;
-    const long long bb = ((long long)(N - 1) * ldb + K) * es;
-    KINET_CHECK_ARG(ab < (1LL << 31) && bb < (1LL << 31), "gemm_headmajor_split: operand larger than 2 GiB");
-    a.a_bytes = (int)ab;
-    a.b_bytes = (int)bb;
     if (M == 0) return KINET_OK;
     return dispatch<false>(a, in_dtype, out_dtype, (hipStream_t)stream);
 }
@@ -920,42 +791,49 @@ extern "C" int kinet_gemm_splitk(const void* A, const void* B, void* C, int M, i
                                  int in_dtype, const float* scale, const float* bias, const void* R, int ldr, int relu,
                                  const float* ln_gamma, const float* ln_beta, float ln_eps, int out_dtype,
                                  const uint8_t* row_mask, float* workspace, int ksplit, kinet_stream_t stream) {
-    KINET_CHECK_ARG(M >= 0 && N >= 0 && K > 0, "gemm_splitk: invalid sizes M=%d N=%d K=%d", M, N, K);
-    KINET_CHECK_ARG(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0, "gemm_splitk: K, lda, ldb must be multiples of 8");
-    KINET_CHECK_ARG(lda >= K && ldb >= K && ldc >= N, "gemm_splitk: leading dims too small");
-    KINET_CHECK_ARG(aligned16(A) && aligned16(B), "gemm_splitk: A and B must be 16-byte aligned");
-    KINET_CHECK_ARG(R == nullptr || ldr >= N, "gemm_splitk: ldr < N");
-    KINET_CHECK_ARG((ln_gamma == nullptr) == (ln_beta == nullptr), "gemm_splitk: LayerNorm needs both gamma and beta");
-    KINET_CHECK_ARG(ln_gamma == nullptr || relu == 0, "gemm_splitk: LayerNorm and ReLU are exclusive");
-    if (M == 0 || N == 0) return KINET_OK;
     GemmArgs a{};
-    a.A = A; a.B = B; a.C = C; a.R = R; a.scale = scale; a.bias = bias; a.row_mask = row_mask;
-    a.ln_g = ln_gamma; a.ln_b = ln_beta; a.ln_eps = ln_eps;
-    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldr = ldr; a.relu = relu;
-    const long long es = (long long)dtype_size(in_dtype);
-    const long long ab = ((long long)(M - 1) * lda + K) * es;
-    const long long bb = ((long long)(N - 1) * ldb + K) * es;
-    KINET_CHECK_ARG(ab < (1LL << 31) && bb < (1LL << 31), "gemm_splitk: operand larger than 2 GiB");
-    a.a_bytes = (int)ab;
-    a.b_bytes = (int)bb;
+    if (int rc = gemm_args(a, "gemm_splitk", false, false, A, nullptr, B, C, M, N, K, lda, ldb, ldc, in_dtype, scale, bias, R,
+                           ldr, relu, ln_gamma, ln_beta, ln_eps, row_mask))
+        return rc;
+    if (M == 0 || N == 0) return KINET_OK;
     return run_splitk<false>(a, in_dtype, out_dtype, workspace, ksplit, (hipStream_t)stream);
 }
 
 extern "C" int kinet_gemm_force_tile(int bm, int bn) {
-    KINET_CHECK_ARG((bm == 0 && bn == 0) || ((bm == 32 && bn == 64) || ((bm == 64 || bm == 128) && (bn == 64 || bn == 128))) ||
-                        (bm == 256 && bn == 128) || (bm == 128 && bn == 256) || (bm == 256 && bn == 256),
+    // (a tile without the LayerNorm epilogue: the fused-LayerNorm launches ignore the override)
+    KINET_CHECK_ARG((bm == 0 && bn == 0) || gemm_tile_index(bm, bn, false, false) >= 0,
                     "gemm_force_tile: unsupported tile %dx%d", bm, bn);
     force_bm = bm;
     force_bn = bn;
     return KINET_OK;
 }
 
-extern "C" int kinet_gemm_last_kernel(void) { return (last_family << 20) | (last_bm << 10) | last_bn; }
+static int pack_kernel(int family, int bm, int bn) { return (family << 20) | (bm << 10) | bn; }
+
+extern "C" int kinet_gemm_last_kernel(void) { return pack_kernel(last_family, last_bm, last_bn); }
+
+extern "C" int kinet_gemm_plan(int M, int N, int K, int Cin, int conv, int ln, int a2, int kchunk, int hm_rows,
+                               int in_dtype, int cus, int* n_launches, int* launches) {
+    KINET_CHECK_ARG(M >= 0 && N >= 0 && K > 0 && cus > 0 && n_launches != nullptr && launches != nullptr,
+                    "gemm_plan: invalid arguments");
+    const GemmProblem p{M, N, K, Cin, conv != 0, ln != 0, a2 != 0, kchunk, hm_rows, gemm_op_class(in_dtype),
+                        kinet_gemm_flags, force_bm, force_bn, solo_launch(), cus};
+    GemmPlan plan;
+    if (int rc = gemm_plan(p, plan)) return rc;
+    *n_launches = plan.n;
+    for (int i = 0; i < plan.n; ++i) {
+        const GemmTile& t = kGemmTiles[plan.launch[i].tile];
+        launches[3 * i] = pack_kernel(t.family, t.bm, t.bn);
+        launches[3 * i + 1] = plan.launch[i].m_begin;
+        launches[3 * i + 2] = plan.launch[i].m_tiles;
+    }
+    return KINET_OK;
+}
+
+extern "C" int kinet_gemm_ksplit(int M, int N, int K, int ln) { return gemm_ksplit(M, N, K, ln != 0); }
 
 extern "C" int kinet_set_solo_launch(int on) {
-    const int old = kinet_solo_launch;
-    kinet_solo_launch = on ? 1 : 0;
-    return old;
+    return kinet_solo_launch.exchange(on ? 1 : 0, std::memory_order_relaxed);
 }
 
 extern "C" int kinet_gemm_set_flags(int flags) {

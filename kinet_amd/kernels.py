@@ -6,6 +6,7 @@ Parameters (reference layout, so state_dicts load unchanged); converted copies (
 casts, OIHW->OHWI conv packing, folded FrozenBatchNorm) are cached per parameter
 version.
 """
+import ctypes
 import weakref
 
 import torch
@@ -97,41 +98,33 @@ def f32(t):
 
 
 # ----------------------------------------------------------------------------------- GEMM
-def _tile(M, N, ln=False, split=False):
-    """The gemm_kernel tile launch() in csrc/gemm.hip picks (bm, bn)."""
-    if ln:
-        return (32 if M <= 8192 else 64), (256 if N <= 256 else 320)
-    if split and M <= 4096:
-        return 64, 64
-    if M <= 4096 and N <= 1024:
-        return 32, 64
-    if N >= 512 and ((M + 127) // 128) * ((N + 127) // 128) >= 2048:
-        return 128, 128
-    return (128, 64) if N <= 64 else (64, 128)
-
-
-def ksplit_for(M, N, K, ln=False):
+def ksplit_for(M, Nout, K, ln=False):
     """Split-K factor for long-K problems with too few output tiles to fill the CUs twice
-    over (the tile choice mirrors launch() in csrc/gemm.hip); 1 = no split."""
-    if K < 1024 or M == 0:
-        return 1
-    bm, bn = _tile(M, N, ln)
-    if ((M + bm - 1) // bm) * ((N + bn - 1) // bn) >= 512:
-        return 1
-    bm, bn = _tile(M, N, ln, split=True)
-    tiles = ((M + bm - 1) // bm) * ((N + bn - 1) // bn)
-    ks = min(4, -(-768 // tiles), K // 256)
-    return ks if ks >= 2 else 1
+    over (include/kinet_gemm.h kinet_gemm_ksplit); 1 = no split."""
+    return N.lib().kinet_gemm_ksplit(M, Nout, K, 1 if ln else 0)
 
 
 GEMM_FAMILIES = ('none', 'tiled', 'tiled-dma', 'dma8', 'rw', 'rw_conv', 'conv3x3', 'stem', 'splitk')
 
 
+def _kernel_id(v):
+    return GEMM_FAMILIES[v >> 20], (v >> 10) & 1023, v & 1023
+
+
 def gemm_last_kernel():
     """(family, bm, bn) of the kernel that served this thread's last GEMM / convolution call
     (include/kinet_gemm.h kinet_gemm_last_kernel); bm = bn = 0 for the special-cased kernels."""
-    v = N.lib().kinet_gemm_last_kernel()
-    return GEMM_FAMILIES[v >> 20], (v >> 10) & 1023, v & 1023
+    return _kernel_id(N.lib().kinet_gemm_last_kernel())
+
+
+def gemm_plan(M, Nout, K, dtype_code=1, conv=False, Cin=0, ln=False, a2=False, kchunk=0, hm_rows=0, cus=256):
+    """The launches the tiled GEMM / convolution kernel plans for a problem under this thread's
+    flags and forced tile (include/kinet_gemm.h kinet_gemm_plan; needs no GPU): a list of
+    ((family, bm, bn), first row, row tiles).  dtype_code: a kinet_dtype (1 = bf16)."""
+    n, out = ctypes.c_int(0), (ctypes.c_int * 6)()
+    N.call('kinet_gemm_plan', M, Nout, K, Cin, int(conv), int(ln), int(a2), kchunk, hm_rows, dtype_code, cus,
+           ctypes.addressof(n), ctypes.addressof(out))
+    return [(_kernel_id(out[3 * i]), out[3 * i + 1], out[3 * i + 2]) for i in range(n.value)]
 
 
 def _epilogue_operand(r, ld):

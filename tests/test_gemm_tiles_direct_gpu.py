@@ -327,25 +327,51 @@ def test_splitk_linear_natural(K, knobs, cdt):
                res=res, relu=True, row_mask=mask)
 
 
-# ------------------------------------------------ the Python mirror of launch()'s tile choice
-def test_tile_mirror(K, knobs):
-    """kernels._tile (which ksplit_for depends on) equals the tile launch() picks by itself."""
+# ------------------------------------------------ the planner's answer against the launch itself
+def test_plan_matches_launch(K, knobs):
+    """kinet_gemm_plan of a call names the kernel that kinet_gemm_last_kernel reports after it (the
+    plan's last launch), on the tile the heuristic is meant to pick for the shape."""
     knobs.flags(4)
     dev = 'cuda'
-    for M, N, Kd in ((4096, 1024, 8), (4097, 1024, 8), (4096, 1028, 8), (5000, 64, 8), (5000, 68, 8),
-                     (65536, 512, 8), (65536, 508, 8)):
+
+    def ones(M, N, Kd):
         y = K.linear(torch.ones(M, Kd, dtype=BF16, device=dev), torch.ones(N, Kd, dtype=BF16, device=dev))
         torch.cuda.synchronize()
         assert (y == Kd).all()
-        _ran(K, 'tiled', *K._tile(M, N))
+
+    for M, N, Kd, bm, bn in ((4096, 1024, 8, 32, 64), (4097, 1024, 8, 64, 128), (4096, 1028, 8, 64, 128),
+                             (5000, 64, 8, 128, 64), (5000, 68, 8, 64, 128), (65536, 512, 8, 128, 128),
+                             (65536, 508, 8, 64, 128)):
+        ones(M, N, Kd)
+        assert K.gemm_plan(M, N, Kd) == [(('tiled', bm, bn), 0, -(-M // bm))]
+        _ran(K, 'tiled', bm, bn)
     # a fused-LayerNorm launch and a split-K one
     g = torch.Generator().manual_seed(1)
     y = K.linear(torch.randn(100, 64, generator=g).bfloat16().cuda(), torch.randn(256, 64, generator=g).bfloat16().cuda(),
                  ln=(torch.ones(256).cuda(), torch.zeros(256).cuda(), 1e-5))
-    _ran(K, 'tiled', *K._tile(100, 256, ln=True))
-    assert K.ksplit_for(8, 1100, 1024) > 1
-    K.linear(torch.ones(8, 1024, dtype=BF16, device=dev), torch.ones(1100, 1024, dtype=BF16, device=dev))
-    _ran(K, 'splitk', *K._tile(8, 1100, split=True))
+    assert K.gemm_plan(100, 256, 64, ln=True) == [(('tiled', 32, 256), 0, 4)]
+    _ran(K, 'tiled', 32, 256)
+    ks = K.ksplit_for(8, 1100, 1024)
+    assert ks > 1
+    y = K.linear(torch.ones(8, 1024, dtype=BF16, device=dev), torch.ones(1100, 1024, dtype=BF16, device=dev))
+    torch.cuda.synchronize()
+    assert (y == 1024).all()
+    assert K.gemm_plan(8, 1100, 1024, kchunk=1024 // ks) == [(('tiled', 64, 64), 0, 1)]    # the grid of the K slices
+    _ran(K, 'splitk', 64, 64)
+    # a multi-tap convolution planned as two launches: a round of 8-wave tiles, then the 64x128 tail
+    # (2x2 taps of 16 channels: K = 64; 140 x 256 output pixels, N = 512: 140 m-tiles of 2 column tiles)
+    knobs.flags(NO_SPECIAL)
+    y = K.conv2d_nhwc(torch.ones(1, 141, 257, 16, dtype=BF16, device=dev), torch.ones(512, 2, 2, 16, dtype=BF16, device=dev), 1, 0)
+    torch.cuda.synchronize()
+    assert y.shape == (1, 140, 256, 512) and (y == 64).all()
+    plan = K.gemm_plan(140 * 256, 512, 64, conv=True, Cin=16)
+    assert plan == [(('dma8', 256, 256), 0, 128), (('tiled', 64, 128), 128 * 256, 48)]
+    _ran(K, *plan[-1][0])
+    # an 8-wave tile under flag 2
+    knobs.flags(4 | 2)
+    ones(4096, 128, 64)
+    assert K.gemm_plan(4096, 128, 64) == [(('dma8', 256, 128), 0, 16)]
+    _ran(K, 'dma8', 256, 128)
 
 
 # -------------------------------------------------- refusals (no kernel starts) and alignment
