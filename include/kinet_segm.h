@@ -1,0 +1,76 @@
+/* kinet_amd C-ABI: the segmentation head of DeformableDETRSegm (detr_segmentation.py: MHAttentionMap
+ * :181-216, MaskHeadSmallConv :105-178, PostProcessSegm :219-253).
+ * dtype codes and conventions: include/kinet_common.h (caller's stream, caller-provided workspaces,
+ * no allocation, no synchronisation, argument errors before any launch).  Activations are NHWC.
+ * Rows of a per-query tensor are frame-major: row r = b*Q + q belongs to frame r / Q.  The
+ * entry points that broadcast a per-frame operand take `row0`, the global index of their first
+ * row, so the head can run over any chunk of rows: nothing reduces across rows, and every
+ * reduction inside a row runs in a fixed order, so the result does not depend on the chunking
+ * and reruns are bit-identical.
+ */
+#ifndef KINET_SEGM_H_
+#define KINET_SEGM_H_
+
+#include "kinet_common.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* MHAttentionMap.forward after its two projections (:203-214):
+ *   out[r, p, n] = softmax over all (n, p) of  scale * qp[r, n*D:(n+1)*D] . kp[b, p, n*D:(n+1)*D]
+ * with D = d / heads, b = r / Q, and -inf (so exactly 0 on output) where mask[b, p] != 0 -- ONE
+ * softmax jointly over the heads x HW logits of a row, not one per head.  A row whose pixels are
+ * all masked is NaN, as in torch.
+ * qp (B*Q, d), kp (B, HW, d), out (B*Q, HW, heads) in `dtype` (F32 / BF16 / F16), f32 arithmetic;
+ * mask (B, HW) bytes or NULL.  d <= 1024, d % heads == 0, heads in {1, 2, 4, 8, 16, 32}.
+ * Two passes over the keys (max and sum online, then the normalised values): no logit buffer. */
+int kinet_segm_attention(const void* qp, const void* kp, const uint8_t* mask, void* out, int B, int Q, int HW,
+                         int heads, int d, float scale, int dtype, kinet_stream_t stream);
+
+/* lay1 of the mask head (:144-146) on [src | attention] without the concatenation: the
+ * convolution is linear, so
+ *   y[r] = frame[(row0 + r) / Q] + conv3x3_pad1(att[r]; w_att)
+ * where frame (B, H, W, Cout) f32 = conv3x3(src; W[:, :d]) + bias is computed once per frame
+ * (kinet_conv2d) and w_att (3, 3, Ca, Cout) f32 holds W[:, d:] with w_att[ky][kx][ci][co] =
+ * W[co][d + ci][ky][kx].  att (rows, H, W, Ca) and y (rows, H, W, Cout) in `dtype`; f32 FMAs in
+ * the order frame, then (ky, kx, ci).  Ca == 8 (the reference's nheads), Cout <= 512;
+ * row0 + rows <= B*Q, rows <= 65535 per call. */
+int kinet_segm_lay1(const void* att, const float* w_att, const float* frame, void* y, int rows, int row0, int Q,
+                    int B, int H, int W, int Ca, int Cout, int dtype, kinet_stream_t stream);
+
+/* GroupNorm + ReLU of the head (:147-175), optionally followed by the nearest upsampling and the
+ * FPN add (:153-156, :161-164, :169-172):
+ *   y[r][Y, X, c] = (f ? f[(row0 + r) / Q][Y, X, c] : 0) + relu(GN_groups(x[r]))[sy(Y), sx(X), c]
+ * with torch's legacy mode="nearest" rule, sy(Y) = min(floorf(Y * ((float)h / H)), h - 1).
+ * x (rows, h, w, C), y (rows, H, W, C), f (B, H, W, C) or NULL, all in `dtype`; gamma / beta f32;
+ * statistics per row over (h*w, C / groups) in f32, taken of x - pivot (the rule of
+ * kinet_groupnorm) in a fixed order.  C % 8 == 0 (a thread moves 8 channels: x, y, f 16-byte
+ * aligned), C <= 2048, groups <= 128; C / groups may be any size (264 / 8 = 33, a vector then spans
+ * two groups).  Without f, (H, W) must equal (h, w).  rows <= 65535 per call.
+ * ws: kinet_segm_gn_workspace(rows, h*w, groups) floats. */
+long kinet_segm_gn_workspace(int rows, int hw, int groups);
+int kinet_segm_gn_relu_up_add(const void* x, const float* gamma, const float* beta, const void* f, void* y,
+                              int rows, int row0, int Q, int B, int h, int w, int H, int W, int C, int groups,
+                              float eps, int dtype, float* ws, kinet_stream_t stream);
+
+/* out_lay (:177): 3x3, pad 1, C -> 1 channel, a direct kernel (an N = 1 implicit GEMM wastes a
+ * tile).  x (rows, H, W, C) in `dtype`, wt (3, 3, C) f32 with wt[ky][kx][c] = W[0][c][ky][kx],
+ * bias one f32 on the device; y (rows, H, W) f32 = bias + sum over (ky, kx, c) in that order.
+ * C <= 64. */
+int kinet_segm_out_conv(const void* x, const float* wt, const float* bias, float* y, int rows, int H, int W, int C,
+                        int dtype, kinet_stream_t stream);
+
+/* PostProcessSegm.forward (:224-253) for one frame, without the full-resolution intermediate:
+ *   p = sigmoid(bilinear_{align_corners=False}(logits -> (max_h, max_w)))[:img_h, :img_w]
+ *   out = nearest(p -> (oh, ow))       as uint8 (p > threshold), or as f32 p with return_probs
+ * logits (Q, h, w) f32; out (Q, oh, ow).  img_h <= max_h, img_w <= max_w.  The bilinear and
+ * nearest index rules are torch's (area_pixel_compute_source_index, legacy nearest). */
+int kinet_segm_postprocess(const float* logits, void* out, int Q, int h, int w, int max_h, int max_w, int img_h,
+                           int img_w, int oh, int ow, float threshold, int return_probs, kinet_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* KINET_SEGM_H_ */

@@ -101,12 +101,18 @@ _SIGS = {
     'kinet_two_stage_queries': [P, P, P, P, P, I, I, I, I, P],
     'kinet_two_stage_fill_rows': [P, P, P, I64, I, I, P],
     'kinet_two_stage_boxes': [P, P, P, P, I64, P],
+    'kinet_segm_attention': [P, P, P, P, I, I, I, I, I, F, I, P],
+    'kinet_segm_lay1': [P, P, P, P] + [I] * 9 + [P],
+    'kinet_segm_gn_workspace': [I, I, I],
+    'kinet_segm_gn_relu_up_add': [P] * 5 + [I] * 10 + [F, I, P, P],
+    'kinet_segm_out_conv': [P, P, P, P, I, I, I, I, I, P],
+    'kinet_segm_postprocess': [P, P] + [I] * 9 + [F, I, P],
     'kinet_last_error': [],
     'kinet_version': [],
 }
 _RESTYPES = {'kinet_last_error': ctypes.c_char_p, 'kinet_version': ctypes.c_char_p,
              'kinet_msda_backward_workspace_bytes': ctypes.c_int64, 'kinet_msda_backward_tune': None,
-             'kinet_groupnorm_workspace': ctypes.c_long,
+             'kinet_groupnorm_workspace': ctypes.c_long, 'kinet_segm_gn_workspace': ctypes.c_long,
              'kinet_gemm_tn_workspace': ctypes.c_int64, 'kinet_colsum_workspace': ctypes.c_int64,
              'kinet_layernorm_backward_workspace': ctypes.c_int64,
              'kinet_dropout_add_layernorm_backward_workspace': ctypes.c_int64,

@@ -1495,3 +1495,110 @@ def mha_backward(q, k, v, do, heads, scale, key_mask=None, dropout_p=0.0, seed=N
            N.ptr(seed) if dropout_p > 0 else None, N.stream(q.device),
            work={'family': 'attn', 'flops': 8.0 * B * heads * Lq * Lk * (E // heads)})
     return dq, dk, dv
+
+
+# ------------------------------------------------------------------- segmentation head
+def segm_attention(qp, kp, mask, Q, heads, out=None):
+    """Joint-softmax attention map (kinet_segm_attention): qp (B*Q, d), kp (B, HW, d), mask (B, HW)
+    bool / uint8 or None -> (B*Q, HW, heads) in qp's dtype, one softmax over heads x HW per row."""
+    N.require_gpu(qp, kp)
+    B, HW, d = kp.shape
+    qp, kp = qp.contiguous(), kp.contiguous()
+    if qp.shape != (B * Q, d) or kp.dtype != qp.dtype:
+        raise RuntimeError(f'segm_attention: qp {tuple(qp.shape)} {qp.dtype} does not match kp {tuple(kp.shape)} {kp.dtype}')
+    m = None
+    if mask is not None:
+        m = mask.reshape(B, HW).contiguous()
+        m = m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
+    if out is None:
+        out = torch.empty((B * Q, HW, heads), dtype=qp.dtype, device=qp.device)
+    N.call('kinet_segm_attention', N.ptr(qp), N.ptr(kp), N.ptr(m), N.ptr(out), B, Q, HW, heads, d,
+           float(d // heads) ** -0.5 if heads else 0.0, N.dtype_code(qp.dtype), N.stream(qp.device),
+           work={'family': 'segm', 'flops': 4.0 * B * Q * HW * d})
+    return out
+
+
+def segm_lay1_weights(weight, d):
+    """lay1's weight (Cout, d + Ca, 3, 3) split for the two parts of the convolution: the packed
+    per-frame weights (Cout, 3, 3, d) per compute dtype come from pack_segm_lay1_src; this is the
+    attention part as f32 (3, 3, Ca, Cout).  Cached per parameter version."""
+    return cached(weight, ('segm_lay1_att', d),
+                  lambda t: t.detach()[:, d:].permute(2, 3, 1, 0).float().contiguous())
+
+
+def pack_segm_lay1_src(weight, d, dtype):
+    """lay1's source-channel weights W[:, :d] packed OHWI in `dtype` (kinet_conv2d operand)."""
+    return cached(weight, ('segm_lay1_src', d, dtype),
+                  lambda t: t.detach()[:, :d].permute(0, 2, 3, 1).to(dtype).contiguous())
+
+
+def segm_lay1(att, w_att, frame, row0, Q):
+    """y[r] = frame[(row0 + r) // Q] + conv3x3(att[r]; w_att) (kinet_segm_lay1): att (rows, H, W, 8),
+    w_att (3, 3, 8, Cout) f32, frame (B, H, W, Cout) f32 -> (rows, H, W, Cout) in att's dtype."""
+    N.require_gpu(att, frame)
+    rows, H, W, Ca = att.shape
+    B, Cout = frame.shape[0], frame.shape[3]
+    if frame.dtype != torch.float32 or tuple(frame.shape[1:3]) != (H, W) or tuple(w_att.shape) != (3, 3, Ca, Cout):
+        raise RuntimeError('segm_lay1: frame must be f32 (B, H, W, Cout) and w_att (3, 3, Ca, Cout)')
+    y = torch.empty((rows, H, W, Cout), dtype=att.dtype, device=att.device)
+    N.call('kinet_segm_lay1', N.ptr(att.contiguous()), N.ptr(w_att), N.ptr(frame.contiguous()), N.ptr(y), rows, row0,
+           Q, B, H, W, Ca, Cout, N.dtype_code(att.dtype), N.stream(att.device),
+           work={'family': 'segm', 'flops': 2.0 * rows * H * W * Cout * 9 * Ca,
+                 'bytes': y.numel() * y.element_size()})
+    return y
+
+
+def segm_gn_relu(x, weight, bias, groups, eps=1e-5, fpn=None, row0=0, Q=None):
+    """relu(GroupNorm(x)) per row, optionally nearest-upsampled to fpn's size and added to
+    fpn[(row0 + r) // Q] (kinet_segm_gn_relu_up_add): x (rows, h, w, C), fpn (B, H, W, C) or None."""
+    N.require_gpu(x)
+    rows, h, w, C = x.shape
+    x = x.contiguous()
+    if fpn is not None:
+        if fpn.dtype != x.dtype or fpn.shape[3] != C:
+            raise RuntimeError('segm_gn_relu: fpn must be (B, H, W, C) in x\'s dtype')
+        fpn = fpn.contiguous()
+        B, H, W = fpn.shape[:3]
+    else:
+        B, H, W, Q = 1, h, w, None      # no per-frame operand: the rows are one "frame"
+    Qn = int(Q) if Q is not None else max(rows + row0, 1)
+    y = torch.empty((rows, H, W, C), dtype=x.dtype, device=x.device)
+    ws = torch.empty(max(1, N.lib().kinet_segm_gn_workspace(rows, h * w, groups)), dtype=torch.float32, device=x.device)
+    N.call('kinet_segm_gn_relu_up_add', N.ptr(x), N.ptr(f32(weight)), N.ptr(f32(bias)), N.ptr(fpn), N.ptr(y), rows,
+           row0, Qn, B, h, w, H, W, C, groups, float(eps), N.dtype_code(x.dtype), N.ptr(ws), N.stream(x.device),
+           work={'family': 'segm', 'bytes': (2 * x.numel() + y.numel()) * x.element_size()})
+    return y
+
+
+def segm_out_weights(weight):
+    """out_lay's weight (1, C, 3, 3) as f32 (3, 3, C), cached per parameter version."""
+    return cached(weight, 'segm_out', lambda t: t.detach()[0].permute(1, 2, 0).float().contiguous())
+
+
+def segm_out_conv(x, wt, bias, out=None):
+    """3x3 pad-1 convolution to one channel (kinet_segm_out_conv): x (rows, H, W, C), wt (3, 3, C) f32,
+    bias (1,) f32 -> (rows, H, W) f32."""
+    N.require_gpu(x)
+    rows, H, W, C = x.shape
+    if out is None:
+        out = torch.empty((rows, H, W), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != rows * H * W:
+        raise RuntimeError('segm_out_conv: out must be contiguous f32 (rows, H, W)')
+    N.call('kinet_segm_out_conv', N.ptr(x.contiguous()), N.ptr(wt), N.ptr(bias), N.ptr(out), rows, H, W, C,
+           N.dtype_code(x.dtype), N.stream(x.device),
+           work={'family': 'segm', 'flops': 18.0 * rows * H * W * C, 'bytes': x.numel() * x.element_size()})
+    return out
+
+
+def segm_postprocess(logits, max_hw, img_hw, out_hw, threshold=0.5, return_probs=False):
+    """PostProcessSegm for one frame (kinet_segm_postprocess): logits (Q, h, w) f32 -> (Q, 1, oh, ow)
+    uint8 (probability > threshold) or f32 probabilities.  Sizes are host ints."""
+    N.require_gpu(logits)
+    logits = logits.float().contiguous()
+    Q, h, w = logits.shape
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    out = torch.empty((Q, 1, oh, ow), dtype=torch.float32 if return_probs else torch.uint8, device=logits.device)
+    N.call('kinet_segm_postprocess', N.ptr(logits), N.ptr(out), Q, h, w, int(max_hw[0]), int(max_hw[1]),
+           int(img_hw[0]), int(img_hw[1]), oh, ow, float(threshold), int(return_probs), N.stream(logits.device),
+           work={'family': 'segm', 'bytes': out.numel() * out.element_size()})
+    return out

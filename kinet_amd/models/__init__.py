@@ -10,7 +10,12 @@ families are built: the deformable image branch (:51-71, the hot path), the Kine
 branch (`args.kine`, :72-107, kinet_amd/models/kinet.py) and vanilla DETR (:111-125, the
 reference's default `deformable: false`; kinet_amd/models/detr.py, inference only).  The
 deformable branch also builds the two-stage variant (`two_stage: true`, inference only; the
-proposal stage runs on csrc/two_stage.hip).  The segmentation heads (`masks`) raise.
+proposal stage runs on csrc/two_stage.hip) and, with `masks: true` (cfgs/train_coco_person_masks.yaml,
+cfgs/train_mots20.yaml), DeformableDETRSegm / DeformableDETRSegmTracking plus the 'segm'
+postprocessor (:63-69, :165-166; kinet_amd/models/segmentation.py on csrc/segm.hip, inference
+only: `out['pred_masks']`).  Still raising NotImplementedError: `masks` without `deformable`
+(vanilla DETRSegm / DETRSegmTracking) or with `two_stage`, the panoptic postprocessor
+(dataset coco_panoptic), and the mask / dice losses (the criterion is built without them).
 """
 import torch
 
@@ -19,6 +24,7 @@ from kinet_amd.models.deformable_detr import DeformableDETR, DeformablePostProce
 from kinet_amd.models.deformable_transformer import build_deforamble_transformer
 from kinet_amd.models.detr import DETR
 from kinet_amd.models.detr_tracking import DeformableDETRTracking, DETRTracking
+from kinet_amd.models.segmentation import DeformableDETRSegm, DeformableDETRSegmTracking, PostProcessSegm
 from kinet_amd.models.misc import NestedTensor, NestedTensorKinet, nested_tensor_from_tensor_list
 
 NUM_CLASSES = {'coco': 91, 'coco_panoptic': 250, 'coco_person': 20, 'mot': 20, 'mot_crowdhuman': 20,
@@ -37,8 +43,14 @@ def build_model(args):
         model = build_kinet(args, num_classes)
         post = {'bbox': DeformablePostProcess() if args.focal_loss else PostProcess()}
         return model, build_criterion(args, num_classes, matcher), post
-    if getattr(args, 'masks', False):
-        raise NotImplementedError('segmentation heads are outside the hot path')
+    masks = bool(getattr(args, 'masks', False))
+    if masks and not args.deformable:
+        raise NotImplementedError('segmentation heads are built for Deformable DETR only: vanilla DETRSegm / '
+                                  'DETRSegmTracking (masks without deformable) are not built')
+    if masks and args.two_stage:
+        raise NotImplementedError('masks with two_stage is not built')
+    if masks and args.dataset == 'coco_panoptic':
+        raise NotImplementedError('PostProcessPanoptic is not built')
     if not args.deformable:
         return _build_detr(args, num_classes)
     if args.two_stage and (args.tracking or args.multi_frame_attention):
@@ -67,13 +79,19 @@ def build_model(args):
         'multi_frame_encoding': args.multi_frame_encoding,
         'merge_frame_features': args.merge_frame_features,
     }
+    mask_kwargs = {'freeze_detr': getattr(args, 'freeze_detr', False)}
     if args.tracking:
         tracking_kwargs = {
             'track_query_false_positive_prob': args.track_query_false_positive_prob,
             'track_query_false_negative_prob': args.track_query_false_negative_prob,
             'matcher': matcher,
             'backprop_prev_frame': args.track_backprop_prev_frame}
-        model = DeformableDETRTracking(tracking_kwargs, detr_kwargs)
+        if masks:
+            model = DeformableDETRSegmTracking(mask_kwargs, tracking_kwargs, detr_kwargs)
+        else:
+            model = DeformableDETRTracking(tracking_kwargs, detr_kwargs)
+    elif masks:
+        model = DeformableDETRSegm(mask_kwargs, detr_kwargs)
     else:
         model = DeformableDETR(**detr_kwargs)
     criterion = None
@@ -83,6 +101,9 @@ def build_model(args):
     except ImportError:
         pass
     postprocessors = {'bbox': DeformablePostProcess()}
+    if masks:
+        # the criterion above carries no mask / dice losses (training the heads is not built)
+        postprocessors['segm'] = PostProcessSegm()
     return model, criterion, postprocessors
 
 
@@ -115,4 +136,5 @@ def _build_detr(args, num_classes):
 
 
 __all__ = ['build_model', 'DETR', 'DETRTracking', 'DeformableDETR', 'DeformableDETRTracking', 'DeformablePostProcess', 'PostProcess',
+           'DeformableDETRSegm', 'DeformableDETRSegmTracking', 'PostProcessSegm',
            'NestedTensor', 'NestedTensorKinet', 'nested_tensor_from_tensor_list']

@@ -2,7 +2,8 @@
 
 DEFAULTS are the keys of cfgs/train.yaml that build_model and the detector read; NAMED
 are the named configs layered on top (cfgs/train_detr.yaml, train_deformable.yaml, train_multi_frame.yaml,
-train_tracking.yaml, train_mot17.yaml, train_full_res.yaml, train_kinet.yaml).  `load_args(*names, **kw)`
+train_tracking.yaml, train_mot17.yaml, train_full_res.yaml, train_kinet.yaml, train_coco_person_masks.yaml,
+train_mots20.yaml).  `load_args(*names, **kw)`
 returns the argparse.Namespace build_model expects (util/misc.py:668-674 equivalent).
 """
 from argparse import Namespace
@@ -41,6 +42,11 @@ NAMED = {
                            track_query_false_positive_eos_weight=True),
     'train_mot17': dict(dataset='mot', epochs=50, lr_drop=10),
     'train_full_res': dict(img_transform={'max_size': 1920, 'val_width': 1080}),
+    # the two segmentation configs (on top of train_deformable; train_mots20 also on train_tracking):
+    # kinet_amd/models/segmentation.py, inference only
+    'train_coco_person_masks': dict(dataset='coco_person', freeze_detr=True, masks=True, lr=0.0001, lr_drop=50,
+                                    epochs=50),
+    'train_mots20': dict(dataset='mot', masks=True, lr=0.00001, lr_backbone=0.000001, epochs=40, lr_drop=40),
     # the KineT model; `tracking` comes from train_tracking as in the reference runs
     'train_kinet': dict(dataset='mot_kine', kine=True, position_embedding='sine', multi_frame_encoding=True,
                         track_prev_frame_range=5, use_encoding_tracklets=False, use_encoding_dets=False,

@@ -279,6 +279,10 @@ class DeformableDETR(nn.Module):
                 offs.append(off)
                 off += h * w
             self._project_frame(fn, src, offs)
+        if getattr(self, '_segm_want', False):
+            # the mask head's inputs (kinet_amd/models/segmentation.py): the current frame's backbone
+            # features, their masks and where its levels start in `src` (offs of the last frame)
+            self._segm_ctx = {'src': src, 'offsets': offs, 'shapes': cur_shapes, 'feats': feats, 'masks': all_masks}
 
         if self.two_stage:
             # the proposals' box head: bbox_embed[num_layers] (the reference reads it through

@@ -1,0 +1,252 @@
+"""Segmentation heads of Deformable DETR on the kinet_amd kernels (inference only).
+
+Mirrors src/trackformer/models/detr_segmentation.py: DETRSegmBase :29-71, DeformableDETRSegm
+:81-84, DeformableDETRSegmTracking :94-98, MaskHeadSmallConv :105-178, MHAttentionMap :181-216 and
+PostProcessSegm :219-253, with identical module / parameter names (`bbox_attention.{q,k}_linear`,
+`mask_head.{lay1..5, gn1..5, out_lay, adapter1..3}`), MRO and constructor arguments, so the
+reference's checkpoints load unchanged.  `out['pred_masks']` is f32 (B, Q_total, H/4, W/4) and the
+fourth return value is the memory LEVEL (B, d, h, w) the attention map reads, not the list.
+
+The head runs csrc/segm.hip (include/kinet_segm.h) and kinet_conv2d in the compute dtype:
+  * attention map: q_linear / k_linear are GEMMs on rows, then one joint softmax over heads x h*w;
+  * lay1 (d+8 -> d+8, 3x3) is linear in its concatenated input [src | attention], so its src part
+    (+ bias) is ONE f32 convolution per frame and only the 8 attention channels (K = 72) are
+    convolved per query, added to the frame part broadcast over the frame's queries;
+  * GroupNorm + ReLU (+ nearest upsample + FPN add) is one entry point; lay2..lay5 are
+    kinet_conv2d; out_lay (16 -> 1) is a direct kernel; the adapters are 1x1 GEMMs once per frame.
+Rows are frame-major (row b*Q + q, `_expand` of :101-102).  The head runs over chunks of rows
+(`mask_query_chunk`, None = sized to `MASK_WORKSPACE_BYTES`); nothing reduces across rows and no
+kernel choice depends on the chunk (split-K is off), so pred_masks does not depend on the chunking.
+
+Not built (NotImplementedError): the training forward and the mask losses, vanilla DETRSegm,
+masks with two_stage, PostProcessPanoptic.  Reference defect: DETRSegmBase.forward(samples,
+targets) drops `prev_features`, so the reference tracker's three-argument call (tracker.py:309) is
+a TypeError with a masks model; here forward(samples, targets=None, prev_features=None) passes it on.
+"""
+import torch
+from torch import nn
+
+from kinet_amd import kernels as K
+from kinet_amd.models.deformable_detr import DeformableDETR
+from kinet_amd.models.deformable_transformer import fast_path
+from kinet_amd.models.detr_tracking import DETRTrackingBase
+
+MASK_WORKSPACE_BYTES = 256 << 20   # bound on one chunk's largest pair of activations
+
+
+class MHAttentionMap(nn.Module):
+    """detr_segmentation.py:181-216: the attention softmax alone (no product with values), ONE
+    softmax over heads x pixels.  forward works on rows: q (B*Q, d), k (B, h*w, d)."""
+
+    def __init__(self, query_dim, hidden_dim, num_heads, dropout=0.0, bias=True):
+        super().__init__()
+        if dropout:
+            raise NotImplementedError('MHAttentionMap: the reference builds it with dropout 0.0')
+        self.num_heads = num_heads
+        self.hidden_dim = hidden_dim
+        self.dropout = nn.Dropout(dropout)
+        self.q_linear = nn.Linear(query_dim, hidden_dim, bias=bias)
+        self.k_linear = nn.Linear(query_dim, hidden_dim, bias=bias)
+        nn.init.zeros_(self.k_linear.bias)
+        nn.init.zeros_(self.q_linear.bias)
+        nn.init.xavier_uniform_(self.k_linear.weight)
+        nn.init.xavier_uniform_(self.q_linear.weight)
+        self.normalize_fact = float(hidden_dim / self.num_heads) ** -0.5
+
+    def forward(self, q, k, mask=None):
+        """q (B, Q, d), k (B, h*w, d) memory rows, mask (B, h*w) -> (B*Q, h*w, heads)."""
+        if not fast_path(self):
+            raise NotImplementedError('the segmentation head runs the inference path only (eval mode under '
+                                      'torch.no_grad())')
+        B, Q, d = q.shape
+        qp = K.linear(q.reshape(B * Q, d), self.q_linear.weight, self.q_linear.bias)
+        kp = K.linear(k.reshape(-1, d), self.k_linear.weight, self.k_linear.bias)
+        return K.segm_attention(qp, kp.view(B, -1, self.hidden_dim), mask, Q, self.num_heads)
+
+
+class MaskHeadSmallConv(nn.Module):
+    """detr_segmentation.py:105-178, NHWC, lay1 split into its per-frame and per-query parts."""
+
+    def __init__(self, dim, fpn_dims, context_dim):
+        super().__init__()
+        inter_dims = [dim, context_dim // 2, context_dim // 4, context_dim // 8, context_dim // 16, context_dim // 64]
+        self.lay1 = nn.Conv2d(dim, dim, 3, padding=1)
+        self.gn1 = nn.GroupNorm(8, dim)
+        self.lay2 = nn.Conv2d(dim, inter_dims[1], 3, padding=1)
+        self.gn2 = nn.GroupNorm(8, inter_dims[1])
+        self.lay3 = nn.Conv2d(inter_dims[1], inter_dims[2], 3, padding=1)
+        self.gn3 = nn.GroupNorm(8, inter_dims[2])
+        self.lay4 = nn.Conv2d(inter_dims[2], inter_dims[3], 3, padding=1)
+        self.gn4 = nn.GroupNorm(8, inter_dims[3])
+        self.lay5 = nn.Conv2d(inter_dims[3], inter_dims[4], 3, padding=1)
+        self.gn5 = nn.GroupNorm(8, inter_dims[4])
+        self.out_lay = nn.Conv2d(inter_dims[4], 1, 3, padding=1)
+        self.dim = dim
+        self.adapter1 = nn.Conv2d(fpn_dims[0], inter_dims[1], 1)
+        self.adapter2 = nn.Conv2d(fpn_dims[1], inter_dims[2], 1)
+        self.adapter3 = nn.Conv2d(fpn_dims[2], inter_dims[3], 1)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_uniform_(m.weight, a=1)
+                nn.init.constant_(m.bias, 0)
+
+    # ---- per-frame operands
+    def frame_part(self, src):
+        """conv3x3(src; lay1.weight[:, :d]) + lay1.bias in f32: (B, h, w, d) -> (B, h, w, dim)."""
+        d = src.shape[3]
+        w = K.pack_segm_lay1_src(self.lay1.weight, d, torch.float32)
+        # (src may be a strided view of the flattened transformer input: the convolution reads packed NHWC)
+        return K.conv2d_nhwc(src.float().contiguous(), w, 1, 1, bias=K.f32(self.lay1.bias), ksplit=1)
+
+    def adapters(self, fpns):
+        """The three 1x1 adapters on the NHWC backbone features (layer3, layer2, layer1)."""
+        out = []
+        for ad, x in zip((self.adapter1, self.adapter2, self.adapter3), fpns):
+            B, h, w, C = x.shape
+            out.append(K.linear(x.view(B * h * w, C), K.param_matrix(ad.weight), ad.bias).view(B, h, w, -1))
+        return out
+
+    @staticmethod
+    def _conv(x, conv):
+        return K.conv2d_nhwc(x, K.pack_conv_weight(conv.weight, x.dtype), 1, 1, bias=K.f32(conv.bias), ksplit=1)
+
+    @staticmethod
+    def _gn(x, gn, fpn=None, row0=0, Q=None):
+        return K.segm_gn_relu(x, gn.weight, gn.bias, gn.num_groups, gn.eps, fpn=fpn, row0=row0, Q=Q)
+
+    def rows(self, att, frame, fpn_adapted, row0, Q, out):
+        """The head for rows [row0, row0 + n) of the B*Q rows: att (n, h, w, heads) -> out (n, H, W) f32."""
+        d = self.dim - att.shape[3]
+        x = K.segm_lay1(att, K.segm_lay1_weights(self.lay1.weight, d), frame, row0, Q)
+        x = self._gn(x, self.gn1)
+        x = self._conv(x, self.lay2)
+        # the first "interpolate" (:156) maps stride 16 onto stride 16: the identity of the same entry point
+        x = self._gn(x, self.gn2, fpn_adapted[0], row0, Q)
+        x = self._conv(x, self.lay3)
+        x = self._gn(x, self.gn3, fpn_adapted[1], row0, Q)
+        x = self._conv(x, self.lay4)
+        x = self._gn(x, self.gn4, fpn_adapted[2], row0, Q)
+        x = self._conv(x, self.lay5)
+        x = self._gn(x, self.gn5)
+        return K.segm_out_conv(x, K.segm_out_weights(self.out_lay.weight), K.f32(self.out_lay.bias), out=out)
+
+    def forward(self, src, att, fpns, Q, chunk=None):
+        """src (B, h, w, d) NHWC, att (B*Q, h, w, heads), fpns NHWC backbone features [layer3, layer2,
+        layer1] -> (B*Q, H/4, W/4) f32 logits."""
+        if not fast_path(self):
+            raise NotImplementedError('the segmentation head runs the inference path only (eval mode under '
+                                      'torch.no_grad())')
+        frame = self.frame_part(src)
+        adapted = self.adapters(fpns)
+        R = att.shape[0]
+        H, W = adapted[2].shape[1:3]
+        out = torch.empty((R, H, W), dtype=torch.float32, device=att.device)
+        if chunk is None:
+            # the largest pair of live activations of a row: lay5's input and output at stride 4, and
+            # lay4's pair one level down
+            c4, c5 = self.lay4.out_channels, self.lay5.out_channels
+            per_row = H * W * (2 * c4 + c5) * att.element_size()
+            chunk = max(1, MASK_WORKSPACE_BYTES // max(per_row, 1))
+        chunk = max(1, min(int(chunk), 65535))
+        for r0 in range(0, R, chunk):
+            r1 = min(R, r0 + chunk)
+            self.rows(att[r0:r1], frame, adapted, r0, Q, out[r0:r1])
+        return out
+
+
+class DETRSegmBase(nn.Module):
+    def __init__(self, freeze_detr=False):
+        if freeze_detr:
+            for param in self.parameters():
+                param.requires_grad_(False)
+        if getattr(self, 'two_stage', False):
+            raise NotImplementedError('masks with two_stage is not built')
+        if self.num_feature_levels != 4 or len(self.backbone.num_channels) != 4:
+            # input_proj[-3] must be the projection of features[-2] (detr_segmentation.py:45-48)
+            raise NotImplementedError('the segmentation head needs the 4-level detector over all four backbone layers '
+                                      '(masks: true sets return_interm_layers)')
+        nheads = self.transformer.nhead
+        self.bbox_attention = MHAttentionMap(self.hidden_dim, self.hidden_dim, nheads, dropout=0.0)
+        self.mask_head = MaskHeadSmallConv(self.hidden_dim + nheads, self.fpn_channels, self.hidden_dim)
+        self.mask_query_chunk = None    # rows of (frame, query) per pass of the head; None = by workspace bound
+        self.keep_attention = False     # True: keep the last attention map as self.last_attention
+        self.last_attention = None
+
+    @property
+    def fpn_channels(self):
+        """detr.py:61-64."""
+        return self.backbone.num_channels[:3][::-1]
+
+    def forward(self, samples, targets: list = None, prev_features=None):
+        if not fast_path(self):
+            raise NotImplementedError('DeformableDETRSegm runs the inference path only (eval mode under '
+                                      'torch.no_grad()); its training forward and the mask / dice losses are not built')
+        self._segm_want = True
+        try:
+            out, targets, features, memory, hs = super().forward(samples, targets, prev_features)
+            ctx = self._segm_ctx
+        finally:
+            self._segm_want = False
+            self._segm_ctx = None
+        # detr_segmentation.py:44-53.  src = input_proj[-3](features[-2]): the current frame's level 1
+        # of the flattened transformer input (the transformer writes new tensors, the buffer is intact)
+        B, d = hs.shape[1], self.hidden_dim
+        h, w = ctx['shapes'][1]
+        off = ctx['offsets'][1]
+        src = ctx['src'][:, off:off + h * w].reshape(B, h, w, d)
+        mask = ctx['masks'][-2]
+        feats = ctx['feats']
+        fpns = [feats[-2], feats[-3], feats[-4]]
+        memory = memory[-3]
+        if tuple(memory.shape[-2:]) != (h, w) or tuple(mask.shape[-2:]) != (h, w):
+            raise RuntimeError('segmentation head: memory level and layer-3 feature differ in size')
+        Q = hs.shape[2]
+        k_rows = memory.flatten(2).permute(0, 2, 1)                       # (B, h*w, d) rows of the level
+        att = self.bbox_attention(hs[-1], k_rows, mask.flatten(1))        # (B*Q, h*w, heads)
+        att = att.view(B * Q, h, w, -1)
+        if self.keep_attention:
+            self.last_attention = att.view(B, Q, h, w, -1).permute(0, 1, 4, 2, 3)   # the reference's (B, Q, heads, h, w)
+        seg = self.mask_head(src, att, fpns, Q, self.mask_query_chunk)
+        out['pred_masks'] = seg.view(B, Q, seg.shape[-2], seg.shape[-1])
+        return out, targets, features, memory, hs
+
+
+class DeformableDETRSegm(DETRSegmBase, DeformableDETR):
+    def __init__(self, mask_kwargs, detr_kwargs):
+        DeformableDETR.__init__(self, **detr_kwargs)
+        DETRSegmBase.__init__(self, **mask_kwargs)
+
+
+class DeformableDETRSegmTracking(DETRSegmBase, DETRTrackingBase, DeformableDETR):
+    def __init__(self, mask_kwargs, tracking_kwargs, detr_kwargs):
+        DeformableDETR.__init__(self, **detr_kwargs)
+        DETRTrackingBase.__init__(self, **tracking_kwargs)
+        DETRSegmBase.__init__(self, **mask_kwargs)
+
+
+class PostProcessSegm(nn.Module):
+    """detr_segmentation.py:219-253 on kinet_segm_postprocess: per frame, bilinear resize of the
+    logits to max_target_sizes.max(0), sigmoid, crop to the frame's size, nearest resize to its
+    original size -- in one kernel, the full-resolution intermediate is never materialised.
+    Returns CPU tensors like the reference; on_device=True leaves them on the GPU (no sync when the
+    size tensors live on the host)."""
+
+    def __init__(self, threshold=0.5):
+        super().__init__()
+        self.threshold = threshold
+
+    @torch.no_grad()
+    def forward(self, results, outputs, orig_target_sizes, max_target_sizes, return_probs=False, results_mask=None,
+                on_device=False):
+        assert len(orig_target_sizes) == len(max_target_sizes)
+        max_h, max_w = max_target_sizes.max(0)[0].tolist()
+        masks_all = outputs['pred_masks'].squeeze(2)
+        sizes = torch.as_tensor(max_target_sizes).tolist()
+        origs = torch.as_tensor(orig_target_sizes).tolist()
+        for i, (logits, t, tt) in enumerate(zip(masks_all, sizes, origs)):
+            masks = K.segm_postprocess(logits, (max_h, max_w), (t[0], t[1]), (tt[0], tt[1]), self.threshold,
+                                       return_probs)
+            if results_mask is not None:
+                masks = masks[results_mask[i]]
+            results[i]['masks'] = masks if on_device else masks.cpu()
+        return results

@@ -94,6 +94,11 @@ class Tracker:
         if generate_attention_maps:
             raise NotImplementedError('attention maps (tracker.py:38-40) need the decoder\'s attention '
                                       'probabilities, which the fused attention kernels do not export')
+        if 'segm' in obj_detector_post:
+            # the reference's own three-argument detector call (tracker.py:309) is a TypeError with a
+            # masks model (DETRSegmBase.forward takes no prev_features)
+            raise NotImplementedError('the tracker does not carry segmentation masks: run the masks model and '
+                                      'PostProcessSegm per frame, or give the tracker the \'bbox\' postprocessor alone')
         self.obj_detector = obj_detector
         self.obj_detector_post = obj_detector_post
         self.detection_obj_score_thresh = tracker_cfg['detection_obj_score_thresh']
