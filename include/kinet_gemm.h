@@ -186,6 +186,23 @@ int kinet_gemm_ksplit(int M, int N, int K, int ln);
  * launched by the tiled families, 0 for the special-cased kernels. */
 int kinet_gemm_last_kernel(void);
 
+/* Which instantiation of the resident-weight kernel (csrc/gemm_rw.hip gemm_rw_kernel, families 4 and 5
+ * above and kinet_msda_sample_records) the calling thread's last launch was, and its grid (host-side
+ * record, no reference counterpart; tests assert the instantiation they mean to test through it).
+ * out[0 .. 14] = KC (K / 32), NT (16-column tiles per wave), BMR (rows per row tile), NS (ring slots),
+ * NW (waves), OCC (workgroups per CU the launch is sized for), HAS_R, LN, HAS_A2, CR (conv-row mode),
+ * PREP (sampling-record epilogue), the output element size in bytes, grid.x (P, workgroups per
+ * column group), grid.y (column groups), the number of row tiles.  All zeros before the first such
+ * launch and after a kinet_gemm* / kinet_conv2d* call that another kernel family served. */
+int kinet_gemm_rw_last_config(int* out);
+
+/* Diagnostic bound on the resident-weight kernel's grid.x, per calling thread (0 = none, the
+ * default): P = min(P, max_p) after the launcher's own sizing, at least 1.  The kernel is persistent
+ * (workgroup x walks row tiles x, x + P, ...), so the bound only changes which workgroup computes
+ * which tile and how often a slot of its LDS ring is reused: outputs are bit-identical for every
+ * value -- a small problem can walk a wrapping ring this way.  Returns the previous value. */
+int kinet_gemm_rw_grid_cap(int max_p);
+
 /* C / R alignment: the fused epilogue moves 4 output elements per access whenever ldc (and ldr)
  * are multiples of 4, so kinet_gemm(_ex), kinet_gemm_headmajor* and kinet_conv2d(_ex) return
  * KINET_ERR_ARG for a C (or R) that is not aligned to 4 output elements in that case; other

@@ -38,6 +38,8 @@ _SIGS = {
     'kinet_set_solo_launch': [I],
     'kinet_gemm_force_tile': [I, I],
     'kinet_gemm_last_kernel': [],
+    'kinet_gemm_rw_last_config': [P],
+    'kinet_gemm_rw_grid_cap': [I],
     'kinet_gemm_plan': [I] * 11 + [P, P],
     'kinet_gemm_ksplit': [I] * 4,
     'kinet_gemm_headmajor': [P, P, P] + [I] * 7 + [P, P, I, I, P],

@@ -59,6 +59,8 @@ inline void record_kernel(int family, int bm, int bn) {
     last_family = family;
     last_bm = bm;
     last_bn = bn;
+    if (family != FAM_RW && family != FAM_RW_CONV)
+        for (int i = 0; i < RW_CFG_FIELDS; ++i) rw_last_cfg[i] = 0;
 }
 
 

@@ -66,6 +66,10 @@ bool launch_stem_conv(const GemmArgs& a, int dtype, hipStream_t stream);
 // weights resident in VGPRs, input halo tiles in LDS; false = not that geometry
 bool launch_conv3x3_c64(const GemmArgs& a, int dtype, hipStream_t stream);
 extern thread_local int rw_min_m;
+// gemm_rw.hip: the calling thread's last resident-weight launch (kinet_gemm_rw_last_config, written by
+// launch_cfg); gemm.hip's record_kernel zeroes it when another family serves a call
+constexpr int RW_CFG_FIELDS = 15;
+extern thread_local int rw_last_cfg[RW_CFG_FIELDS];
 extern thread_local int kinet_gemm_flags;   // gemm.hip (diagnostic selection flags; 128 = the read-time-split KINET_F32_X3 TN kernel)
 
 namespace {

@@ -284,6 +284,14 @@ __global__ __launch_bounds__(NW * 64, OCC) void gemm_rw_kernel(const GemmArgs p,
     const __amdgpu_buffer_rsrc_t rm =
         __builtin_amdgcn_make_buffer_rsrc((void*)(p.row_mask ? (const void*)p.row_mask : p.A), (short)0,
                                           p.row_mask ? M : 0, 0x00020000);
+    // The row mask of the last partial group of 16 rows (M % 16 != 0), as 16 wave-uniform bits read once
+    // by byte loads: the tile DMA below moves the mask 16 bytes at a time, and in the group that straddles
+    // the end of the M-byte mask the dword holding the last M % 4 bytes is out of range and reads 0
+    // (masked rows among the last M % 4 were stored unmasked).  Bytes past M, and a NULL mask (an empty
+    // descriptor), read 0
+    const int mtail0 = M & ~15;
+    const unsigned tailbits =
+        (unsigned)__ballot(__builtin_amdgcn_raw_buffer_load_b8(rm, (unsigned)(mtail0 + (lane & 15)), 0, 0) != 0) & 0xffffu;
     const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(PREP ? (const void*)p.prep_ref : p.A), (short)0, PREP ? M * 16 * p.prep_refd : 0, 0x00020000);
 
@@ -363,7 +371,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void gemm_rw_kernel(const GemmArgs p,
             const unsigned off = m0 + r_row[j] < M ? rbase + r_lo[j] : OOB;
             dma16(rr, st + C_::R_OFF + (j * NTHR + wave * 64) * 16, off);
         }
-        // row-mask bytes m0 .. m0+BMR (every wave writes the same 1 KiB; bytes past M read 0)
+        // row-mask bytes m0 .. m0+BMR (every wave writes the same 1 KiB).  A 16-byte access that
+        // straddles the end of the M-byte mask reads 0 in its last dword: the rows of the last partial
+        // group of 16 get their mask bytes from tailbits once the tile has landed (main loop)
         dma16(rm, st + C_::MASK_OFF, lane < TMR ? (unsigned)(m0 + lane * 16) : OOB);
         // PREP: the tile's reference points, BMR rows x 4 levels x prep_refd f32 (<= 1 KiB; every
         // wave writes the same bytes, rows past M read 0)
@@ -464,8 +474,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void gemm_rw_kernel(const GemmArgs p,
     int pend_slot = 0;
     auto store_pending = [&](bool valid) {
         if constexpr (HM32_OK) {
-            if (hm32) {
-                if (!valid) return;   // nothing pending (and pend_slot may be the slot about to be computed)
+            // (iteration 0, nothing pending: the S dummy stores below -- the counted waits take them for
+            // granted on this path too -- and pend_slot may be the slot about to be computed)
+            if (hm32 && valid) {
                 char* scr = stages + pend_slot * C_::STAGE + wave * (TMR * 2048);
                 const int g = lane >> 4, r = lane & 15;
 #pragma unroll
@@ -540,6 +551,14 @@ __global__ __launch_bounds__(NW * 64, OCC) void gemm_rw_kernel(const GemmArgs p,
             }
         }
         lds_barrier();
+        // the row tile that holds the last partial group of 16 rows (once per launch, and only with
+        // M % 16 != 0): its mask bytes come from tailbits.  After the barrier every wave's copy of
+        // the tile's mask DMA has landed; every wave writes the same 16 bytes and reads them back
+        // itself, so no second barrier is needed
+        if ((bx + i * P) * BMR + BMR > mtail0 && mtail0 < M) {
+            char* mk = stages + (i % NS) * C_::STAGE + C_::MASK_OFF + (mtail0 - (bx + i * P) * BMR);
+            if (lane < 16) mk[lane] = (char)((tailbits >> lane) & 1u);
+        }
         // PREP: the tile's mask bytes and reference points read BEFORE the next tile's DMA is
         // issued: an LDS read after it gets an s_waitcnt vmcnt(0) from the compiler (it cannot
         // prove the DMA's stage disjoint), which would wait for that DMA before the epilogue
@@ -554,7 +573,13 @@ __global__ __launch_bounds__(NW * 64, OCC) void gemm_rw_kernel(const GemmArgs p,
                 pref[t] = *reinterpret_cast<const float4*>(sc + C_::REF_OFF + (rl * 4 + l) * (p.prep_refd == 2 ? 8 : 16));
             }
         }
-        store_pending(i > 0);
+        // the counted waits above take S stores per iteration for granted, the dummy ones of
+        // iteration 0 included.  Seen as a constant false (an iteration 0 that the optimiser peeled
+        // off), their S equal stores of zeros to one offset fold into one; an opaque copy of i keeps
+        // every iteration's stores S instructions
+        int it = i;
+        asm volatile("" : "+s"(it));
+        store_pending(it > 0);
         if (hm32) lds_barrier();   // every wave done with its transpose scratch (the slot refilled below)
         if (i + NS - 1 < cnt) issue(i + NS - 1);
 
@@ -681,6 +706,13 @@ __global__ __launch_bounds__(NW * 64, OCC) void gemm_rw_kernel(const GemmArgs p,
     }
 }
 
+}  // namespace
+
+thread_local int rw_last_cfg[RW_CFG_FIELDS] = {};   // declared in gemm_common.h
+thread_local int rw_grid_cap = 0;                   // kinet_gemm_rw_grid_cap (0 = no cap)
+
+namespace {
+
 template <typename T, typename TO, int KC, int BMR, int NS, bool HAS_R, bool LN, bool HAS_A2 = false, int NT = 4,
           bool CR = false, bool PREP = false, int OCC = 2, int NW = 4>
 void launch_cfg(const GemmArgs& a, hipStream_t stream) {
@@ -694,6 +726,12 @@ void launch_cfg(const GemmArgs& a, hipStream_t stream) {
     const int slots = 256 * OCC;
     int P = slots / ng >= 8 ? slots / ng / 8 * 8 : slots / ng;
     if (P > n_mtiles) P = n_mtiles;
+    // diagnostics (host side, per calling thread): kinet_gemm_rw_grid_cap bounds P -- the kernel is
+    // persistent, so P only decides which workgroup walks which row tiles; kinet_gemm_rw_last_config
+    // reads the record back
+    if (rw_grid_cap > 0) P = P > rw_grid_cap ? rw_grid_cap : (P < 1 ? 1 : P);
+    const int cfg[RW_CFG_FIELDS] = {KC, NT, BMR, NS, NW, OCC, HAS_R, LN, HAS_A2, CR, PREP, (int)sizeof(TO), P, ng, n_mtiles};
+    for (int i = 0; i < RW_CFG_FIELDS; ++i) rw_last_cfg[i] = cfg[i];
     dim3 grid(P, ng), block(NW * 64);
     hipLaunchKernelGGL((gemm_rw_kernel<T, TO, KC, NT, BMR, NS, HAS_R, LN, HAS_A2, CR, PREP, OCC, NW>), grid, block, 0,
                        stream, a, n_mtiles);
@@ -914,6 +952,18 @@ bool launch_rw_conv(const GemmArgs& a, int in_dtype, hipStream_t stream) {
 }  // namespace kinet
 
 using namespace kinet;
+
+extern "C" int kinet_gemm_rw_last_config(int* out) {
+    KINET_CHECK_ARG(out != nullptr, "gemm rw last config: NULL argument");
+    for (int i = 0; i < RW_CFG_FIELDS; ++i) out[i] = rw_last_cfg[i];
+    return KINET_OK;
+}
+
+extern "C" int kinet_gemm_rw_grid_cap(int max_p) {
+    const int old = rw_grid_cap;
+    rw_grid_cap = max_p > 0 ? max_p : 0;
+    return old;
+}
 
 // The MSDA sampling-offsets | attention-weights projection of an encoder call, with the
 // softmax, sampling locations and bilinear setup in its epilogue (prep_records): writes the

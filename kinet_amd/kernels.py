@@ -117,6 +117,25 @@ def gemm_last_kernel():
     return _kernel_id(N.lib().kinet_gemm_last_kernel())
 
 
+GEMM_RW_CONFIG_FIELDS = ('KC', 'NT', 'BMR', 'NS', 'NW', 'OCC', 'HAS_R', 'LN', 'HAS_A2', 'CR', 'PREP', 'out_bytes',
+                         'P', 'ng', 'n_mtiles')
+
+
+def gemm_rw_last_config():
+    """The resident-weight kernel instantiation and grid of this thread's last launch as a dict over
+    GEMM_RW_CONFIG_FIELDS (include/kinet_gemm.h kinet_gemm_rw_last_config); all zeros when the last
+    GEMM / convolution call ran another kernel."""
+    out = (ctypes.c_int * len(GEMM_RW_CONFIG_FIELDS))()
+    N.call('kinet_gemm_rw_last_config', ctypes.addressof(out))
+    return dict(zip(GEMM_RW_CONFIG_FIELDS, out))
+
+
+def gemm_rw_grid_cap(max_p):
+    """Bound the resident-weight kernel's grid.x for this thread (0 = no bound; include/kinet_gemm.h
+    kinet_gemm_rw_grid_cap): same outputs bit for bit.  Returns the previous bound."""
+    return N.lib().kinet_gemm_rw_grid_cap(int(max_p))
+
+
 def gemm_plan(M, Nout, K, dtype_code=1, conv=False, Cin=0, ln=False, a2=False, kchunk=0, hm_rows=0, cus=256):
     """The launches the tiled GEMM / convolution kernel plans for a problem under this thread's
     flags and forced tile (include/kinet_gemm.h kinet_gemm_plan; needs no GPU): a list of
@@ -332,10 +351,16 @@ def attn_out_ffn_fused(samp, out_proj, residual, norm1, linear1, linear2, norm2,
     return out.view(*samp.shape[:-1], D)
 
 
-def value_proj_headmajor(x, weight, bias, head_dim, row_mask=None, out_dtype=None):
+def _headmajor_out(out, shape, dtype):
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous() or out.data_ptr() % 16:
+        raise ValueError(f'out: a contiguous, 16-byte aligned {dtype} tensor of shape {tuple(shape)} expected')
+    return out
+
+
+def value_proj_headmajor(x, weight, bias, head_dim, row_mask=None, out_dtype=None, out=None):
     """MSDA value projection written head-major: x (B, S, K) -> (Nout/head_dim, B, S, head_dim),
     padding rows zeroed (ms_deform_attn.py:64-67).  out_dtype: x.dtype, or float16 from bf16
-    operands (the sampling kernel's mixed f16 x f32 FMA path)."""
+    operands (the sampling kernel's mixed f16 x f32 FMA path).  out: the tensor to write (tests)."""
     N.require_gpu(x)
     B, S, K = x.shape
     x2 = x.reshape(B * S, K)
@@ -344,7 +369,8 @@ def value_proj_headmajor(x, weight, bias, head_dim, row_mask=None, out_dtype=Non
     w = weight_as(weight, x.dtype)
     Nout = w.shape[0]
     od = out_dtype or x.dtype
-    out = torch.empty((Nout // head_dim, B, S, head_dim), dtype=od, device=x.device)
+    shape = (Nout // head_dim, B, S, head_dim)
+    out = torch.empty(shape, dtype=od, device=x.device) if out is None else _headmajor_out(out, shape, od)
     mask = row_mask.reshape(-1).to(torch.uint8).contiguous() if row_mask is not None else None
     e = x.element_size()
     N.call('kinet_gemm_headmajor', N.ptr(x2), N.ptr(w), N.ptr(out), B * S, Nout, K, x2.stride(0), K,
@@ -395,11 +421,11 @@ def split_value_weights(weight, bias, heads):
     return cached(weight, 'split_w', perm), cached(bias, 'split_b', lambda b: perm(b).float().contiguous())
 
 
-def value_proj_headmajor_split(x, weight_split, bias_split, heads, row_mask=None, out_dtype=None):
+def value_proj_headmajor_split(x, weight_split, bias_split, heads, row_mask=None, out_dtype=None, out=None):
     """MSDA value projection of a head_dim-36 layer into the two planes the split encoder
     kernel reads (kinet_gemm_headmajor_split): x (B, S, K), weight/bias from split_value_weights
     -> SplitValue(main (heads, B, S, 32), tail (heads, B, S, 4)); padding rows zeroed
-    (ms_deform_attn.py:64-67)."""
+    (ms_deform_attn.py:64-67).  out: the flat B*S*Nout buffer to write both planes into (tests)."""
     N.require_gpu(x)
     B, S, K = x.shape
     x2 = x.reshape(B * S, K)
@@ -408,7 +434,7 @@ def value_proj_headmajor_split(x, weight_split, bias_split, heads, row_mask=None
     w = weight_as(weight_split, x.dtype)
     Nout = w.shape[0]
     od = out_dtype or x.dtype
-    buf = torch.empty(B * S * Nout, dtype=od, device=x.device)
+    buf = torch.empty(B * S * Nout, dtype=od, device=x.device) if out is None else _headmajor_out(out, (B * S * Nout,), od)
     main = buf[:heads * B * S * 32].view(heads, B, S, 32)
     tail = buf[heads * B * S * 32:].view(heads, B, S, Nout // heads - 32)
     mask = row_mask.reshape(-1).to(torch.uint8).contiguous() if row_mask is not None else None
@@ -1033,10 +1059,10 @@ def _load_add_operand(x2, x_add, B, Lq, K):
     return x2, a2, 0
 
 
-def offsets_proj_headmajor(x, weight, bias, heads, x_add=None, out_dtype=torch.float16):
+def offsets_proj_headmajor(x, weight, bias, heads, x_add=None, out_dtype=torch.float16, out=None):
     """The MSDA offsets + logits projection (x [+ x_add]) @ W^T + b stored head-major
     (heads, B, Lq, Nout/heads): W's rows must already be grouped per head
-    (MSDeformAttn.packed_offsets_weights_headmajor)."""
+    (MSDeformAttn.packed_offsets_weights_headmajor).  out: the tensor to write (tests)."""
     N.require_gpu(x)
     B, Lq, K = x.shape
     x2 = x.reshape(B * Lq, K)
@@ -1046,7 +1072,8 @@ def offsets_proj_headmajor(x, weight, bias, heads, x_add=None, out_dtype=torch.f
     w = weight_as(weight, x.dtype)
     Nout = w.shape[0]
     rec = Nout // heads
-    out = torch.empty((heads, B, Lq, rec), dtype=out_dtype, device=x.device)
+    shape = (heads, B, Lq, rec)
+    out = torch.empty(shape, dtype=out_dtype, device=x.device) if out is None else _headmajor_out(out, shape, out_dtype)
     e = x.element_size()
     N.call('kinet_gemm_headmajor_ex', N.ptr(x2), N.ptr(a2), N.ptr(w), N.ptr(out), B * Lq, Nout, K, x2.stride(0), K,
            N.dtype_code(x.dtype), N.dtype_code(out_dtype), N.ptr(f32(bias)), None, Lq, rec, a2_rows,

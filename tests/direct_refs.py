@@ -940,3 +940,249 @@ def conv_case(name, dtype, cls):
     else:
         x, w = generic_operands((B, H, W, Cin), (Cout, KH, KW, Cin), K, dtype, g)
     return x, w, conv64(x, w, stride, pad), conv64(x.abs(), w.abs(), stride, pad)
+
+
+# ======================================= resident-weight GEMM (csrc/gemm_rw.hip)
+# The case table of tests/test_gemm_rw_direct_gpu.py, shared with the CPU checks of its references
+# (test_direct_refs_cpu.py).  One row per variant of gemm_rw_kernel:
+#   (name, K, N, flags, opts, compute dtype, output dtype, (KC, NT, BMR, NS, NW, OCC), ng)
+# flags: kinet_gemm_set_flags bits on top of 8 (the resident-weight kernel from M >= 256), which every
+#   case sets;  opts, space separated: R residual, Rld residual with ldr = N + 8, LN LayerNorm, A2 the
+#   load-time add, s per-column scale, b bias, relu, mask the row mask, ld output rows of N + 8 elements;
+# the last two columns are the instantiation and the number of column groups EXPECTED FROM READING
+# launch_t / launch_k / launch_ring / launch_288 and RwCfg (ring_depth worked out by hand from the LDS
+# budget): literals, never taken from the library.  M is 17 * BMR - 5 for every case: 17 row tiles, the
+# last one ragged (11 of 16 or 27 of 32 rows).
+RW_F16ROW, RW_W4, RW_LN6, RW_NOTR, RW_NOSTEM = 131072, 268435456, 4194304, 1073741824, 32
+_B, _H, _F = torch.bfloat16, torch.float16, torch.float32
+RW_CASES = [
+    # K = 64: 128-byte rows, 32-row tiles whatever the epilogue (flag 131072 does not apply)
+    ('k64 plain', 64, 256, 0, '', _B, _B, (2, 4, 32, 4, 4, 2), 1),
+    ('k64 plain N=264', 64, 264, 0, 's b mask', _H, _F, (2, 4, 32, 4, 4, 2), 2),
+    ('k64 R', 64, 200, 0, 'R s b relu mask', _H, _H, (2, 4, 32, 3, 4, 2), 1),
+    ('k64 R+LN', 64, 256, 0, 'R LN mask', _B, _B, (2, 4, 32, 3, 4, 2), 1),
+    ('k64 LN', 64, 200, 0, 'LN', _H, _H, (2, 4, 32, 4, 4, 2), 1),
+    ('k64 A2', 64, 256, 0, 'A2 b', _B, _H, (2, 4, 32, 4, 4, 2), 1),
+    ('k64 A2 ld', 64, 264, 0, 'A2 ld mask', _B, _F, (2, 4, 32, 4, 4, 2), 2),
+    # K = 128
+    ('k128 plain', 128, 256, 0, '', _B, _B, (4, 4, 32, 4, 4, 2), 1),
+    ('k128 plain 16-row', 128, 264, RW_F16ROW, 's b mask', _H, _H, (4, 4, 16, 4, 4, 2), 2),
+    ('k128 R', 128, 200, 0, 'R s b relu mask', _B, _B, (4, 4, 16, 4, 4, 2), 1),
+    ('k128 R 8-wave', 128, 456, 0, 'R b', _H, _H, (4, 4, 16, 4, 8, 1), 1),
+    ('k128 R N>256 4-wave', 128, 520, RW_W4, 'Rld b mask', _B, _H, (4, 4, 16, 4, 4, 2), 3),
+    ('k128 R+LN', 128, 256, 0, 'R LN', _H, _H, (4, 4, 16, 4, 4, 2), 1),
+    ('k128 LN', 128, 200, 0, 'LN mask', _B, _F, (4, 4, 16, 4, 4, 2), 1),
+    ('k128 A2', 128, 264, 0, 'A2 b', _B, _F, (4, 4, 16, 4, 4, 2), 2),
+    ('k128 N=1024', 128, 1024, 0, 'b', _B, _H, (4, 4, 32, 4, 4, 2), 4),
+    # K = 256
+    ('k256 plain', 256, 200, 0, 's b relu', _H, _H, (8, 4, 32, 4, 4, 2), 1),
+    ('k256 plain ld', 256, 264, 0, 'b ld mask', _B, _B, (8, 4, 32, 4, 4, 2), 2),
+    ('k256 plain 16-row', 256, 256, RW_F16ROW, '', _B, _F, (8, 4, 16, 4, 4, 2), 1),
+    ('k256 R', 256, 256, 0, 'Rld b', _B, _H, (8, 4, 16, 4, 4, 2), 1),
+    ('k256 R 8-wave', 256, 512, 0, 'R s b relu mask', _B, _B, (8, 4, 16, 4, 8, 1), 1),
+    ('k256 R 8-wave N=520', 256, 520, 0, 'R b ld', _H, _H, (8, 4, 16, 4, 8, 1), 2),
+    ('k256 R N>256 4-wave', 256, 456, RW_W4, 'R s b mask', _H, _H, (8, 4, 16, 4, 4, 2), 2),
+    ('k256 R+LN', 256, 200, 0, 'R LN mask', _B, _B, (8, 4, 16, 4, 4, 2), 1),
+    ('k256 R+LN N=256', 256, 256, 0, 'R LN', _H, _H, (8, 4, 16, 4, 4, 2), 1),
+    ('k256 LN', 256, 256, 0, 'LN', _H, _F, (8, 4, 16, 4, 4, 2), 1),
+    ('k256 A2', 256, 200, 0, 'A2 b mask', _H, _H, (8, 4, 16, 4, 4, 2), 1),
+    ('k256 A2 N=264', 256, 264, 0, 'A2', _B, _F, (8, 4, 16, 4, 4, 2), 2),
+    ('k256 N=1024', 256, 1024, 0, 's b', _H, _F, (8, 4, 32, 4, 4, 2), 4),
+    # K = 512: 128-column groups of 4 waves (NT = 2), 256-column groups of 8
+    ('k512 N=128', 512, 128, 0, '', _B, _B, (16, 2, 16, 4, 4, 2), 1),
+    ('k512 N=72', 512, 72, 0, 's b relu mask', _H, _F, (16, 2, 16, 4, 4, 2), 1),
+    ('k512 8-wave', 512, 256, 0, 's b mask', _H, _H, (16, 2, 16, 4, 8, 1), 1),
+    ('k512 8-wave N=200', 512, 200, 0, 'b ld', _B, _H, (16, 2, 16, 4, 8, 1), 1),
+    ('k512 N=136 4-wave', 512, 136, RW_W4, 's b', _B, _B, (16, 2, 16, 4, 4, 2), 2),
+    ('k512 N=256 4-wave', 512, 256, RW_W4, 'b mask', _B, _F, (16, 2, 16, 4, 4, 2), 2),
+    # K = 288: 36-chunk rows (their own swizzle), 16-row tiles, 12 columns per lane (NT = 3) but for
+    # the 9-wave LayerNorm group (NT = 2)
+    ('k288 A2 8-wave', 288, 384, 0, 'A2 b', _B, _H, (9, 3, 16, 4, 8, 1), 1),
+    ('k288 A2 8-wave N=328', 288, 328, 0, 'A2 mask', _H, _F, (9, 3, 16, 4, 8, 1), 1),
+    ('k288 A2 N=192', 288, 192, 0, 'A2 b', _H, _H, (9, 3, 16, 3, 4, 2), 1),
+    ('k288 A2 N=384 4-wave', 288, 384, RW_W4, 'A2 b ld', _B, _B, (9, 3, 16, 3, 4, 2), 2),
+    ('k288 R+LN 9-wave', 288, 288, 0, 'R LN mask', _B, _B, (9, 2, 16, 4, 9, 1), 1),
+    ('k288 R+LN 9-wave N=280', 288, 280, 0, 'R LN', _H, _H, (9, 2, 16, 4, 9, 1), 1),
+    ('k288 R+LN 6-wave', 288, 288, RW_LN6, 'R LN', _H, _H, (9, 3, 16, 4, 6, 1), 1),
+    ('k288 R+LN 6-wave N=280', 288, 280, RW_LN6, 'R LN mask', _B, _B, (9, 3, 16, 4, 6, 1), 1),
+    ('k288 LN 9-wave', 288, 288, 0, 'LN', _H, _F, (9, 2, 16, 4, 9, 1), 1),
+    ('k288 LN 9-wave N=280', 288, 280, 0, 'LN mask', _B, _B, (9, 2, 16, 4, 9, 1), 1),
+    ('k288 LN 6-wave', 288, 288, RW_LN6, 'LN mask', _B, _F, (9, 3, 16, 4, 6, 1), 1),
+    ('k288 LN 6-wave N=280', 288, 280, RW_LN6, 'LN', _H, _H, (9, 3, 16, 4, 6, 1), 1),
+    ('k288 R', 288, 200, 0, 'R s b relu mask', _B, _H, (9, 3, 16, 3, 4, 2), 2),
+    ('k288 R N=136', 288, 136, 0, 'Rld b', _H, _H, (9, 3, 16, 3, 4, 2), 1),
+    ('k288 N=1728 8-wave', 288, 1728, 0, 'b', _B, _B, (9, 3, 16, 4, 8, 1), 5),
+    ('k288 N=1728 4-wave', 288, 1728, RW_W4, 'b mask', _H, _F, (9, 3, 16, 4, 4, 2), 9),
+    ('k288 N=288', 288, 288, 0, 's b ld', _B, _B, (9, 3, 16, 4, 4, 2), 2),
+    ('k288 N=392', 288, 392, 0, 'b mask', _H, _H, (9, 3, 16, 4, 8, 1), 2),
+]
+RW_TILES = 17
+RW_CONFIG_FIELDS = ('KC', 'NT', 'BMR', 'NS', 'NW', 'OCC', 'HAS_R', 'LN', 'HAS_A2', 'CR', 'PREP', 'out_bytes', 'P',
+                    'ng', 'n_mtiles')
+# grid cap -> workgroups per column group for 17 row tiles: one tile each; one workgroup walking all
+# 17 (every ring slot reused 4-8 times); 6 / 6 / 5 tiles with the ragged tile last; one workgroup with 2
+# tiles and 15 with 1 (the prefetch guard cnt < NS - 1 on both sides)
+RW_CAPS = {0: 17, 1: 1, 3: 3, 16: 16}
+
+
+def rw_rows(bmr):
+    return RW_TILES * bmr - 5
+
+
+def rw_opts(case):
+    return set(case[4].replace('Rld', 'R Rld').split())
+
+
+def rw_expected(cfg, ng, has_r, ln, a2, out_dtype, cap, cr=0, prep=0, tiles=RW_TILES):
+    """The record kinet_gemm_rw_last_config must return for a table row under grid cap `cap`."""
+    p = tiles if cap == 0 else min(cap, tiles)
+    vals = tuple(cfg) + (int(has_r), int(ln), int(a2), cr, prep, 4 if out_dtype == torch.float32 else 2, p, ng, tiles)
+    return dict(zip(RW_CONFIG_FIELDS, vals))
+
+
+def rw_mask(M, bmr):
+    """Masked rows: the first row, the first and the last row of a tile, a whole tile, the last
+    (ragged) row."""
+    m = torch.zeros(M, dtype=torch.bool)
+    m[0] = m[2 * bmr] = m[4 * bmr - 1] = m[M - 1] = True
+    m[6 * bmr:7 * bmr] = True
+    return m
+
+
+def _rw_seed(name, cls):
+    return sum(map(ord, name)) * 131 + (0 if cls == 'exact' else 5)
+
+
+def rw_inputs(case, cls, offset=0.0):
+    """Every operand of one table row as CPU tensors (f32 holding values of the operand types), and
+    its f64 reference.  cls 'exact' / 'generic' as for the tiled kernel; LayerNorm rows take exact
+    matrix operands whatever cls says, an f32 bias of offset + randn, a residual of randn rounded to the
+    output type (test_ln_epilogue_direct_gpu.py's rule) and return ln = (gamma, beta).
+    A2: exact class -- x2 multiples of 1/2 in [-1, 1], so x + x2 is exact in bf16 and f16 (multiples
+    of 1/2 up to 2, products multiples of 1/16 up to 1/2: sums still exact in f32); generic class --
+    the reference's operand is (x + x2) rounded once to the operand type, as the kernel's is.
+    Returns a dict: x, w, x2, scale, bias, res, relu, mask, ln, acc, absprod, pre, maj (pre: the f64
+    epilogue value before LayerNorm and before the row mask)."""
+    name, K, N, _, _, cdt, odt, cfg, _ = case
+    o = rw_opts(case)
+    M = rw_rows(cfg[2])
+    ln = 'LN' in o
+    if ln:
+        cls = 'exact'
+    g = torch.Generator().manual_seed(_rw_seed(name, cls) + int(offset))
+    x, w, acc, ap = gemm_case(M, N, K, cdt, cls)
+    d = dict(x=x, w=w, x2=None, scale=None, bias=None, res=None, relu='relu' in o, mask=None, ln=None)
+    if 'A2' in o:
+        x2 = exact_x((M, K), g) if cls == 'exact' else torch.randn(M, K, generator=g).to(cdt).float()
+        a = (x + x2).to(cdt).double()
+        acc, ap = a @ w.double().T, a.abs() @ w.double().abs().T
+        d['x2'] = x2
+    if ln:
+        d['bias'] = offset + torch.randn(N, generator=g)
+        if 'R' in o:
+            d['res'] = torch.randn(M, N, generator=g).to(odt).float()
+        d['ln'] = (torch.rand(N, generator=g) + 0.5, torch.randn(N, generator=g))
+    else:
+        if 's' in o or 'b' in o:
+            scale, bias = exact_epilogue(N, g) if cls == 'exact' else generic_epilogue(N, g)
+            d['bias'] = bias
+            if 's' in o:
+                d['scale'] = scale
+        if 'R' in o:
+            d['res'] = exact_res((M, N), g) if cls == 'exact' else torch.randn(M, N, generator=g).to(odt).float()
+    if 'mask' in o:
+        d['mask'] = rw_mask(M, cfg[2])
+    d['acc'], d['absprod'] = acc, ap
+    d['pre'], d['maj'] = epilogue64(acc, d['scale'], d['bias'], d['res'], d['relu'])
+    return d
+
+
+def rw_masked(v, mask):
+    return v if mask is None else torch.where(mask.reshape(-1, 1), torch.zeros_like(v), v)
+
+
+def rw_ln_check(got, inp, odt, eps=1e-5):
+    """(worst err / bound, number of elements over it) of a LayerNorm row's output `got` under
+    test_ln_epilogue_direct_gpu.py's bound: one rounding of a 16-bit output of the f64 result + 4x
+    the maximum error of torch's CPU f32 layer_norm of the same pre-activation; masked rows are 0."""
+    gam, bet = inp['ln']
+    ref, t = ln_epilogue_yardstick(inp['pre'], gam, bet, eps)
+    ref = rw_masked(ref, inp['mask'])
+    err = (got.double() - ref).abs()
+    tol = OUT_ROUND[odt] * ref.abs() + 4 * t
+    return float((err / tol).max()), int((err > tol).sum())
+
+
+def rw_generic_ratio(got, inp, K, odt):
+    """Worst err / gemm_generic_bound of the (M, N) output `got` of a case without LayerNorm."""
+    ref = rw_masked(inp['pre'], inp['mask'])
+    bound = gemm_generic_bound(inp['absprod'], K, inp['maj'], ref, odt, inp['scale'])
+    return float(((got.double() - ref).abs() / bound).max())
+
+
+# Head-major stores: (name, K, head_dim or 'split', flags, compute dtype, output dtype, config, ng);
+# N = K (the value projections), B = 7 x S = 77 rows on 32-row tiles, B = 3 x S = 89 on 16-row tiles.
+RW_HM_CASES = [
+    ('hm32 k256 transpose', 256, 32, 0, _B, _H, (8, 4, 32, 4, 4, 2), 1),
+    ('hm32 k256 direct', 256, 32, RW_NOTR, _B, _H, (8, 4, 32, 4, 4, 2), 1),
+    ('hm32 k256 transpose 16-row', 256, 32, RW_F16ROW, _H, _H, (8, 4, 16, 4, 4, 2), 1),
+    ('hm32 k256 direct 16-row', 256, 32, RW_F16ROW | RW_NOTR, _B, _B, (8, 4, 16, 4, 4, 2), 1),
+    ('hm36 k288', 288, 36, 0, _B, _H, (9, 3, 16, 4, 4, 2), 2),
+    ('hm48 k288', 288, 48, 0, _H, _H, (9, 3, 16, 4, 4, 2), 2),
+    ('hm split k288', 288, 'split', 0, _B, _H, (9, 3, 16, 4, 4, 2), 2),
+    ('hm split k288 bf16', 288, 'split', 0, _B, _B, (9, 3, 16, 4, 4, 2), 2),
+]
+
+
+def rw_hm_batch(bmr):
+    return (7, 77) if bmr == 32 else (3, 89)
+
+
+def rw_hm_layout(rows, B, S, h):
+    """(M, d) rows in the head-major layout the kernel stores: (d // h, B, S, h)."""
+    M, d = rows.shape
+    return rows.view(B, S, d // h, h).permute(2, 0, 1, 3).contiguous()
+
+
+def rw_hm_rows(y):
+    """A head-major output (heads, B, S, h) back in (row, column) order, as the tests compare it."""
+    heads, B, S, h = y.shape
+    return y.permute(1, 2, 0, 3).reshape(B * S, heads * h)
+
+
+# Conv-row mode (family 5): (name, (KH, Cin, Cout, stride (h, w), pad_h, Hin, Win), flags, opts, config,
+# ng).  Two images of Hout = 4 rows of Wout = 33 pixels: M = 264 rows, 9 tiles of 32 or 17 of 16, so tiles
+# straddle output rows (33 is odd) and the image boundary (row 132 sits inside a tile of either height).
+#   strided 1x1: Cin = 256, stride 2, input 7 x 65;
+#   the tap-folded stem form, 7 x 1 taps of 24 channels (K = 168 of the kernel's 256: the chunks past K
+#     read zeros), vertical stride 2 / pad 3 (flag 32 keeps the dedicated stem kernel off it);
+#   3 x 1 taps of 64 channels with pad 3 over 3 input rows: output rows 0 and 3 read padding only.
+RW_CONV_CASES = [
+    ('ds 256->256', (1, 256, 256, (2, 2), 0, 7, 65), 0, '', (8, 4, 32, 4, 4, 2), 1),
+    ('ds 256->512', (1, 256, 512, (2, 2), 0, 7, 65), 0, 's b relu', (8, 4, 32, 4, 4, 2), 2),
+    ('ds 256->256 16-row', (1, 256, 256, (2, 2), 0, 7, 65), RW_F16ROW, 's b', (8, 4, 16, 4, 4, 2), 1),
+    ('ds 256->512 16-row', (1, 256, 512, (2, 2), 0, 7, 65), RW_F16ROW, '', (8, 4, 16, 4, 4, 2), 2),
+    ('stem 7x1 N=64', (7, 24, 64, (2, 1), 3, 8, 33), RW_NOSTEM, 's b relu', (8, 2, 32, 4, 4, 2), 1),
+    ('stem 7x1 N=128 16-row', (7, 24, 128, (2, 1), 3, 8, 33), RW_NOSTEM | RW_F16ROW, '', (8, 2, 16, 4, 4, 2), 1),
+    ('taps 3x1 N=128', (3, 64, 128, (2, 1), 3, 3, 33), RW_NOSTEM, 's b', (8, 2, 32, 4, 4, 2), 1),
+    ('taps 3x1 N=64 16-row', (3, 64, 64, (2, 1), 3, 3, 33), RW_NOSTEM | RW_F16ROW, 'b relu', (8, 2, 16, 4, 4, 2), 1),
+]
+RW_CONV_BATCH, RW_CONV_ROWS = 2, 264
+
+
+@functools.lru_cache(maxsize=None)
+def rw_conv_inputs(name, dtype, cls):
+    """(x NHWC, w (Cout, KH, 1, Cin), scale, bias, acc64, |x| * |w|) of a conv-row case."""
+    geo, opts = next((c[1], c[3]) for c in RW_CONV_CASES if c[0] == name)
+    KH, Cin, Cout, stride, pad_h, Hin, Win = geo
+    K = KH * Cin
+    g = torch.Generator().manual_seed(_rw_seed(name, cls))
+    if cls == 'exact':
+        x, w = exact_x((RW_CONV_BATCH, Hin, Win, Cin), g), exact_w((Cout, KH, 1, Cin), K, g)
+        scale, bias = exact_epilogue(Cout, g)
+    else:
+        x, w = generic_operands((RW_CONV_BATCH, Hin, Win, Cin), (Cout, KH, 1, Cin), K, dtype, g)
+        scale, bias = generic_epilogue(Cout, g)
+    o = opts.split()
+    return (x, w, scale if 's' in o else None, bias if 'b' in o else None, conv64(x, w, stride, (pad_h, 0)),
+            conv64(x.abs(), w.abs(), stride, (pad_h, 0)))

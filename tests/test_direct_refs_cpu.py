@@ -703,3 +703,220 @@ def test_gemm_table_covers_the_k_cycle():
             assert all(k % 8 == 0 and k <= 392 for k in ks)
     # the 15-block grid of the XCD remap (15 = 8 + 7: both branches of the bijection)
     assert all(-(-(3 * bm - 1) // bm) * -(-(5 * bn - 4) // bn) == 15 for bm, bn in R.GEMM_TILES)
+
+
+# ======================================= resident-weight GEMM (csrc/gemm_rw.hip)
+# The configuration columns of R.RW_CASES (KC, NT, BMR, NS, NW, OCC, ng) state what the launchers are
+# read to choose; without a GPU they can be cross-checked only as far as they are literal -- against
+# each other and against the shapes -- which is what test_rw_tables_are_consistent does.  The rest
+# checks the references and the acceptance of tests/test_gemm_rw_direct_gpu.py.
+_RW_PLAIN = [c for c in R.RW_CASES if 'LN' not in R.rw_opts(c)]
+_RW_LN = [c for c in R.RW_CASES if 'LN' in R.rw_opts(c)]
+_rw_id = lambda c: c[0].replace(' ', '_')          # noqa: E731
+
+
+def _rw_f32(inp, cdt, odt, x=None, w=None, res=None, mask=None):
+    """The case in torch's own f32: (x [+ x2] rounded to cdt) @ w^T, the f32 epilogue, LayerNorm, the row
+    mask, one output rounding.  x / w / res / mask override the case's operands (emulated defects)."""
+    x = inp['x'] if x is None else x
+    w = inp['w'] if w is None else w
+    res = inp['res'] if res is None else res
+    mask = inp['mask'] if mask is None else mask
+    if inp['x2'] is not None:
+        x = (x + inp['x2'][:, :x.shape[1]]).to(cdt).float()
+    v = x @ w.T
+    if inp['scale'] is not None:
+        v = v * inp['scale']
+    if inp['bias'] is not None:
+        v = v + inp['bias']
+    if res is not None:
+        v = v + res
+    if inp['relu']:
+        v = torch.relu(v)
+    if inp['ln'] is not None:
+        v = F.layer_norm(v, (v.shape[-1],), inp['ln'][0], inp['ln'][1], 1e-5)
+    assert v.dtype == torch.float32
+    return R.rw_masked(v, mask).to(odt)
+
+
+def _rw_accepts(got, inp, case, cls):
+    """The GPU module's acceptance of an (M, N) output."""
+    Kd, odt = case[1], case[6]
+    if inp['ln'] is not None:
+        return R.rw_ln_check(got, inp, odt)[1] == 0
+    if cls == 'exact':
+        return bool((got == R.rw_masked(inp['pre'], inp['mask']).to(odt)).all())
+    return R.rw_generic_ratio(got, inp, Kd, odt) <= 1.0
+
+
+def test_rw_tables_are_consistent():
+    names = [c[0] for c in R.RW_CASES]
+    assert len(set(names)) == len(names)
+    combos = {}
+    layouts = set()
+    for name, K, N, flags, opts, cdt, odt, (KC, NT, BMR, NS, NW, OCC), ng in R.RW_CASES:
+        o = R.rw_opts((name, K, N, flags, opts))
+        GW = NW * NT * 16
+        assert KC * 32 == K and K in (64, 128, 256, 512, 288) and N % 8 == 0, name
+        assert ng == -(-N // GW), name
+        assert BMR in (16, 32) and R.rw_rows(BMR) == {16: 267, 32: 539}[BMR] and 2 <= NS <= 4, name
+        assert R.rw_rows(BMR) > 256 and -(-R.rw_rows(BMR) // BMR) == R.RW_TILES and R.rw_rows(BMR) % BMR, name
+        assert (NW, OCC) in ((4, 2), (8, 1), (9, 1), (6, 1)), name
+        # what the kernel accepts: a residual is of a 16-bit output type; LayerNorm rows fit one group
+        assert 'R' not in o or odt != torch.float32, name
+        assert 'LN' not in o or (ng == 1 and N <= (288 if K == 288 else 256) and 'relu' not in o), name
+        assert 'A2' not in o or not (o & {'R', 'LN'}), name
+        assert K != 512 or (N <= 256 and not (o & {'R', 'LN', 'A2'})), name
+        assert (K == 64) <= (BMR == 32), name
+        combos.setdefault(K, set()).add((cdt, odt if odt != torch.float32 else 'f32'))
+        layouts |= {d for d in (0, -56, 8) if N % GW == d % GW} | ({'ld'} if 'ld' in o else set())
+    B_, H_ = torch.bfloat16, torch.float16
+    for K, seen in combos.items():
+        assert {(B_, B_), (H_, H_), (B_, H_)} <= seen and any(t[1] == 'f32' for t in seen), (K, seen)
+    assert layouts == {0, -56, 8, 'ld'}
+    assert R.RW_CAPS == {0: 17, 1: 1, 3: 3, 16: 16}
+    # cap 3: 6 / 6 / 5 tiles, the ragged tile (16) walked last by workgroup 1; cap 16: 2 tiles on workgroup 0
+    assert [len(range(b, 17, 3)) for b in range(3)] == [6, 6, 5] and 16 in range(1, 17, 3)
+    assert [len(range(b, 17, 16)) for b in range(16)] == [2] + [1] * 15
+    for bmr in (16, 32):
+        M = R.rw_rows(bmr)
+        m = R.rw_mask(M, bmr)
+        assert m[0] and m[M - 1] and m[6 * bmr:7 * bmr].all() and not m[5 * bmr:6 * bmr].any() and not m[7 * bmr]
+        assert m[2 * bmr] and not m[2 * bmr - 1] and not m[2 * bmr + 1]         # a tile's first row
+        assert m[4 * bmr - 1] and not m[4 * bmr - 2] and not m[4 * bmr]          # a tile's last row
+        assert R.rw_hm_batch(bmr)[0] * R.rw_hm_batch(bmr)[1] == M
+    for name, (KH, Cin, Cout, stride, pad_h, Hin, Win), flags, opts, cfg, ng in R.RW_CONV_CASES:
+        Ho, Wo = R.out_size(Hin, Win, KH, 1, stride, (pad_h, 0))
+        assert (Ho, Wo) == (4, 33) and R.RW_CONV_BATCH * Ho * Wo == R.RW_CONV_ROWS >= 256 and KH * Cin <= 256, name
+        assert Wo >= cfg[2] and Wo % cfg[2] and (Ho * Wo) % cfg[2], name      # tiles straddle rows and the image
+        assert ng == -(-Cout // (cfg[4] * cfg[1] * 16)) and cfg[0] == 8, name
+    exp = R.rw_expected((8, 4, 16, 4, 8, 1), 2, True, False, False, torch.bfloat16, 3)
+    assert tuple(exp) == R.RW_CONFIG_FIELDS and exp['P'] == 3 and exp['n_mtiles'] == 17 and exp['out_bytes'] == 2
+
+
+def test_rw_config_fields_match_the_wrapper():
+    from kinet_amd import kernels
+    assert kernels.GEMM_RW_CONFIG_FIELDS == R.RW_CONFIG_FIELDS
+
+
+@pytest.mark.parametrize('case', _RW_PLAIN, ids=_rw_id)
+def test_rw_exact_cases_are_exact_with_headroom(case):
+    """Every exact-class row: operands on their grids (x + x2 exact in the operand type), torch's f32
+    evaluation equals the f64 one, and the output type resolves one dropped product everywhere."""
+    name, K, N, _, _, cdt, odt, cfg, _ = case
+    inp = R.rw_inputs(case, 'exact')
+    a = inp['x'] if inp['x2'] is None else inp['x'] + inp['x2']
+    assert (a.to(cdt).float() == a).all() and (inp['w'].to(cdt).float() == inp['w']).all()
+    assert ((a * 2) == (a * 2).round()).all() and a.abs().max() <= (1 if inp['x2'] is None else 2)
+    assert ((a @ inp['w'].T).double() == inp['acc']).all() and inp['acc'].abs().max() < 2 ** 9
+    assert (_f32_chunked(a, inp['w'], 32, True).double() == inp['acc']).all()
+    if inp['res'] is not None:
+        assert (inp['res'].to(odt).float() == inp['res']).all()
+    want = R.rw_masked(inp['pre'], inp['mask'])
+    assert R.exact_headroom(inp['pre'], inp['scale'], odt).all(), name
+    got = _rw_f32(inp, cdt, odt)
+    assert (got == want.to(odt)).all() and _rw_accepts(got, inp, case, 'exact')
+    less = R.epilogue64(inp['acc'] - 1.0 / 16, inp['scale'], inp['bias'], inp['res'], False)[0]
+    assert (less.to(odt) != R.epilogue64(inp['acc'], inp['scale'], inp['bias'], inp['res'], False)[0].to(odt)).all()
+
+
+@pytest.mark.parametrize('case', R.RW_CASES, ids=_rw_id)
+def test_rw_generic_and_ln_bounds_hold_for_torch_f32(case):
+    cdt, odt = case[5], case[6]
+    if 'LN' in R.rw_opts(case):
+        for offset in (100.0, 0.0):
+            inp = R.rw_inputs(case, 'exact', offset)
+            assert _rw_accepts(_rw_f32(inp, cdt, odt), inp, case, 'exact')
+    else:
+        inp = R.rw_inputs(case, 'generic')
+        got = _rw_f32(inp, cdt, odt)
+        print(f'{case[0]}: torch f32 worst err / bound {R.rw_generic_ratio(got, inp, case[1], odt):.3f}')
+        assert _rw_accepts(got, inp, case, 'generic')
+
+
+_RW_DEFECT_CASES = [c for c in R.RW_CASES if c[0] in (
+    'k64 R', 'k64 R+LN', 'k128 R 8-wave', 'k128 LN', 'k256 plain ld', 'k256 R 8-wave', 'k256 R+LN', 'k256 A2',
+    'k512 8-wave', 'k512 N=72', 'k288 R+LN 9-wave', 'k288 LN 6-wave', 'k288 R', 'k288 N=1728 4-wave', 'k288 A2 8-wave N=328')]
+
+
+@pytest.mark.parametrize('case,cls', [(c, cls) for c in _RW_DEFECT_CASES for cls in ('exact', 'generic')
+                                      if cls == 'exact' or 'LN' not in R.rw_opts(c)],
+                         ids=lambda v: _rw_id(v) if isinstance(v, tuple) else v)
+def test_rw_acceptance_rejects_emulated_defects(case, cls):
+    """Defects of the kind this kernel can have, emulated on torch's f32 evaluation: each leaves the GPU
+    module's acceptance (in both operand classes; LayerNorm rows have one class, at offset 0)."""
+    name, K, N, _, _, cdt, odt, (KC, NT, BMR, NS, NW, OCC), _ = case
+    o = R.rw_opts(case)
+    inp = R.rw_inputs(case, cls)
+    M = R.rw_rows(BMR)
+    good = _rw_f32(inp, cdt, odt)
+    assert _rw_accepts(good, inp, case, cls)
+    # the last 8-element K chunk dropped
+    assert not _rw_accepts(_rw_f32(inp, cdt, odt, x=inp['x'][:, :K - 8], w=inp['w'][:, :K - 8]), inp, case, cls)
+    # a tile's rows computed from the tile NS earlier (a ring slot read before its DMA landed)
+    t = NS + 1
+    stale = good.clone()
+    stale[t * BMR:(t + 1) * BMR] = _rw_f32(inp, cdt, odt, mask=torch.zeros(M, dtype=torch.bool))[(t - NS) * BMR:(t - NS + 1) * BMR]
+    assert not _rw_accepts(stale, inp, case, cls)
+    # ... and only that tile's A rows stale, residual and mask in place
+    xs = inp['x'].clone()
+    xs[t * BMR:(t + 1) * BMR] = inp['x'][(t - NS) * BMR:(t - NS + 1) * BMR]
+    assert not _rw_accepts(_rw_f32(inp, cdt, odt, x=xs), inp, case, cls)
+    if 'R' in o:        # the residual read one 8-column chunk off
+        assert not _rw_accepts(_rw_f32(inp, cdt, odt, res=torch.roll(inp['res'], 8, 1)), inp, case, cls)
+    if 'mask' in o:     # a mask byte applied to the neighbouring row
+        assert not _rw_accepts(_rw_f32(inp, cdt, odt, mask=torch.roll(inp['mask'], 1)), inp, case, cls)
+
+
+@pytest.mark.parametrize('case', R.RW_HM_CASES, ids=_rw_id)
+def test_rw_headmajor_acceptance_rejects_a_plane_offset(case):
+    """The head-major cases: exact with headroom, and planes stored one head off are not accepted."""
+    name, d, hd, _, cdt, odt, cfg, _ = case
+    M = R.rw_rows(cfg[2])
+    x, w, acc, _ = R.gemm_case(M, d, d, cdt, 'exact')
+    bias = R.exact_epilogue(d, torch.Generator().manual_seed(d + cfg[2] + len(name)))[1]
+    pre = R.epilogue64(acc, None, bias)[0]
+    assert R.exact_headroom(pre, None, odt).all()
+    want = R.rw_masked(pre, R.rw_mask(M, cfg[2])).to(odt)
+    h = 36 if hd == 'split' else hd
+    B, S = R.rw_hm_batch(cfg[2])
+    stored = R.rw_hm_layout(want, B, S, h)                 # (d // h, B, S, h), as the kernel writes it
+    assert torch.equal(R.rw_hm_rows(stored), want)
+
+    def rejected(y):    # the GPU test's acceptance: every element of the permuted-back output equal
+        return float((R.rw_hm_rows(y) != want).any(1).float().mean())
+    assert rejected(torch.roll(stored, 1, 0)) > 0.9         # every plane stored one head off
+    assert rejected(torch.roll(stored, 1, 2)) > 0.9         # ... one row off inside its plane
+    one = stored.clone()
+    one[3] = stored[2]                                      # one plane holding its neighbour's values
+    assert 0 < rejected(one) and (R.rw_hm_rows(one) != want).any(0).sum() == h
+    if hd == 'split':   # the two planes of a 36-column head: only the 4-column tail planes one head off
+        tail = stored.clone()
+        tail[..., 32:] = torch.roll(stored[..., 32:], 1, 0)
+        assert rejected(tail) > 0.9 and not (R.rw_hm_rows(tail) != want).view(M, d // h, h)[..., :32].any()
+
+
+@pytest.mark.parametrize('name', [c[0] for c in R.RW_CONV_CASES])
+def test_rw_conv_cases_exact_and_bounded(name):
+    geo, opts = next((c[1], c[3]) for c in R.RW_CONV_CASES if c[0] == name)
+    KH, Cin, Cout, stride, pad_h, Hin, Win = geo
+    for dt in (torch.bfloat16, torch.float16):
+        x, w, scale, bias, acc, ap = R.rw_conv_inputs(name, dt, 'exact')
+        cols = R.unfold_nhwc(x, KH, 1, stride, (pad_h, 0))
+        assert ((cols @ w.reshape(Cout, -1).T).double() == acc).all()
+        pre, _ = R.epilogue64(acc, scale, bias, None, 'relu' in opts.split())
+        assert R.exact_headroom(R.epilogue64(acc, scale, bias)[0], scale, dt).all()
+        if KH == 3:
+            assert (acc.view(2, 4, 33, Cout)[:, [0, 3]] == 0).all() and (acc.view(2, 4, 33, Cout)[:, 1:3] != 0).any()
+        x, w, scale, bias, acc, ap = R.rw_conv_inputs(name, dt, 'generic')
+        pre, maj = R.epilogue64(acc, scale, bias, None, 'relu' in opts.split())
+        bound = R.gemm_generic_bound(ap, KH * Cin, maj, pre, dt, scale)
+        cols = R.unfold_nhwc(x, KH, 1, stride, (pad_h, 0))
+        v = cols @ w.reshape(Cout, -1).T
+        v = v if scale is None else v * scale
+        v = v if bias is None else v + bias
+        v = torch.relu(v) if 'relu' in opts.split() else v
+        assert ((v.to(dt).double() - pre).abs() <= bound).all()
+        # the rows of one output row taken from the row above (a wrong carry at the row's end) leave it
+        bad = torch.roll(v.view(2, 4, 33, Cout), 1, 1).reshape(-1, Cout)
+        assert ((bad.to(dt).double() - pre).abs() > bound).float().mean() > 0.25
