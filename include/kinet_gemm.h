@@ -203,6 +203,39 @@ int kinet_gemm_rw_last_config(int* out);
  * value -- a small problem can walk a wrapping ring this way.  Returns the previous value. */
 int kinet_gemm_rw_grid_cap(int max_p);
 
+/* How a resident-weight launch is chosen.  One host-side planner (csrc/gemm_rw_plan.h) holds every
+ * eligibility rule and variant heuristic of gemm_rw_kernel: from the described problem, the calling
+ * thread's flags and grid cap and the device's compute-unit count it yields "not eligible" (another
+ * kernel family serves the call) or one entry of the one table of kernel instantiations plus its
+ * grid.  The launcher reads kernel, workgroup size, grid and the kinet_gemm_rw_last_config record from
+ * that entry alone.
+ *
+ * kinet_gemm_rw_plan: the planner's answer for a described problem, without touching a device (no
+ * reference counterpart; works on a machine without a GPU).  problem[KINET_RWP_FIELDS], indexed by the
+ * enum below: kind 0 = kinet_gemm(_ex) / kinet_gemm_headmajor* (once the call reaches the
+ * resident-weight dispatch: no split-K, flag 4 clear), 1 = kinet_conv2d(_ex) of a convolution that is
+ * not a plain GEMM (the direct 3x3 and stem kernels are asked before it), 2 = kinet_msda_sample_records
+ * (N = heads * 48, output f16).  Dtypes are kinet_dtypes; RESIDUAL / LN / A2 / ROW_MASK say whether the
+ * operand is given, *_ALIGNED whether its pointer is 16-byte aligned; HM_* are rows_per_batch, head_dim,
+ * split_cols and tail_dim of a head-major store (0 otherwise); CIN .. WOUT the convolution geometry
+ * (STRIDE / PAD vertical).  cus: the compute-unit count to plan for (256 on MI355X).  Reads the calling
+ * thread's kinet_gemm_set_flags and kinet_gemm_rw_grid_cap like a real call.  *eligible = 0 / 1;
+ * config[0 .. 14] = the record kinet_gemm_rw_last_config would return after the launch (zeros if not
+ * eligible). */
+enum {
+    KINET_RWP_KIND, KINET_RWP_M, KINET_RWP_N, KINET_RWP_K, KINET_RWP_IN_DTYPE, KINET_RWP_OUT_DTYPE, KINET_RWP_RESIDUAL,
+    KINET_RWP_LN, KINET_RWP_A2, KINET_RWP_LDC, KINET_RWP_LDR, KINET_RWP_C_ALIGNED, KINET_RWP_R_ALIGNED,
+    KINET_RWP_A2_ALIGNED, KINET_RWP_HM_ROWS, KINET_RWP_HM_D, KINET_RWP_HM_SPLIT, KINET_RWP_HM_D2, KINET_RWP_CIN,
+    KINET_RWP_KW, KINET_RWP_STRIDE, KINET_RWP_STRIDE_W, KINET_RWP_PAD, KINET_RWP_PAD_W, KINET_RWP_WIN, KINET_RWP_WOUT,
+    KINET_RWP_ROW_MASK, KINET_RWP_FIELDS
+};
+int kinet_gemm_rw_plan(const int* problem, int cus, int* eligible, int* config);
+
+/* Smallest a2_rows (rows of an A2 shared by every frame of the batch) kinet_gemm_headmajor_ex and
+ * kinet_msda_sample_records accept: the tallest row tile of a resident-weight variant with an A2,
+ * whose addressing lets a tile wrap around the A2 rows at most once (32). */
+int kinet_gemm_rw_min_a2_rows(void);
+
 /* C / R alignment: the fused epilogue moves 4 output elements per access whenever ldc (and ldr)
  * are multiples of 4, so kinet_gemm(_ex), kinet_gemm_headmajor* and kinet_conv2d(_ex) return
  * KINET_ERR_ARG for a C (or R) that is not aligned to 4 output elements in that case; other

@@ -41,6 +41,8 @@ _SIGS = {
     'kinet_gemm_rw_last_config': [P],
     'kinet_gemm_rw_grid_cap': [I],
     'kinet_gemm_plan': [I] * 11 + [P, P],
+    'kinet_gemm_rw_plan': [P, I, P, P],
+    'kinet_gemm_rw_min_a2_rows': [],
     'kinet_gemm_ksplit': [I] * 4,
     'kinet_gemm_headmajor': [P, P, P] + [I] * 7 + [P, P, I, I, P],
     'kinet_gemm_headmajor_ex': [P, P, P, P] + [I] * 7 + [P, P, I, I, I, P],

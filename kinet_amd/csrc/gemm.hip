@@ -750,7 +750,7 @@ extern "C" int kinet_gemm_headmajor_ex(const void* A, const void* A2, const void
                                        int lda, int ldb, int in_dtype, int out_dtype, const float* bias,
                                        const uint8_t* row_mask, int rows_per_batch, int head_dim, int a2_rows,
                                        kinet_stream_t stream) {
-    KINET_CHECK_ARG(a2_rows == 0 || (A2 != nullptr && a2_rows >= 32 && M % a2_rows == 0),
+    KINET_CHECK_ARG(a2_rows == 0 || (A2 != nullptr && a2_rows >= kRwMinA2Rows && M % a2_rows == 0),
                     "gemm_headmajor: a2_rows must be 0 or >= 32 dividing M (got %d)", a2_rows);
     KINET_CHECK_ARG(out_dtype == in_dtype || (in_dtype == KINET_BF16 && out_dtype == KINET_F16),
                     "gemm_headmajor: out_dtype must equal in_dtype (or f16 from bf16)");
@@ -841,7 +841,6 @@ extern "C" int kinet_set_solo_launch(int on) {
 extern "C" int kinet_gemm_set_flags(int flags) {
     const int old = kinet_gemm_flags;
     kinet_gemm_flags = flags;
-    kinet::rw_min_m = (flags & 8) ? 256 : 4096;
     return old;
 }
 

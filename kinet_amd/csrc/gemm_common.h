@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_rw_plan.h"
 
 namespace kinet {
 
@@ -65,10 +66,8 @@ bool launch_stem_conv(const GemmArgs& a, int dtype, hipStream_t stream);
 // conv3x3.hip: the direct 3x3 stride-1 64 -> 64 channel convolution (ResNet layer-1 conv2),
 // weights resident in VGPRs, input halo tiles in LDS; false = not that geometry
 bool launch_conv3x3_c64(const GemmArgs& a, int dtype, hipStream_t stream);
-extern thread_local int rw_min_m;
 // gemm_rw.hip: the calling thread's last resident-weight launch (kinet_gemm_rw_last_config, written by
-// launch_cfg); gemm.hip's record_kernel zeroes it when another family serves a call
-constexpr int RW_CFG_FIELDS = 15;
+// launch_planned); gemm.hip's record_kernel zeroes it when another family serves a call
 extern thread_local int rw_last_cfg[RW_CFG_FIELDS];
 extern thread_local int kinet_gemm_flags;   // gemm.hip (diagnostic selection flags; 128 = the read-time-split KINET_F32_X3 TN kernel)
 

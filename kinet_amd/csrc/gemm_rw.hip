@@ -26,47 +26,28 @@
 //    the newest DMA, so outstanding stores never hold up the ring's counted wait.
 #include <hip/hip_runtime.h>
 
+#include <utility>
+
 #include "../../include/kinet_gemm.h"
 #include "../../include/kinet_msda.h"
 #include "common.h"
 #include "gemm_common.h"
+#include "gemm_rw_plan.h"
 
 namespace kinet {
 namespace {
 
-// NW waves per workgroup (4, or 6 for the d = 288 LayerNorm rows: 6 x 48 = 288 columns);
-// rows of K = 32*KC 16-bit elements: a power-of-two number of 16-byte chunks, or a multiple of
-// 4 (K = 288: 36 chunks).  A tile region whose bytes are not whole DMA rounds (NW*64 lanes x
-// 16 B) is padded to whole rounds; the padding chunks read zeros (out of range) and nothing
-// reads them back.
+// The LDS geometry of an instantiation (rw_lds, gemm_rw_plan.h) as compile-time constants, plus the
+// swizzles
 template <int KC, int NT, int BMR, int NS, bool HAS_R, bool LN, bool HAS_A2, bool PREP = false, int NW = 4>
 struct RwCfg {
-    static constexpr int NTHR = NW * 64;
-    static constexpr int OPB = NTHR * 16;                   // bytes per DMA round
-    static constexpr int ROW = KC * 64;                     // A row bytes (K = 32*KC, 16-bit)
-    static constexpr int CPR = ROW / 16;                    // 16-byte chunks per A row
-    static constexpr bool POW2 = (CPR & (CPR - 1)) == 0;
-    static constexpr int SWM = (CPR < 16 ? CPR : 16) - 1;   // source-side XOR swizzle mask
-    static constexpr int GW = NW * NT * 16;                 // columns per workgroup
-    static constexpr int A_BYTES = BMR * ROW;
-    static constexpr int A_OPS = (A_BYTES + OPB - 1) / OPB;   // DMA instructions per thread per tile
-    static constexpr int A_SPAN = A_OPS * OPB;
-    static constexpr int A2_BYTES = HAS_A2 ? A_SPAN : 0;    // second A operand (A + A2)
-    static constexpr int R_ROW = GW * 2;
-    static constexpr int R_CPR = R_ROW / 16;
-    static constexpr bool R_POW2 = (R_CPR & (R_CPR - 1)) == 0;
-    static constexpr int R_SWM = (R_CPR < 16 ? R_CPR : 16) - 1;
-    static constexpr int R_OPS = HAS_R ? (BMR * R_ROW + OPB - 1) / OPB : 0;
-    static constexpr int R_BYTES = R_OPS * OPB;
-    static constexpr int R_OFF = A_SPAN + A2_BYTES;
-    static constexpr int MASK_OFF = R_OFF + R_BYTES;
-    static constexpr int REF_OFF = MASK_OFF + 1024;         // PREP: the tile's reference points
-    static constexpr int REF_OPS = PREP ? BMR / 16 : 0;     // 1 KiB DMAs: BMR rows x 4 levels x <= 16 B
-    static constexpr int STAGE = REF_OFF + REF_OPS * 1024;  // + one DMA of row-mask bytes (+ refs)
-    static constexpr int PAR = 4 * GW * 4;                  // scale, bias, gamma, beta (f32)
-    static constexpr int LNS = LN ? 2 * BMR * NW * 4 : 0;   // [2][BMR][NW waves] partial sums
-    static constexpr int BYTES = PAR + LNS + NS * STAGE;
-    static constexpr int D = A_OPS * (HAS_A2 ? 2 : 1) + R_OPS + 1 + REF_OPS;
+    static constexpr RwLds G = rw_lds(RwVariant{KC, NT, BMR, NW, 0, HAS_R, LN, HAS_A2, false, PREP, 0}, NS);
+    static constexpr int NTHR = G.NTHR, ROW = G.ROW, CPR = G.CPR, SWM = G.SWM, GW = G.GW;
+    static constexpr int A_OPS = G.A_OPS, A_SPAN = G.A_SPAN;
+    static constexpr int R_ROW = G.R_ROW, R_CPR = G.R_CPR, R_SWM = G.R_SWM, R_OPS = G.R_OPS, R_OFF = G.R_OFF;
+    static constexpr int MASK_OFF = G.MASK_OFF, REF_OFF = G.REF_OFF, REF_OPS = G.REF_OPS, STAGE = G.STAGE;
+    static constexpr int PAR = G.PAR, LNS = G.LNS, BYTES = G.BYTES, D = G.D;
+    static constexpr bool POW2 = G.POW2, R_POW2 = G.R_POW2;
     // LDS position of 16-byte chunk c of tile row r (an involution: the DMA fills position c
     // with source chunk sw(r, c), a reader of logical chunk q reads position sw(r, q)).  Rows of
     // 36 chunks (K = 288, 576 B = 144 banks: rows r and r + 4 share banks) swap chunks within
@@ -74,11 +55,6 @@ struct RwCfg {
     // 4-bank groups
     __device__ static constexpr int sw(int r, int c) { return POW2 ? c ^ (r & SWM) : c ^ ((r >> 2) & 3); }
     __device__ static constexpr int rsw(int r, int c) { return R_POW2 ? c ^ (r & R_SWM) : c ^ ((r >> 2) & 3); }
-    static_assert(!PREP || (NT == 3 && (NW == 4 || NW == 8) && (BMR == 16 || BMR == 32) && !HAS_R && !LN),
-                  "sampling records: one head per wave (12 columns per lane), 16- or 32-row tiles");
-    static_assert(POW2 || CPR % 4 == 0, "A rows: power-of-two or multiple-of-4 chunks");
-    static_assert(!HAS_R || R_POW2 || R_CPR % 4 == 0, "residual rows: power-of-two or multiple-of-4 chunks");
-    static_assert(BMR / 16 <= 64, "mask DMA lanes");
 };
 
 template <int N>
@@ -713,240 +689,86 @@ thread_local int rw_grid_cap = 0;                   // kinet_gemm_rw_grid_cap (0
 
 namespace {
 
-template <typename T, typename TO, int KC, int BMR, int NS, bool HAS_R, bool LN, bool HAS_A2 = false, int NT = 4,
-          bool CR = false, bool PREP = false, int OCC = 2, int NW = 4>
-void launch_cfg(const GemmArgs& a, hipStream_t stream) {
-    constexpr int GW = NW * NT * 16;
-    const int n_mtiles = (a.M + BMR - 1) / BMR;
-    const int ng = (a.N + GW - 1) / GW;
-    // 2 resident workgroups per CU over all groups: never more than the 512 slots (a second
-    // round of workgroups would double the launch), and a multiple of 8 so the column groups
-    // of one row tile land on one XCD (linear id bx + y*P) and share its L2 copy of the tile
-    // (OCC resident workgroups per CU: 256 * OCC slots)
-    const int slots = 256 * OCC;
-    int P = slots / ng >= 8 ? slots / ng / 8 * 8 : slots / ng;
-    if (P > n_mtiles) P = n_mtiles;
-    // diagnostics (host side, per calling thread): kinet_gemm_rw_grid_cap bounds P -- the kernel is
-    // persistent, so P only decides which workgroup walks which row tiles; kinet_gemm_rw_last_config
-    // reads the record back
-    if (rw_grid_cap > 0) P = P > rw_grid_cap ? rw_grid_cap : (P < 1 ? 1 : P);
-    const int cfg[RW_CFG_FIELDS] = {KC, NT, BMR, NS, NW, OCC, HAS_R, LN, HAS_A2, CR, PREP, (int)sizeof(TO), P, ng, n_mtiles};
-    for (int i = 0; i < RW_CFG_FIELDS; ++i) rw_last_cfg[i] = cfg[i];
-    dim3 grid(P, ng), block(NW * 64);
-    hipLaunchKernelGGL((gemm_rw_kernel<T, TO, KC, NT, BMR, NS, HAS_R, LN, HAS_A2, CR, PREP, OCC, NW>), grid, block, 0,
-                       stream, a, n_mtiles);
-}
-
-// deepest DMA ring (<= 4 row tiles) that keeps the workgroup within 80 KiB of LDS (two per CU)
-template <int KC, int BMR, bool HAS_R, bool LN, bool HAS_A2, int NT = 4, bool PREP = false, int NW = 4,
-          int BUDGET = 80 * 1024>
-constexpr int ring_depth() {
-    constexpr int base = RwCfg<KC, NT, BMR, 1, HAS_R, LN, HAS_A2, PREP, NW>::BYTES -
-                         RwCfg<KC, NT, BMR, 1, HAS_R, LN, HAS_A2, PREP, NW>::STAGE;
-    constexpr int stage = RwCfg<KC, NT, BMR, 1, HAS_R, LN, HAS_A2, PREP, NW>::STAGE;
-    return (BUDGET - base) / stage >= 4 ? 4 : (BUDGET - base) / stage;
-}
-
-// K = 288 (d = 288: configs 3-5): 16-row tiles, 12 columns per lane (NT = 3, 108 weight VGPRs;
-// 180-210 in all: two waves per SIMD).  LayerNorm rows (N <= 288) need the whole row in one
-// workgroup: 9 waves x 32 columns (NT = 2, 126-152 VGPRs; the 6-wave x 48-column group under
-// flag 4194304), one workgroup per CU with a ring of up to 4 tiles in 160 KiB; the other
-// epilogues take 4-wave 192-column groups, two per CU (a row tile is shared by its groups
-// through the XCD's L2, as at K = 256).
-template <typename T, typename TO, bool HAS_R, bool LN, bool HAS_A2, int NW, int NT = 3, int OCC = NW == 4 ? 2 : 1>
-void launch_288(const GemmArgs& a, hipStream_t stream) {
-    constexpr int NS = ring_depth<9, 16, HAS_R, LN, HAS_A2, NT, false, NW, 160 * 1024 / OCC>();
-    static_assert(NS >= 2, "LDS budget");
-    launch_cfg<T, TO, 9, 16, NS, HAS_R, LN, HAS_A2, NT, false, false, OCC, NW>(a, stream);
-}
-
-template <typename T, typename TO, int KC, bool HAS_R, bool LN, bool HAS_A2, int NT = 4>
-void launch_ring(const GemmArgs& a, hipStream_t stream) {
-    // 16-row tiles when a tile carries a second operand (residual / A2) or the LayerNorm
-    // epilogue (which needs them at K = 256 to stay in 256 VGPRs) or a K of 512+ (1-2 KiB
-    // rows): a 2-4 deep ring then fits; K = 64 rows (128 B) need 32-row tiles for whole 4 KiB
-    // DMA rounds
-    constexpr int BMR = (KC == 2 || (KC <= 8 && !HAS_R && !LN && !HAS_A2)) ? 32 : 16;
-    constexpr int NS = ring_depth<KC, BMR, HAS_R, LN, HAS_A2, NT>();
-    static_assert(NS >= 2, "LDS budget");
-    if constexpr (BMR == 32 && KC >= 4) {
-        // flag 131072 (tests): the same problem on 16-row tiles -- the 32-row tiles' two MFMA row
-        // tiles per wave (TMR = 2) must give the 16-row tiles' results bit for bit
-        if (kinet_gemm_flags & 131072) {
-            constexpr int NS16 = ring_depth<KC, 16, HAS_R, LN, HAS_A2, NT>();
-            launch_cfg<T, TO, KC, 16, NS16, HAS_R, LN, HAS_A2, NT>(a, stream);
-            return;
-        }
-    }
-    launch_cfg<T, TO, KC, BMR, NS, HAS_R, LN, HAS_A2, NT>(a, stream);
-}
-
-template <typename T, typename TO, int KC, int NT = 4>
-void launch_k(const GemmArgs& a, hipStream_t stream) {
-    const bool r = a.R != nullptr, ln = a.ln_g != nullptr;
-    if (a.A2 != nullptr) {
-        // the query + position-embedding projections (no residual / LayerNorm there)
-        if (r || ln) return;
-        launch_ring<T, TO, KC, false, false, true, NT>(a, stream);
-    } else if (r && ln) launch_ring<T, TO, KC, true, true, false, NT>(a, stream);
-    else if (r) {
-        // + residual with N > 256 (the stage-end conv3s, 128 -> 512 and 256 -> 1024): 8-wave
-        // 512-column groups, one workgroup per CU, so each row tile's x rows are fetched by half as
-        // many groups (one instead of two at N = 512); flag 268435456: the 4-wave 256-column groups
-        if constexpr (NT == 4 && KC <= 8) {
-            if (a.N > 256 && !(kinet_gemm_flags & 268435456)) {
-                constexpr int NS8 = ring_depth<KC, 16, true, false, false, 4, false, 8, 160 * 1024>();
-                launch_cfg<T, TO, KC, 16, NS8, true, false, false, 4, false, false, 1, 8>(a, stream);
-                return;
-            }
-        }
-        launch_ring<T, TO, KC, true, false, false, NT>(a, stream);
-    } else if (ln) launch_ring<T, TO, KC, false, true, false, NT>(a, stream);
-    // (plain epilogues keep the 4-wave groups: 8-wave 512-column groups ran config 2's six decoder
-    // value projections (N = 1536) slower, 669 vs 648 us, profiles/r06ar_wide_8wave_ab.txt)
-    else launch_ring<T, TO, KC, false, false, false, NT>(a, stream);
-}
-
-// K = 512 (the ResNet 1x1 convs into the layer-2 bottlenecks, input_proj of level 0): the
-// weight slice stays at 128 VGPRs per wave by narrowing the column group to 128 columns
-// (NT = 2) -- the host routes only N <= 256 without residual / LayerNorm / A2 here (at most
-// 2 column groups, which share each row tile through the XCD's L2)
 template <typename T, typename TO>
-void launch_t(const GemmArgs& a, hipStream_t stream) {
-    if (a.K == 288) {
-        const bool r = a.R != nullptr, ln = a.ln_g != nullptr;
-        if (a.A2 != nullptr) {
-            // x + pos rows (the d = 288 offsets / logits and value projections): one 8-wave group of
-            // up to 384 columns per row tile, so each tile's x + pos rows are read once -- as the
-            // records GEMM (kinet_msda_sample_records); flag 268435456: the 4-wave 192-column groups
-            if (a.N > 192 && a.N <= 384 && !(kinet_gemm_flags & 268435456)) launch_288<T, TO, false, false, true, 8, 3, 1>(a, stream);
-            else launch_288<T, TO, false, false, true, 4>(a, stream);
-            return;
-        }
-        // LayerNorm rows: 9 waves x 32 columns (one 288-column group; flag 4194304: the 6-wave x
-        // 48-column groups, A/B and tests); without LayerNorm 4-wave 192-column groups (one 9-wave
-        // group measured within noise, round 5: profiles/r05s_split_nine_waves.log)
-        if (r && ln) {
-            if (kinet_gemm_flags & 4194304) launch_288<T, TO, true, true, false, 6>(a, stream);
-            else launch_288<T, TO, true, true, false, 9, 2>(a, stream);
-        } else if (ln) {
-            if (kinet_gemm_flags & 4194304) launch_288<T, TO, false, true, false, 6>(a, stream);
-            else launch_288<T, TO, false, true, false, 9, 2>(a, stream);
-        } else if (r) {
-            launch_288<T, TO, true, false, false, 4>(a, stream);
-        } else if (a.N > 384 && !(kinet_gemm_flags & 268435456)) {
-            // N > 384 (the d = 288 decoder's six value projections in one launch, N = 1728): 8-wave
-            // 384-column groups, one workgroup per CU -- half as many groups fetch each row tile:
-            // 1048 -> 948 us in config 3 (profiles/r06ar_wide_8wave_ab.txt); at 192 < N <= 384 (the
-            // value projection's split planes) 89 vs 91 us, bench within noise: not taken (r06at)
-            launch_288<T, TO, false, false, false, 8, 3, 1>(a, stream);
-        } else {
-            launch_288<T, TO, false, false, false, 4>(a, stream);
-        }
-        return;
+constexpr int type_pair = sizeof(TO) == 4 ? (std::is_same<T, bf16_t>::value ? RWT_BF16_F32 : RWT_F16_F32)
+                          : std::is_same<T, TO>::value ? (std::is_same<T, bf16_t>::value ? RWT_BF16_BF16 : RWT_F16_F16)
+                                                       : RWT_BF16_F16;
+
+// Launch entry I of kRwVariants (gemm_rw_plan.h) for one type pair if `variant` names it.  These are
+// the only launches of gemm_rw_kernel, so the table is the list of its instantiations.
+template <typename T, typename TO, int I>
+void launch_entry(int variant, dim3 grid, hipStream_t stream, const GemmArgs& a, int n_mtiles) {
+    constexpr RwVariant v = kRwVariants[I];
+    if constexpr ((v.types & type_pair<T, TO>) != 0) {
+        if (variant != I) return;
+        hipLaunchKernelGGL((gemm_rw_kernel<T, TO, v.kc, v.nt, v.bmr, rw_ring_depth(v), v.has_r, v.ln, v.has_a2, v.cr, v.prep,
+                                           v.occ, v.nw>),
+                           grid, dim3(v.threads()), 0, stream, a, n_mtiles);
     }
-    if (a.K == 64) launch_k<T, TO, 2>(a, stream);
-    else if (a.K == 128) launch_k<T, TO, 4>(a, stream);
-    else if (a.K == 256) launch_k<T, TO, 8>(a, stream);
-    else if (a.N > 128 && a.N <= 256 && !(kinet_gemm_flags & 268435456)) {
-        // K == 512, N == 256 (config 2's level-0 input projection, 512 -> 256): one 8-wave
-        // 256-column group per row tile, one workgroup per CU, so each tile's 1 KiB rows are read
-        // once (the two 4-wave 128-column groups fetched 2x the operand, profiles/pmc_traffic.json)
-        constexpr int NS = ring_depth<16, 16, false, false, false, 2, false, 8, 160 * 1024>();
-        launch_cfg<T, TO, 16, 16, NS, false, false, false, 2, false, false, 1, 8>(a, stream);
-    } else launch_ring<T, TO, 16, false, false, false, 2>(a, stream);   // K == 512
+}
+template <typename T, typename TO, int... I>
+void launch_variant(int variant, dim3 grid, hipStream_t stream, const GemmArgs& a, int n_mtiles,
+                    std::integer_sequence<int, I...>) {
+    (launch_entry<T, TO, I>(variant, grid, stream, a, n_mtiles), ...);
+}
+
+// Plan the problem (gemm_rw_plan.h: every eligibility rule and variant heuristic lives there) and
+// run the planned launch: kernel, block, grid and the record all come from its one table entry.
+// false = not eligible, nothing launched.
+bool launch_planned(RwProblem p, const GemmArgs& a, hipStream_t stream) {
+    p.flags = kinet_gemm_flags;
+    p.cap = rw_grid_cap;
+    p.cus = cu_count();
+    RwPlan plan;
+    if (!rw_plan(p, plan)) return false;
+    GemmArgs ac = a;
+    ac.c_bytes = plan.c_bytes;
+    ac.hm_tr = plan.hm_tr;
+    rw_config_record(plan, p.out_dtype, rw_last_cfg);
+    const dim3 grid(plan.P, plan.ng);
+    constexpr std::make_integer_sequence<int, kNumRwVariants> all{};
+    switch (rw_type_pair(p.in_dtype, p.out_dtype)) {   // (one of these: rw_plan checked the entry's mask)
+    case RWT_BF16_BF16: launch_variant<bf16_t, bf16_t>(plan.variant, grid, stream, ac, plan.n_mtiles, all); break;
+    case RWT_BF16_F16: launch_variant<bf16_t, f16_t>(plan.variant, grid, stream, ac, plan.n_mtiles, all); break;
+    case RWT_BF16_F32: launch_variant<bf16_t, float>(plan.variant, grid, stream, ac, plan.n_mtiles, all); break;
+    case RWT_F16_F16: launch_variant<f16_t, f16_t>(plan.variant, grid, stream, ac, plan.n_mtiles, all); break;
+    case RWT_F16_F32: launch_variant<f16_t, float>(plan.variant, grid, stream, ac, plan.n_mtiles, all); break;
+    }
+    return true;
 }
 
 bool al16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
-}  // namespace
+// the fields of a problem that its GemmArgs carry
+RwProblem rw_problem(int kind, const GemmArgs& a, int in_dtype, int out_dtype) {
+    RwProblem p{};
+    p.kind = kind;
+    p.M = a.M; p.N = a.N; p.K = a.K;
+    p.in_dtype = in_dtype; p.out_dtype = out_dtype;
+    p.r = a.R != nullptr; p.ln = a.ln_g != nullptr; p.a2 = a.A2 != nullptr;
+    p.ldc = a.ldc; p.ldr = a.ldr;
+    p.c_al16 = al16(a.C); p.r_al16 = al16(a.R); p.a2_al16 = al16(a.A2);
+    p.hm_rows = a.hm_rows; p.hm_d = a.hm_d; p.hm_split = a.hm_split; p.hm_d2 = a.hm_d2;
+    p.Cin = a.Cin; p.KW = a.KW; p.stride = a.stride; p.stride_w = a.stride_w; p.pad = a.pad; p.pad_w = a.pad_w;
+    p.Win = a.Win; p.Wout = a.Wout;
+    p.row_mask = a.row_mask != nullptr;
+    return p;
+}
 
-thread_local int rw_min_m = 4096;   // smallest M routed to the resident-weight kernel (kinet_gemm_set_flags bit 3: 256)
+}  // namespace
 
 // Entry from gemm.hip's dispatcher: launch the resident-weight kernel when the problem
 // fits it; false leaves the call to the tiled kernel.
 bool launch_rw(const GemmArgs& a, int in_dtype, int out_dtype, hipStream_t stream) {
-    if (in_dtype != KINET_BF16 && in_dtype != KINET_F16) return false;
-    if (a.M < rw_min_m || (a.K != 64 && a.K != 128 && a.K != 256 && a.K != 512 && a.K != 288)) return false;
-    if (a.K == 288 && (kinet_gemm_flags & 1048576)) return false;   // flag: K = 288 on the tiled kernels (A/B)
-    if (a.K == 512 && (a.N > 256 || a.R != nullptr || a.ln_g != nullptr || a.A2 != nullptr || (kinet_gemm_flags & 256)))
-        return false;
-    if (a.A2 != nullptr && (a.R != nullptr || a.ln_g != nullptr || !al16(a.A2))) return false;
-    if (a.N % 8 != 0 || (a.ln_g != nullptr && a.N > (a.K == 288 ? 288 : 256))) return false;
-    const bool o16 = out_dtype == in_dtype || (in_dtype == KINET_BF16 && out_dtype == KINET_F16);
-    const bool o32 = out_dtype == KINET_F32;
-    if (!o16 && !o32) return false;
-    if (o16 ? (a.ldc % 8 != 0) : (a.ldc % 4 != 0)) return false;
-    if (!al16(a.C) || (a.R != nullptr && (!o16 || a.ldr % 8 != 0 || !al16(a.R)))) return false;
-    // head-major stores: 16-byte units need hm_d % 8 == 0; the K = 288 path stores 4-column
-    // units (hm_d % 4 == 0) and takes the split planes (hm_d2 == 4)
-    if (a.hm_rows && (a.K == 288 ? (a.hm_d % 4 != 0 || (a.hm_split && (a.hm_d2 != 4 || a.hm_split % a.hm_d != 0)))
-                                 : (a.hm_d % 8 != 0 || a.hm_split)))
-        return false;
-    // output descriptor extent (buffer stores; offsets must stay below 2^31)
-    const long long osz = out_dtype == KINET_F32 ? 4 : 2;
-    const long long cb = a.hm_rows ? (long long)a.M * a.N * osz
-                                   : (a.M > 0 ? ((long long)(a.M - 1) * a.ldc + a.N) * osz : 0);
-    if (cb >= (1LL << 31)) return false;
-    GemmArgs ac = a;
-    ac.c_bytes = (int)cb;
-    ac.hm_tr = (kinet_gemm_flags & 1073741824) ? 0 : 1;   // flag: 32-column head-major stores without the LDS transpose (A/B)
-    if (in_dtype == KINET_BF16) {
-        if (out_dtype == KINET_F16) launch_t<bf16_t, f16_t>(ac, stream);
-        else if (o16) launch_t<bf16_t, bf16_t>(ac, stream);
-        else launch_t<bf16_t, float>(ac, stream);
-    } else {
-        if (o16) launch_t<f16_t, f16_t>(ac, stream);
-        else launch_t<f16_t, float>(ac, stream);
-    }
-    return true;
+    return launch_planned(rw_problem(RW_GEMM, a, in_dtype, out_dtype), a, stream);
 }
 
-// Entry from gemm.hip's conv dispatcher: the KH x 1, horizontally stride-1 unpadded conv of
-// the tap-folded stem (K = KH*Cin <= 256) as a resident-weight stream with the conv-row gather
-// (a short-K conv in the tiled kernel exposes a full load latency per 3-step tile); false
-// leaves the call to the tiled kernel.
+// Entry from gemm.hip's conv dispatcher (same-type convolutions: the tap-folded stem form and the
+// strided 1x1, gemm_rw_plan.h); false leaves the call to the tiled kernel.
 bool launch_rw_conv(const GemmArgs& a, int in_dtype, hipStream_t stream) {
-    if (in_dtype != KINET_BF16 && in_dtype != KINET_F16) return false;
-    // strided 1x1 (the ResNet downsample of stage 2, 256 -> 512 at stride 2): row m = output
-    // pixel, its A row = input pixel (img, 2 oh, 2 ow) -- the conv-row DMA with a horizontal
-    // stride; weights resident (K = 256), 256-column groups sharing each row tile through L2.
-    // The implicit-GEMM kernel ran it at ~310 TF/s (1.8 TB/s of compulsory bytes)
-    if (a.K == 256 && a.Cin == 256 && a.KW == 1 && a.pad == 0 && a.pad_w == 0 && a.stride > 1 &&
-        a.stride_w == a.stride && a.M >= rw_min_m && a.Wout >= 32 && a.N % 256 == 0 && a.R == nullptr &&
-        a.ln_g == nullptr && a.row_mask == nullptr && a.ldc % 8 == 0 && al16(a.C) && !(kinet_gemm_flags & 2048)) {
-        const long long cb = ((long long)(a.M - 1) * a.ldc + a.N) * 2;
-        if (cb >= (1LL << 31)) return false;
-        GemmArgs ac = a;
-        ac.c_bytes = (int)cb;
-        constexpr int NS = ring_depth<8, 32, false, false, false, 4>();
-        constexpr int NS16 = ring_depth<8, 16, false, false, false, 4>();
-        if (kinet_gemm_flags & 131072) {   // tests: 16-row tiles (bit-identical to the 32-row ones)
-            if (in_dtype == KINET_BF16) launch_cfg<bf16_t, bf16_t, 8, 16, NS16, false, false, false, 4, true>(ac, stream);
-            else launch_cfg<f16_t, f16_t, 8, 16, NS16, false, false, false, 4, true>(ac, stream);
-            return true;
-        }
-        if (in_dtype == KINET_BF16) launch_cfg<bf16_t, bf16_t, 8, 32, NS, false, false, false, 4, true>(ac, stream);
-        else launch_cfg<f16_t, f16_t, 8, 32, NS, false, false, false, 4, true>(ac, stream);
-        return true;
-    }
-    if (a.M < rw_min_m || a.K > 256 || a.KW != 1 || a.stride_w != 1 || a.pad_w != 0 || a.Win != a.Wout) return false;
-    if (a.Cin % 8 != 0 || a.Wout < 32 || a.N > 128 || a.N % 8 != 0 || a.R != nullptr || a.ln_g != nullptr) return false;
-    if (a.ldc % 8 != 0 || !al16(a.C) || a.row_mask != nullptr) return false;
-    const long long cb = ((long long)(a.M - 1) * a.ldc + a.N) * 2;
-    if (cb >= (1LL << 31)) return false;
-    GemmArgs ac = a;
-    ac.c_bytes = (int)cb;
-    constexpr int NS = ring_depth<8, 32, false, false, false>();
-    constexpr int NS16 = ring_depth<8, 16, false, false, false>();
-    if (kinet_gemm_flags & 131072) {   // tests: 16-row tiles (bit-identical to the 32-row ones)
-        if (in_dtype == KINET_BF16) launch_cfg<bf16_t, bf16_t, 8, 16, NS16, false, false, false, 2, true>(ac, stream);
-        else launch_cfg<f16_t, f16_t, 8, 16, NS16, false, false, false, 2, true>(ac, stream);
-        return true;
-    }
-    if (in_dtype == KINET_BF16) launch_cfg<bf16_t, bf16_t, 8, 32, NS, false, false, false, 2, true>(ac, stream);
-    else launch_cfg<f16_t, f16_t, 8, 32, NS, false, false, false, 2, true>(ac, stream);
-    return true;
+    RwProblem p = rw_problem(RW_CONV, a, in_dtype, in_dtype);
+    p.a2 = false;   // (convolutions take no A2)
+    return launch_planned(p, a, stream);
 }
 
 }  // namespace kinet
@@ -965,6 +787,38 @@ extern "C" int kinet_gemm_rw_grid_cap(int max_p) {
     return old;
 }
 
+extern "C" int kinet_gemm_rw_min_a2_rows(void) { return kRwMinA2Rows; }
+
+extern "C" int kinet_gemm_rw_plan(const int* problem, int cus, int* eligible, int* config) {
+    KINET_CHECK_ARG(problem != nullptr && eligible != nullptr && config != nullptr && cus > 0, "gemm_rw_plan: invalid arguments");
+    const int* f = problem;
+    KINET_CHECK_ARG(f[KINET_RWP_KIND] >= RW_GEMM && f[KINET_RWP_KIND] <= RW_RECORDS && f[KINET_RWP_M] >= 0 &&
+                        f[KINET_RWP_N] >= 0 && f[KINET_RWP_K] > 0, "gemm_rw_plan: invalid problem");
+    // (what kinet_msda_sample_records checks before it plans)
+    KINET_CHECK_ARG(f[KINET_RWP_KIND] != RW_RECORDS || (f[KINET_RWP_K] == 256 && f[KINET_RWP_N] % 192 == 0 && f[KINET_RWP_M] > 0 &&
+                                                        f[KINET_RWP_OUT_DTYPE] == KINET_F16),
+                    "gemm_rw_plan: records are K = 256, N = heads * 48 with heads %% 4 == 0, M > 0, f16 output");
+    RwProblem p{};
+    p.kind = f[KINET_RWP_KIND];
+    p.M = f[KINET_RWP_M]; p.N = f[KINET_RWP_N]; p.K = f[KINET_RWP_K];
+    p.in_dtype = f[KINET_RWP_IN_DTYPE]; p.out_dtype = f[KINET_RWP_OUT_DTYPE];
+    p.r = f[KINET_RWP_RESIDUAL] != 0; p.ln = f[KINET_RWP_LN] != 0; p.a2 = f[KINET_RWP_A2] != 0;
+    p.ldc = f[KINET_RWP_LDC]; p.ldr = f[KINET_RWP_LDR];
+    p.c_al16 = f[KINET_RWP_C_ALIGNED] != 0; p.r_al16 = f[KINET_RWP_R_ALIGNED] != 0; p.a2_al16 = f[KINET_RWP_A2_ALIGNED] != 0;
+    p.hm_rows = f[KINET_RWP_HM_ROWS]; p.hm_d = f[KINET_RWP_HM_D]; p.hm_split = f[KINET_RWP_HM_SPLIT]; p.hm_d2 = f[KINET_RWP_HM_D2];
+    p.Cin = f[KINET_RWP_CIN]; p.KW = f[KINET_RWP_KW]; p.stride = f[KINET_RWP_STRIDE]; p.stride_w = f[KINET_RWP_STRIDE_W];
+    p.pad = f[KINET_RWP_PAD]; p.pad_w = f[KINET_RWP_PAD_W]; p.Win = f[KINET_RWP_WIN]; p.Wout = f[KINET_RWP_WOUT];
+    p.row_mask = f[KINET_RWP_ROW_MASK] != 0;
+    p.flags = kinet_gemm_flags;
+    p.cap = rw_grid_cap;
+    p.cus = cus;
+    RwPlan plan;
+    *eligible = rw_plan(p, plan) ? 1 : 0;
+    for (int i = 0; i < RW_CFG_FIELDS; ++i) config[i] = 0;
+    if (*eligible) rw_config_record(plan, p.out_dtype, config);
+    return KINET_OK;
+}
+
 // The MSDA sampling-offsets | attention-weights projection of an encoder call, with the
 // softmax, sampling locations and bilinear setup in its epilogue (prep_records): writes the
 // head-major sampling records kinet_msda_encoder_forward_records reads.  include/kinet_msda.h.
@@ -973,7 +827,7 @@ extern "C" int kinet_msda_sample_records(const void* A, const void* A2, const vo
                                          int ref_dim, const uint8_t* query_attn_mask, const int64_t* spatial_shapes_host,
                                          int num_levels, int num_point, int frac_bits, void* records,
                                          int a2_rows, kinet_stream_t stream) {
-    KINET_CHECK_ARG(a2_rows == 0 || (A2 != nullptr && a2_rows >= 32 && M % a2_rows == 0),
+    KINET_CHECK_ARG(a2_rows == 0 || (A2 != nullptr && a2_rows >= kRwMinA2Rows && M % a2_rows == 0),
                     "msda records: a2_rows must be 0 or >= 32 dividing M (got %d)", a2_rows);
     KINET_CHECK_ARG(M >= 0 && num_heads > 0 && num_heads % 4 == 0, "msda records: heads must be a multiple of 4 (got %d)",
                     num_heads);
@@ -1008,34 +862,10 @@ extern "C" int kinet_msda_sample_records(const void* A, const void* A2, const vo
         a.prep_H[l] = (int)spatial_shapes_host[2 * l];
         a.prep_W[l] = (int)spatial_shapes_host[2 * l + 1];
     }
-    hipStream_t s = (hipStream_t)stream;
-    constexpr int NS1 = ring_depth<8, 16, false, false, false, 3, true>();
-    // With the position embedding added on load (A2, the encoder): ONE 8-wave 384-column group per
-    // 16-row tile, one workgroup per CU (166 VGPRs, a 4-slot ring): each row tile's x + pos rows
-    // are read once.  The two 4-wave 192-column groups before it (three workgroups per CU, a
-    // 2-slot ring) were meant to share each row tile through the XCD's L2 (same XCD by linear id),
-    // but PMC showed 1.11 GB fetched per batch-28 call against ~0.35 GB of operands: 270 -> 238 us
-    // per call, encoder call 0.72-0.74 -> 0.69-0.70 ms, bench 1416 / 1429 -> 1441 / 1446 frames/s
-    // interleaved, records bit-identical (profiles/r06am_records_8wave_ab.txt; two 8-wave groups per
-    // CU: 245 us, 1435 / 1445).  Flag 268435456 keeps the 4-wave groups (A/B, tests).  Round 4's
-    // notes on the 4-wave grid: three per CU beat two with a 4-slot ring under three streams
-    // (profiles/r04z_occ_ab.log), four per CU spilled.  The 32-row tile (two MFMA row tiles per
-    // wave) is not used here: its epilogue, interleaved by the compiler with the second tile's
-    // MFMA chain, differed from the 16-row tile in a few hundred record words from run to run
-    // (round 4-5)
-    if (A2 && !(kinet_gemm_flags & 268435456)) {
-        constexpr int NS8 = ring_depth<8, 16, false, false, true, 3, true, 8, 160 * 1024>();
-        if (in_dtype == KINET_BF16) launch_cfg<bf16_t, f16_t, 8, 16, NS8, false, false, true, 3, false, true, 1, 8>(a, s);
-        else launch_cfg<f16_t, f16_t, 8, 16, NS8, false, false, true, 3, false, true, 1, 8>(a, s);
-        KINET_LAUNCH_CHECK();
-        return KINET_OK;
-    }
-    if (in_dtype == KINET_BF16) {
-        if (A2) launch_cfg<bf16_t, f16_t, 8, 16, 2, false, false, true, 3, false, true, 3>(a, s);
-        else launch_cfg<bf16_t, f16_t, 8, 16, NS1, false, false, false, 3, false, true>(a, s);
-    } else {
-        if (A2) launch_cfg<f16_t, f16_t, 8, 16, 2, false, false, true, 3, false, true, 3>(a, s);
-        else launch_cfg<f16_t, f16_t, 8, 16, NS1, false, false, false, 3, false, true>(a, s);
+    // (which of the three record variants: rw_plan, RW_RECORDS)
+    if (!launch_planned(rw_problem(RW_RECORDS, a, in_dtype, KINET_F16), a, (hipStream_t)stream)) {
+        set_error("msda records: no kernel variant for this call");
+        return KINET_ERR_ARG;
     }
     KINET_LAUNCH_CHECK();
     return KINET_OK;

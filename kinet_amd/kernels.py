@@ -7,6 +7,7 @@ casts, OIHW->OHWI conv packing, folded FrozenBatchNorm) are cached per parameter
 version.
 """
 import ctypes
+import functools
 import weakref
 
 import torch
@@ -144,6 +145,39 @@ def gemm_plan(M, Nout, K, dtype_code=1, conv=False, Cin=0, ln=False, a2=False, k
     N.call('kinet_gemm_plan', M, Nout, K, Cin, int(conv), int(ln), int(a2), kchunk, hm_rows, dtype_code, cus,
            ctypes.addressof(n), ctypes.addressof(out))
     return [(_kernel_id(out[3 * i]), out[3 * i + 1], out[3 * i + 2]) for i in range(n.value)]
+
+
+# the problem fields of kinet_gemm_rw_plan, in the order of include/kinet_gemm.h's KINET_RWP_ enum
+GEMM_RW_PROBLEM_FIELDS = ('kind', 'M', 'N', 'K', 'in_dtype', 'out_dtype', 'residual', 'ln', 'a2', 'ldc', 'ldr', 'c_aligned',
+                          'r_aligned', 'a2_aligned', 'hm_rows', 'hm_d', 'hm_split', 'hm_d2', 'Cin', 'KW', 'stride', 'stride_w',
+                          'pad', 'pad_w', 'Win', 'Wout', 'row_mask')
+GEMM_RW_KINDS = ('gemm', 'conv', 'records')
+
+
+def gemm_rw_plan(M, Nout, K, in_dtype=1, out_dtype=None, kind='gemm', cus=256, **fields):
+    """The resident-weight launch planned for a described problem under this thread's flags and grid
+    cap (include/kinet_gemm.h kinet_gemm_rw_plan; needs no GPU): None when the kernel does not take
+    the problem, else the record gemm_rw_last_config() would return after the launch.  in_dtype /
+    out_dtype: kinet_dtypes (1 = bf16; out_dtype defaults to in_dtype, f16 for records); fields: the
+    other GEMM_RW_PROBLEM_FIELDS (default: ldc = ldr = N, every pointer aligned, everything else 0)."""
+    if out_dtype is None:
+        out_dtype = N.dtype_code(torch.float16) if kind == 'records' else in_dtype
+    p = dict.fromkeys(GEMM_RW_PROBLEM_FIELDS, 0)
+    p.update(kind=GEMM_RW_KINDS.index(kind), M=M, N=Nout, K=K, in_dtype=in_dtype, out_dtype=out_dtype, ldc=Nout, ldr=Nout,
+             c_aligned=1, r_aligned=1, a2_aligned=1)
+    unknown = set(fields) - set(GEMM_RW_PROBLEM_FIELDS)
+    if unknown:
+        raise TypeError(f'gemm_rw_plan: unknown fields {sorted(unknown)}')
+    p.update({k: int(v) for k, v in fields.items()})
+    prob = (ctypes.c_int * len(GEMM_RW_PROBLEM_FIELDS))(*(p[f] for f in GEMM_RW_PROBLEM_FIELDS))
+    ok, out = ctypes.c_int(0), (ctypes.c_int * len(GEMM_RW_CONFIG_FIELDS))()
+    N.call('kinet_gemm_rw_plan', ctypes.addressof(prob), cus, ctypes.addressof(ok), ctypes.addressof(out))
+    return dict(zip(GEMM_RW_CONFIG_FIELDS, out)) if ok.value else None
+
+
+@functools.lru_cache(maxsize=None)
+def _min_a2_rows():
+    return N.lib().kinet_gemm_rw_min_a2_rows()
 
 
 def _epilogue_operand(r, ld):
@@ -1043,7 +1077,7 @@ def _load_add_operand(x2, x_add, B, Lq, K):
     deformable_transformer.py forward_flat) -- else x_add has x's rows and layout."""
     if x_add is None:
         return x2, None, 0
-    if x_add.shape[0] == 1 and B > 1 and Lq >= 32:
+    if x_add.shape[0] == 1 and B > 1 and Lq >= _min_a2_rows():
         if x2.stride(-1) != 1 or x2.stride(0) != K or x2.data_ptr() % 16:
             x2 = x2.contiguous()
         a2 = x_add.reshape(Lq, K)

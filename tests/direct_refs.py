@@ -950,8 +950,9 @@ def conv_case(name, dtype, cls):
 #   case sets;  opts, space separated: R residual, Rld residual with ldr = N + 8, LN LayerNorm, A2 the
 #   load-time add, s per-column scale, b bias, relu, mask the row mask, ld output rows of N + 8 elements;
 # the last two columns are the instantiation and the number of column groups EXPECTED FROM READING
-# launch_t / launch_k / launch_ring / launch_288 and RwCfg (ring_depth worked out by hand from the LDS
-# budget): literals, never taken from the library.  M is 17 * BMR - 5 for every case: 17 row tiles, the
+# the launch rules (rw_plan and kRwVariants of csrc/gemm_rw_plan.h; the ring depth worked out by hand
+# from the LDS budget): literals, never taken from the library (test_gemm_rw_plan_cpu.py compares the
+# planner with them).  M is 17 * BMR - 5 for every case: 17 row tiles, the
 # last one ragged (11 of 16 or 27 of 32 rows).
 RW_F16ROW, RW_W4, RW_LN6, RW_NOTR, RW_NOSTEM = 131072, 268435456, 4194304, 1073741824, 32
 _B, _H, _F = torch.bfloat16, torch.float16, torch.float32
@@ -1168,6 +1169,13 @@ RW_CONV_CASES = [
     ('taps 3x1 N=64 16-row', (3, 64, 64, (2, 1), 3, 3, 33), RW_NOSTEM | RW_F16ROW, 'b relu', (8, 2, 16, 4, 4, 2), 1),
 ]
 RW_CONV_BATCH, RW_CONV_ROWS = 2, 264
+
+# Sampling records (PREP), 3 frames x 89 queries x 8 heads: (name, flags, x_add, config, ng): one 8-wave
+# 384-column group; two 4-wave groups with the load-time add (2 ring slots, 3 workgroups per CU) and
+# without it
+PREP_CASES = [('records 8-wave', 0, True, (8, 3, 16, 4, 8, 1), 1),
+              ('records 4-wave A2', RW_W4, True, (8, 3, 16, 2, 4, 3), 2),
+              ('records 4-wave', 0, False, (8, 3, 16, 4, 4, 2), 2)]
 
 
 @functools.lru_cache(maxsize=None)

@@ -4,10 +4,11 @@ against f64 references (tests/direct_refs.py, checked on the CPU by test_direct_
 Every case sets flag 8 (the resident-weight kernel from M >= 256) and asserts through
 kinet_gemm_rw_last_config the whole instantiation and grid it expects -- KC, NT, BMR, NS, NW, OCC, HAS_R,
 LN, HAS_A2, CR, PREP, the output element size, P, ng, n_mtiles.  The expectations are the literal
-tables RW_CASES / RW_HM_CASES / RW_CONV_CASES of direct_refs.py (and PREP_CASES below), written down
-from reading launch_t / launch_k / launch_ring / launch_288 / launch_rw_conv and RwCfg; nothing in
-them comes from the library, so on a machine without a GPU they can be cross-checked only as far as
-they are literal (shapes, flags and field names: test_direct_refs_cpu.py).
+tables RW_CASES / RW_HM_CASES / RW_CONV_CASES / PREP_CASES of direct_refs.py, written down from reading
+the launch rules (now rw_plan and kRwVariants of csrc/gemm_rw_plan.h) and the LDS geometry; nothing in
+them comes from the library.  On a machine without a GPU test_gemm_rw_plan_cpu.py checks every row of
+them, under every grid cap used here, against the library's planner (kinet_gemm_rw_plan), and
+test_direct_refs_cpu.py their shapes, flags and field names.
 
 Shapes: 17 row tiles with a ragged last one (M = 17 * BMR - 5), run under kinet_gemm_rw_grid_cap 0, 1, 3
 and 16: one tile per workgroup; one workgroup walking all 17 through its NS <= 4 ring slots; 6 / 6 / 5
@@ -317,15 +318,8 @@ def test_rw_conv_rows(K, knobs, case, cdt, cls):
 
 
 # ----------------------------------------------------------------- sampling records (PREP)
-# (name, flags, x_add, config, ng): one 8-wave 384-column group; two 4-wave groups with the load-time add
-# (2 ring slots, 3 workgroups per CU) and without it
-PREP_CASES = [('records 8-wave', 0, True, (8, 3, 16, 4, 8, 1), 1),
-              ('records 4-wave A2', R.RW_W4, True, (8, 3, 16, 2, 4, 3), 2),
-              ('records 4-wave', 0, False, (8, 3, 16, 4, 4, 2), 2)]
-
-
 @pytest.mark.parametrize('dtype', [BF16, F16], ids=_name)
-@pytest.mark.parametrize('case', PREP_CASES, ids=lambda c: c[0].replace(' ', '_'))
+@pytest.mark.parametrize('case', R.PREP_CASES, ids=lambda c: c[0].replace(' ', '_'))
 def test_rw_records_same_under_caps(K, knobs, case, dtype):
     """kinet_msda_sample_records has its oracle test (test_msda_gpu.py); here: the records are
     bit-identical however the 17 row tiles are spread over workgroups."""
