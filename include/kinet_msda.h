@@ -184,6 +184,14 @@ int kinet_msda_encoder_forward_records(const void* value, int64_t value_sb, int6
  * empty call, or no call yet).  Host-side bookkeeping for the rooflines; no GPU call. */
 int kinet_msda_backward_last_kernel(void);
 
+/* Which forward sampling kernel the calling thread's last kinet_msda_fused_forward or
+ * kinet_msda_encoder_forward{,_split,_records} launched: family << 8 | detail, or -1 = none (an
+ * empty or refused call, or no call yet).  family 1 = msda_fused_kernel, detail = its vector width
+ * (1, 2, 4, 8); family 2 = msda_fused_fast_kernel, detail = its level count (4 or 8); family 3 =
+ * msda_enc_kernel, detail = the plan's gathered levels fl (0-3) | 16 for the records front end |
+ * 32 for the split (36-channel) one.  Host-side bookkeeping; no GPU call. */
+int kinet_msda_fused_last_kernel(void);
+
 /* Head_dim-36 encoder calls (configs 3-5, d = 288: cfgs/train_multi_frame.yaml:2) on the strip
  * kernel: the value in TWO head-major planes written by kinet_gemm_headmajor_split --
  * value_main (M, N, S, 32) f16 (channels 0-31 of each head; strides as value_sb / value_sm of

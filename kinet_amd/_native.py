@@ -26,6 +26,7 @@ _SIGS = {
     'kinet_msda_backward_tune': [I] * 5,
     'kinet_msda_backward_debug': [I],
     'kinet_msda_backward_last_kernel': [],
+    'kinet_msda_fused_last_kernel': [],
     'kinet_msda_encoder_forward': [P, I64, I64, P, P, P, I, P, P] + [I] * 8 + [P, P],
     'kinet_msda_encoder_plan': [P, I, I, I, P],
     'kinet_msda_encoder_set_strips': [I],

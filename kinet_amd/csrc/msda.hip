@@ -31,6 +31,7 @@
 #include "msda_util.h"
 
 namespace kinet {
+thread_local int msda_fused_last = -1;
 namespace {
 
 constexpr int kThreads = 256;
@@ -1383,6 +1384,7 @@ int launch_fused(const void* value, long vsb, int vss, long vsm, const int64_t* 
                  float* attw_out, int N, int S, int M, int D, int L, int Lq, int P, const int* torder,
                  hipStream_t stream) {
     const Cfg c = pick_cfg(D, M, sizeof(T));
+    msda_fused_last = -1;
     KINET_CHECK_ARG(c.lpq <= 64, "msda fused: head_dim/vec (%d) exceeds a wave", c.lpq);
     if (N == 0 || Lq == 0) return KINET_OK;
     if constexpr (sizeof(T) == 2) {
@@ -1404,6 +1406,7 @@ int launch_fused(const void* value, long vsb, int vss, long vsm, const int64_t* 
                                    ref, ref_dim, qmask, loc_out,
                                    attw_out, (TO*)out, S, M, Lq, torder);
             KINET_LAUNCH_CHECK();
+            msda_fused_last = kFusedFast << 8 | L;
             return KINET_OK;
         }
     }
@@ -1434,6 +1437,7 @@ int launch_fused(const void* value, long vsb, int vss, long vsm, const int64_t* 
     }
 #undef KF
     KINET_LAUNCH_CHECK();
+    msda_fused_last = kFusedGeneric << 8 | c.vec;
     return KINET_OK;
 }
 }  // namespace
@@ -1505,6 +1509,8 @@ extern "C" int kinet_msda_backward(const void* value, const int64_t* spatial_sha
 }
 
 extern "C" int kinet_msda_backward_last_kernel(void) { return bwd_last; }
+
+extern "C" int kinet_msda_fused_last_kernel(void) { return msda_fused_last; }
 
 extern "C" int kinet_msda_backward_debug(int flags) {
     const int old = bwd_dbg;

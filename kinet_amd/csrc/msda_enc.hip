@@ -889,6 +889,7 @@ int encoder_forward(const void* value, int64_t value_sb, int64_t value_sm, const
                     int frac_bits, bool rec, void* output, int batch, int spatial_size, int num_heads, int channels,
                     int num_levels, int num_query, int num_point, int output_dtype, const int32_t* query_tile_order,
                     kinet_stream_t stream, const void* tail = nullptr, int64_t tail_sb = 0, int64_t tail_sm = 0) {
+    msda_fused_last = -1;
     KINET_CHECK_ARG(batch >= 0 && spatial_size > 0 && num_heads > 0 && num_query >= 0, "msda encoder: bad sizes");
     const bool has_tail = tail != nullptr;
     KINET_CHECK_ARG(channels == (has_tail ? 36 : 32) && num_levels == EL && num_point == EP,
@@ -991,6 +992,7 @@ int encoder_forward(const void* value, int64_t value_sb, int64_t value_sm, const
 #undef TK_QM
 #undef TK
         KINET_LAUNCH_CHECK();
+        msda_fused_last = kFusedEncoder << 8 | 32 | pl.fl;
         return KINET_OK;
     }
 #define EK(TO_, FL_, RD_, QM_) hipLaunchKernelGGL((msda_enc_kernel<TO_, FL_, RD_, QM_>), grid, block, 0, s, a)
@@ -1015,6 +1017,7 @@ int encoder_forward(const void* value, int64_t value_sb, int64_t value_sm, const
 #undef EK_QM
 #undef EK
     KINET_LAUNCH_CHECK();
+    msda_fused_last = kFusedEncoder << 8 | (rec ? 16 : 0) | pl.fl;
     return KINET_OK;
 }
 }  // namespace

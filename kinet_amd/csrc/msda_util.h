@@ -9,6 +9,11 @@ namespace kinet {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 
+// the forward sampling kernel the calling thread's last fused / encoder call launched, in the
+// packing of kinet_msda_fused_last_kernel (defined in msda.hip; host-side bookkeeping only)
+extern thread_local int msda_fused_last;
+constexpr int kFusedGeneric = 1, kFusedFast = 2, kFusedEncoder = 3;
+
 // acc += f16(half of x) * f16(half of w) in f32 (both multiplicands 16-bit sources)
 __device__ __forceinline__ float fma_mix16_lo_lo(float acc, uint32_t x, uint32_t w) {
     asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel_hi:[1,1,0]" : "+v"(acc) : "v"(x), "v"(w));

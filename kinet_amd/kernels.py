@@ -980,6 +980,19 @@ _enc_plans = {}
 _KT = {torch.bfloat16: 'kinet::bf16_t', torch.float16: 'kinet::f16_t', torch.float32: 'float', torch.float64: 'double'}
 
 
+def msda_fused_last_kernel():
+    """The forward sampling kernel the calling thread's last msda_fused / msda_encoder* call
+    launched (kinet_msda_fused_last_kernel): ('generic', vec), ('fast', L), ('encoder', fl, front
+    end) with front end 'offlog', 'records' or 'split', or None (no launch)."""
+    code = N.lib().kinet_msda_fused_last_kernel()
+    if code < 0:
+        return None
+    fam, det = code >> 8, code & 255
+    if fam == 3:
+        return ('encoder', det & 15, 'split' if det & 32 else 'records' if det & 16 else 'offlog')
+    return ({1: 'generic', 2: 'fast'}[fam], det)
+
+
 def msda_encoder_set_strips(strips):
     """Strips per head map for the encoder sampler on the calling thread (0 = the plan's own
     choice; kinet_msda_encoder_set_strips, A/B tooling).  The cached plans are dropped, so
@@ -1023,10 +1036,10 @@ def msda_split_supported(dtype, head_dim, shapes, Lq, n_heads, n_levels, n_point
 
 
 def msda_encoder_split(value, shapes, offlog_hm, reference_points, n_heads, query_attn_mask=None, out_dtype=None,
-                       query_tile_order=None):
+                       query_tile_order=None, out=None):
     """Head_dim-36 encoder sampling (kinet_msda_encoder_forward_split): value a SplitValue from
     value_proj_headmajor_split, offlog_hm (M, B, Lq, 48) f16, reference_points (B, Lq, 4, 2|4) f32
-    -> (B, Lq, M*36)."""
+    -> (B, Lq, M*36).  out: the tensor to write (tests)."""
     main, tail = value.main, value.tail
     M_, B, S, _ = main.shape
     D = 36
@@ -1037,7 +1050,8 @@ def msda_encoder_split(value, shapes, offlog_hm, reference_points, n_heads, quer
         hs = _host_shapes[key] = torch.tensor(key, dtype=torch.int64)
     ref = reference_points.float().contiguous()
     od = out_dtype or torch.bfloat16
-    out = torch.empty((B, Lq, M_ * D), dtype=od, device=main.device)
+    shape = (B, Lq, M_ * D)
+    out = torch.empty(shape, dtype=od, device=main.device) if out is None else _headmajor_out(out, shape, od)
     qm = query_attn_mask.to(torch.uint8).contiguous() if query_attn_mask is not None else None
     if query_tile_order is not None and (query_tile_order.dtype != torch.int32 or
                                          query_tile_order.numel() != (Lq + 15) // 16):
@@ -1119,10 +1133,11 @@ def offsets_proj_headmajor(x, weight, bias, heads, x_add=None, out_dtype=torch.f
 
 
 def msda_encoder(value, shapes, offlog_hm, reference_points, n_heads, query_attn_mask=None, out_dtype=None,
-                 query_tile_order=None):
+                 query_tile_order=None, out=None):
     """Encoder-sized MSDeformAttn sampling (kinet_msda_encoder_forward): value (M, B, S, 32)
     f16 head-major, shapes = host list of (H, W), offlog_hm (M, B, Lq, 48) f16 from
-    offsets_proj_headmajor, reference_points (B, Lq, 4, 2|4) f32 -> (B, Lq, M*32)."""
+    offsets_proj_headmajor, reference_points (B, Lq, 4, 2|4) f32 -> (B, Lq, M*32).  out: the tensor
+    to write (tests)."""
     M_, B, S, D = value.shape
     Lq = offlog_hm.shape[2]
     key = tuple(tuple(int(v) for v in s) for s in shapes)
@@ -1131,7 +1146,8 @@ def msda_encoder(value, shapes, offlog_hm, reference_points, n_heads, query_attn
         hs = _host_shapes[key] = torch.tensor(key, dtype=torch.int64)
     ref = reference_points.float().contiguous()
     od = out_dtype or torch.bfloat16
-    out = torch.empty((B, Lq, M_ * D), dtype=od, device=value.device)
+    shape = (B, Lq, M_ * D)
+    out = torch.empty(shape, dtype=od, device=value.device) if out is None else _headmajor_out(out, shape, od)
     qm = query_attn_mask.to(torch.uint8).contiguous() if query_attn_mask is not None else None
     if query_tile_order is not None and (query_tile_order.dtype != torch.int32 or
                                          query_tile_order.numel() != (Lq + 15) // 16):
@@ -1203,10 +1219,10 @@ def msda_sample_records(x, weight, bias, heads, reference_points, shapes_host, x
     return rec, fb
 
 
-def msda_encoder_records(value, shapes, records, frac_bits, out_dtype=None, query_tile_order=None):
+def msda_encoder_records(value, shapes, records, frac_bits, out_dtype=None, query_tile_order=None, out=None):
     """Encoder-sized MSDA sampling from sampling records (kinet_msda_encoder_forward_records):
     value (M, B, S, 32) f16 head-major, records (M, B, Lq, 24) int32 from msda_sample_records
-    -> (B, Lq, M*32)."""
+    -> (B, Lq, M*32).  out: the tensor to write (tests)."""
     M_, B, S, D = value.shape
     Lq = records.shape[2]
     key = tuple(tuple(int(v) for v in s) for s in shapes)
@@ -1214,7 +1230,8 @@ def msda_encoder_records(value, shapes, records, frac_bits, out_dtype=None, quer
     if hs is None:
         hs = _host_shapes[key] = torch.tensor(key, dtype=torch.int64)
     od = out_dtype or torch.bfloat16
-    out = torch.empty((B, Lq, M_ * D), dtype=od, device=value.device)
+    shape = (B, Lq, M_ * D)
+    out = torch.empty(shape, dtype=od, device=value.device) if out is None else _headmajor_out(out, shape, od)
     if query_tile_order is not None and (query_tile_order.dtype != torch.int32 or
                                          query_tile_order.numel() != (Lq + 15) // 16):
         raise RuntimeError('msda_encoder_records: query_tile_order must be int32 with ceil(Lq/16) entries')
@@ -1233,7 +1250,7 @@ def msda_encoder_records(value, shapes, records, frac_bits, out_dtype=None, quer
 
 def msda_fused(value, spatial_shapes, offlog, reference_points, n_heads, n_levels, n_points,
                query_attn_mask=None, want_loc_attw=False, head_major=False, out_dtype=None,
-               query_tile_order=None):
+               query_tile_order=None, out=None):
     """Sampling of MSDeformAttn.forward (ms_deform_attn.py:69-87) in one kernel.
     value: projected values, either (B, S, d) row-major (column slices allowed) or, with
     head_major=True, (M, B, S, D) as written by value_proj_headmajor;
@@ -1243,6 +1260,7 @@ def msda_fused(value, spatial_shapes, offlog, reference_points, n_heads, n_level
     query_tile_order: optional int32 (ceil(Lq/16),) processing order of the 16-query tiles
     (encoder_tile_order); only the fast 16-bit D=32 kernel uses it, the generic kernel
     ignores it (the output is identical either way).
+    out: the tensor to write (tests).
     Cached weights/geometry are built on the stream current at first use: a caller that
     runs several streams from a cold start synchronises once after the first forward.
     Returns (B, Lq, d) [, loc, attw]."""
@@ -1266,7 +1284,7 @@ def msda_fused(value, spatial_shapes, offlog, reference_points, n_heads, n_level
     if ref.shape[2] != n_levels:
         raise RuntimeError(f'reference_points has {ref.shape[2]} levels, module expects {n_levels}')
     od = out_dtype or value.dtype
-    out = torch.empty((B, Lq, d), dtype=od, device=value.device)
+    out = torch.empty((B, Lq, d), dtype=od, device=value.device) if out is None else _headmajor_out(out, (B, Lq, d), od)
     loc = attw = None
     if want_loc_attw:
         loc = torch.empty((B, Lq, n_heads, n_levels, n_points, 2), dtype=torch.float32, device=value.device)

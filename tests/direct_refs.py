@@ -1,6 +1,6 @@
 """High-precision restatements of the small kernels' operations, shared by
 test_ops_direct_gpu.py / test_grad_prims_gpu.py / test_grad_norm_attn_gpu.py /
-test_train_ops_direct_gpu.py / test_gemm_tiles_direct_gpu.py and checked on the CPU by
+test_train_ops_direct_gpu.py / test_gemm_tiles_direct_gpu.py / test_msda_direct_gpu.py and checked on the CPU by
 test_direct_refs_cpu.py.
 Plain torch on the CPU; nothing here touches the GPU or the native library."""
 import functools
@@ -1194,3 +1194,403 @@ def rw_conv_inputs(name, dtype, cls):
     o = opts.split()
     return (x, w, scale if 's' in o else None, bias if 'b' in o else None, conv64(x, w, stride, (pad_h, 0)),
             conv64(x.abs(), w.abs(), stride, (pad_h, 0)))
+
+
+# ============================ MSDA forward sampling (csrc/msda.hip, csrc/msda_enc.hip)
+def msda_sample_ref(value, shapes, loc, attw):
+    """ms_deform_im2col's forward (ms_deform_im2col_cuda.cuh:165-237) in plain torch f64: value
+    (B, S, M, D), shapes [(H, W)] * L, loc (B, Lq, M, L, P, 2) normalised (x, y), attw (B, Lq, M, L, P).
+    Per tap h = y H - 0.5, w = x W - 0.5; outside (-1, H) x (-1, W) it adds 0; else the four corners
+    (floor(h) + {0, 1}, floor(w) + {0, 1}) inside the level, weighted (1 - lh | lh) (1 - lw | lw) a.
+    That is bilinear interpolation of the level padded with zeros, continuous in (h, w) everywhere.
+    Returns, each (B, Lq, M * D) unless said:
+      out    the output
+      A      sum |a w_corner v|, the running-error majorant;  A_lvl (L, ...) its split per level
+      V      sum |v| over the in-level corners of taps with a != 0 (what an ABSOLUTE tap-weight error multiplies)
+      G_lvl  (L, ...) per level: sum over its taps of a (gx + gy), gx (gy) the largest |difference| of
+             horizontally (vertically) adjacent pixels of the zero-padded level within rows
+             floor(h) - 1 .. floor(h) + 2, columns floor(w) - 1 .. floor(w) + 2: every cell a location
+             error below one pixel can reach.  Moving every tap of level l by at most d_l pixels per
+             axis moves the output by at most sum_l G_lvl[l] d_l;  G = sum_l G_lvl[l]."""
+    value, loc, attw = value.double(), loc.double(), attw.double()
+    B, S, M, D = value.shape
+    _, Lq, _, L, P, _ = loc.shape
+    bi = torch.arange(B).view(B, 1, 1, 1)
+    mi = torch.arange(M).view(1, 1, M, 1)
+    out = torch.zeros(B, Lq, M, D, dtype=torch.float64)
+    A_lvl = torch.zeros(L, B, Lq, M, D, dtype=torch.float64)
+    G_lvl, V = torch.zeros_like(A_lvl), torch.zeros_like(out)
+    start = 0
+    for l, (H, W) in enumerate((int(h), int(w)) for h, w in shapes):
+        v = value[:, start:start + H * W]                                   # (B, H W, M, D)
+        h = loc[:, :, :, l, :, 1] * H - 0.5                                 # (B, Lq, M, P)
+        w = loc[:, :, :, l, :, 0] * W - 0.5
+        a = attw[:, :, :, l, :]
+        valid = (h > -1) & (w > -1) & (h < H) & (w < W)
+        hl, wl = torch.floor(h), torch.floor(w)
+        lh, lw = h - hl, w - wl
+        for dy, wy in ((0, 1 - lh), (1, lh)):
+            for dx, wx in ((0, 1 - lw), (1, lw)):
+                r, c = hl + dy, wl + dx
+                ok = valid & (r >= 0) & (r < H) & (c >= 0) & (c < W)
+                idx = (r.clamp(0, H - 1) * W + c.clamp(0, W - 1)).long()
+                vc = v[bi, idx, mi] * ok[..., None]                         # (B, Lq, M, P, D)
+                t = (a * wy * wx)[..., None] * vc
+                out += t.sum(3)
+                A_lvl[l] += t.abs().sum(3)
+                V += (vc.abs() * (a != 0)[..., None]).sum(3)
+        # the slope: |differences| of the level padded by 3 zero pixels, max-pooled over the 4 x 4 footprint
+        img = F.pad(v.permute(0, 2, 3, 1).reshape(B, M * D, H, W), (3, 3, 3, 3))
+        gx = F.max_pool2d((img[..., :, 1:] - img[..., :, :-1]).abs(), (4, 3), 1)     # (B, M D, H + 3, W + 3)
+        gy = F.max_pool2d((img[..., 1:, :] - img[..., :-1, :]).abs(), (3, 4), 1)
+        g = (gx + gy).reshape(B, M, D, (H + 3) * (W + 3)).permute(0, 3, 1, 2)      # (B, pix, M, D)
+        gidx = ((hl + 2).clamp(0, H + 2) * (W + 3) + (wl + 2).clamp(0, W + 2)).long()
+        G_lvl[l] = (a[..., None] * g[bi, gidx, mi]).sum(3)
+        start += H * W
+    f = lambda t: t.reshape(*t.shape[:-2], M * D)
+    return {'out': f(out), 'A': f(A_lvl.sum(0)), 'A_lvl': f(A_lvl), 'V': f(V), 'G_lvl': f(G_lvl), 'G': f(G_lvl.sum(0))}
+
+
+# ---- the strip plan of the encoder kernel (msda_enc.hip: plan_layout, enc_plan, enc_tiles) ----
+ENC_MAIN, ENC_TAIL, ENC_HALO, ENC_QT = 2544, 2256, 4, 16
+
+# (name, level shapes, batch, heads, channels, forced strips) -> (fl, nstrip, used), Lq = S.  Written down
+# by reading plan_layout / enc_plan for 256 compute units:
+#   region of a staged level: cap = min(H + 2, ceil(H / n) + 3 + 2 * 4) rows, ceil16(cap W + 2) map pixels,
+#   after a zero margin of ceil16(widest staged W + 2); budget 2544 pixels (36 channels: 2256);
+#   fl = the fewest gathered levels that fit at some n <= min(64, tiles // 16); the automatic n is the first
+#   >= the smallest fitting one that fills 90 % of a round of 256 workgroups (8 maps: never below 29, so the
+#   smallest fitting n); a forced n is honoured in [smallest fitting, min(64, tiles // 16)].
+#   'all' n = 1: 48 + ceil16(27*40+2) + ceil16(17*20+2) + ceil16(10*10+2) + ceil16(6*5+2) = 48+1088+352+112+32
+#   'wide1': level 0 needs >= 12 rows of 200 + margin 208 > 2544 with the others; levels 1-3: 112+704+256+112
+#   'wide2': level 1 (190 wide, 14 rows) does not fit beside 2-3; levels 2-3: 32 + ceil16(8*30+2) + ceil16(5*15+2)
+#   'wide2s': level 2 = 13 x 180: cap 12 (n >= 13: ceil(13/13) + 11) -> 192 + 2176 + 144; with 36 channels
+#             12 * 180 + 192 > 2256 at every n, level 3 alone: 32 + ceil16(7*20+2)
+#   'wide3': level 2 (7 rows of 220) + level 3 (5 rows of 216) exceed the map; level 3: 224 + ceil16(5*216+2)
+#   'tall1': level 0 (200 wide) never fits; levels 1-3 are taller than cap from n = 2 (n = 4: 21, 19, 16 rows)
+MSDA_ENC_GEO = {
+    'all': ((25, 40), (15, 20), (8, 10), (4, 5)),
+    'wide1': ((10, 200), (5, 100), (3, 50), (2, 25)),
+    'wide2': ((10, 200), (12, 190), (6, 30), (3, 15)),
+    'wide2s': ((10, 200), (12, 190), (13, 180), (5, 20)),
+    'wide3': ((4, 230), (3, 225), (5, 220), (3, 216)),
+    'tall1': ((12, 200), (40, 30), (30, 20), (20, 10)),
+}
+MSDA_ENC_REFUSED = ((20, 250), (20, 250), (20, 250), (20, 250))
+MSDA_ENC_CASES = [
+    ('all', 1, 8, 32, 0, (0, 1, 1632)), ('all', 1, 8, 32, 1, (0, 1, 1632)), ('all', 1, 8, 32, 2, (0, 2, 1520)),
+    ('all', 1, 8, 32, 3, (0, 3, 1344)), ('all', 3, 8, 32, 3, (0, 3, 1344)), ('all', 1, 5, 32, 3, (0, 3, 1344)), ('all', 2, 5, 32, 3, (0, 3, 1344)),
+    ('all', 1, 8, 36, 3, (0, 3, 1344)), ('all', 1, 8, 32, 13, (0, 1, 1632)),          # 13 > tiles // 16 = 5: ignored
+    ('wide1', 1, 8, 32, 0, (1, 1, 1184)), ('wide1', 1, 8, 32, 3, (1, 3, 1184)), ('wide1', 1, 8, 36, 0, (1, 1, 1184)),
+    ('wide2', 1, 8, 32, 0, (2, 1, 368)), ('wide2', 1, 8, 32, 4, (2, 4, 368)),
+    ('wide2s', 1, 8, 32, 0, (2, 13, 2512)), ('wide2s', 1, 8, 32, 3, (2, 13, 2512)),  # 3 < 13: ignored
+    ('wide2s', 1, 8, 36, 0, (3, 1, 176)), ('wide2s', 1, 8, 36, 3, (3, 3, 176)),
+    ('wide3', 1, 8, 32, 0, (3, 1, 1312)), ('wide3', 1, 8, 32, 2, (3, 2, 1312)),
+    ('tall1', 1, 8, 32, 0, (1, 1, 2176)), ('tall1', 1, 8, 32, 4, (1, 4, 1232)), ('tall1', 1, 8, 36, 4, (1, 4, 1232)),
+    ('tall1', 1, 8, 32, 13, (1, 13, 928)),
+]
+
+
+def msda_enc_expected(name, batch, heads, channels, forced):
+    return next(c[5] for c in MSDA_ENC_CASES if c[:5] == (name, batch, heads, channels, forced))
+
+
+def msda_enc_caps(shapes, fl, n):
+    """Rows per staged region (0 for a gathered level), plan_layout's rule."""
+    return [0 if l < fl else min(H + 2, (H + n - 1) // n + 3 + 2 * ENC_HALO) for l, (H, W) in enumerate(shapes)]
+
+
+def msda_enc_windows(shapes, fl, n, order=None):
+    """enc_tiles' staged rows restated in f64: per strip s and staged level l the window [r, r + cap - 1]
+    (a footprint is read from LDS iff r <= floor(h) < r + cap - 1) -> (tile -> strip (ntile,), r (n, L)).
+    The strip's query rows come from its level-0 tiles (or every tile's first query when it has none);
+    hmin = floor(ylo H - 0.5), hmax = floor(yhi H - 0.5) + 1, r = hmin - max(0, (cap - (hmax - hmin + 1)) // 2)
+    clamped to [-1, H + 1 - cap].  The kernel computes ylo H - 0.5 in f32: where that lands within
+    rounding of an integer its window may sit one row off this one, so callers keep one row of slack."""
+    hw = [h * w for h, w in shapes]
+    starts = np.concatenate([[0], np.cumsum(hw)]).astype(np.int64)
+    Lq = int(starts[-1])
+    ntile = (Lq + ENC_QT - 1) // ENC_QT
+    order = np.arange(ntile) if order is None else np.asarray(order)
+    caps = msda_enc_caps(shapes, fl, n)
+    strip_of = np.zeros(ntile, dtype=np.int64)
+    win = np.zeros((n, len(shapes)), dtype=np.int64)
+    for s in range(n):
+        t0, t1 = s * ntile // n, (s + 1) * ntile // n
+        q0 = order[t0:t1] * ENC_QT
+        strip_of[order[t0:t1]] = s
+        H0, W0 = shapes[0]
+        in0 = q0 < starts[1]
+        if in0.any():
+            qb = np.minimum(q0[in0] + ENC_QT, starts[1]) - 1
+            ylo, yhi = ((q0[in0] // W0).min() + 0.5) / H0, ((qb // W0).max() + 0.5) / H0
+        else:
+            lv = np.searchsorted(starts, q0, side='right') - 1
+            y = ((q0 - starts[lv]) // np.array([w for _, w in shapes])[lv] + 0.5) / np.array([h for h, _ in shapes])[lv]
+            ylo, yhi = y.min(), y.max()
+        for l in range(fl, len(shapes)):
+            H, cap = shapes[l][0], caps[l]
+            hmin, hmax = math.floor(ylo * H - 0.5), math.floor(yhi * H - 0.5) + 1
+            r = hmin - max(0, cap - (hmax - hmin + 1)) // 2
+            win[s, l] = max(-1, min(r, H + 1 - cap))
+    return strip_of, win
+
+
+# ---- problems: two operand classes ----
+def msda_hm(offlog, M, L=4, P=4):
+    """(B, Lq, M L P 3) [offsets | logits] -> (M, B, Lq, L P 3) per-head [offsets | logits], f16."""
+    B, Lq, _ = offlog.shape
+    off = offlog[..., :M * L * P * 2].reshape(B, Lq, M, L * P * 2)
+    lg = offlog[..., M * L * P * 2:].reshape(B, Lq, M, L * P)
+    return torch.cat([off, lg], -1).permute(2, 0, 1, 3).contiguous().half()
+
+
+def msda_pixel_refs(shapes, B):
+    """The encoder's reference points with valid ratios 1: query q = pixel (i, j) of its level ->
+    ((j + .5) / W, (i + .5) / H) at every level; also each query's (level, row, col)."""
+    pts, meta = [], []
+    for l, (h, w) in enumerate(shapes):
+        yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float64), torch.arange(w, dtype=torch.float64), indexing='ij')
+        pts.append(torch.stack([(xx.reshape(-1) + 0.5) / w, (yy.reshape(-1) + 0.5) / h], -1))
+        meta.append(torch.stack([torch.full((h * w,), l), yy.reshape(-1).long(), xx.reshape(-1).long()], -1))
+    r = torch.cat(pts, 0)
+    return r[None, :, None, :].expand(B, -1, len(shapes), -1).contiguous(), torch.cat(meta, 0)
+
+
+MSDA_COLD = -30000.0     # a cold logit: exp(-30000) is exactly 0 in f32 and -30000 rounds to a finite f16
+ADDR_CATS = ('near', 'far', 'row-1', 'rowH-1', 'col-1', 'colW-1', 'win_first', 'win_last')
+
+
+@functools.lru_cache(maxsize=None)
+def msda_addr_case(shapes, B, M, Lq, ref_dim, D=32, P=4, plan=None, order=None, seed=0):
+    """The addressing class.  Values 4 * integers in [-8, 8] (exact in bf16 / f16, and a quarter of a sum
+    of four is still an integer).  Per (b, q, head m) ONE tap has logit 0 and the others MSDA_COLD: the
+    softmax is exactly (1, 0, ..., 0).  The hot tap (l, p) = ((q + m) % L, (q // L + m) % P) rotates over
+    the L * P taps with the query index.  Per (b, q, level l) one TARGET: a pixel centre (h, w) = (row, col)
+    -- one pixel read -- or, every other query, the cell corner (row + .5, col + .5) -- four pixels at
+    weight 1/4.  The offsets are small multiples of 1/2 (exact in f16), shared by the level's taps, and the
+    reference point is target - offset term, rounded to f32: the f64 location of the hot tap is within one
+    f32 rounding of the target.
+    Target categories rotate with (q // 16 + l): 'near' (within 2 rows of the query's own row), 'far' (more
+    than cap rows from it, where the level is taller than its staged window), row -1, row H - 1, column -1,
+    column W - 1, and the first / last rows of the strip's staged window (plan = (fl, nstrip), tile order
+    `order`; without a plan the categories fold onto the first six and 'far' means any other row).
+    -> dict(value (B, S, M, D) f64, offlog (B, Lq, 3 M L P) f32, refs (B, Lq, L, ref_dim) f32, cat (B, Lq, L) index
+    into ADDR_CATS, hot (B, Lq, M) hot level, refs64 the reference points before their rounding to f32: the
+    records front end takes none, its records are built from these)."""
+    g = torch.Generator().manual_seed(seed + 7 * Lq + M)
+    L = len(shapes)
+    S = sum(h * w for h, w in shapes)
+    value = 4.0 * torch.randint(-8, 9, (B, S, M, D), generator=g).double()
+    q = torch.arange(Lq)
+    if Lq == S:
+        _, meta = msda_pixel_refs(shapes, 1)
+        qy = (meta[:, 1].double() + 0.5) / torch.tensor([shapes[l][0] for l in meta[:, 0].tolist()], dtype=torch.float64)
+        qx = (meta[:, 2].double() + 0.5) / torch.tensor([shapes[l][1] for l in meta[:, 0].tolist()], dtype=torch.float64)
+    else:
+        qy, qx = torch.rand(Lq, generator=g).double(), torch.rand(Lq, generator=g).double()
+    fl, n = plan if plan is not None else (L, 1)
+    caps = msda_enc_caps(shapes, fl, n)
+    strip_of, win = msda_enc_windows(shapes, fl, n, order) if plan is not None and Lq == S else (None, None)
+    offlog = torch.zeros(B, Lq, 3 * M * L * P)
+    refs = torch.zeros(B, Lq, L, ref_dim, dtype=torch.float64)
+    cat = torch.zeros(B, Lq, L, dtype=torch.long)
+    off = torch.randint(-6, 7, (B, Lq, L, 2), generator=g).double() / 2          # (x, y) raw offsets
+    if ref_dim == 4:
+        refs[..., 2:] = torch.randint(1, 5, (B, Lq, L, 2), generator=g).double() / 8      # w, h in {1/8 .. 1/2}
+    for l, (H, W) in enumerate(shapes):
+        own_r = torch.floor(qy * H).long().clamp(0, H - 1)[None].expand(B, -1)
+        own_c = torch.floor(qx * W).long().clamp(0, W - 1)[None].expand(B, -1)
+        k = ((q // 16 + l)[None] + torch.arange(B)[:, None]) % len(ADDR_CATS)
+        dr = torch.randint(-2, 3, (B, Lq), generator=g)
+        dc = torch.randint(-2, 3, (B, Lq), generator=g)
+        row, col = (own_r + dr).clamp(0, H - 1), (own_c + dc).clamp(0, W - 1)
+        c_near = torch.zeros_like(k)
+        staged = l >= fl and strip_of is not None
+        far_ok = H > caps[l] if plan is not None and l >= fl else H > 6
+        gap = caps[l] + 1 if plan is not None and l >= fl else 3
+        up, dn = own_r - gap - dr.abs(), own_r + gap + dr.abs()
+        far_row = torch.where(up >= 0, up, dn)
+        is_far = (k == 1) & far_ok & (far_row >= 0) & (far_row < H)
+        row = torch.where(is_far, far_row, row)
+        is_top, is_bot = k == 2, k == 3
+        row = torch.where(is_top, torch.full_like(row, -1), torch.where(is_bot, torch.full_like(row, H - 1), row))
+        is_left, is_right = k == 4, k == 5
+        col = torch.where(is_left, torch.full_like(col, -1), torch.where(is_right, torch.full_like(col, W - 1), col))
+        kk = torch.where(is_far, 1, torch.where(is_top, 2, torch.where(is_bot, 3, torch.where(is_left, 4, torch.where(
+            is_right, 5, c_near)))))
+        if staged:
+            # rows r, r + 1 and r + cap - 3 .. r + cap - 1 of the query's strip: both sides of either edge of
+            # `r <= floor(h) < r + cap - 1` whichever way the kernel's f32 window rounds
+            r0 = torch.as_tensor(win[strip_of[(q // 16).numpy()], l])[None].expand(B, -1)
+            first = (r0 + (dr % 2)).clamp(-1, H - 1)
+            last = (r0 + caps[l] - 3 + (dr % 3)).clamp(-1, H - 1)
+            row = torch.where(k == 6, first, torch.where(k == 7, last, row))
+            kk = torch.where(k == 6, 6, torch.where(k == 7, 7, kk))
+        cat[:, :, l] = kk
+        corner = (((q // 2)[None] + torch.arange(B)[:, None]) % 2).double() * 0.5          # cell corner every other pair
+        # a corner target on the last row / column would be half outside: fine (zero padding), kept
+        th, tw = row.double() + corner, col.double() + corner
+        ty, tx = (th + 0.5) / H, (tw + 0.5) / W
+        ox, oy = off[:, :, l, 0], off[:, :, l, 1]
+        if ref_dim == 2:
+            refs[:, :, l, 0], refs[:, :, l, 1] = tx - ox / H, ty - oy / W          # the (H, W) normaliser on (x, y)
+        else:
+            refs[:, :, l, 0] = tx - ox / P * refs[:, :, l, 2] * 0.5
+            refs[:, :, l, 1] = ty - oy / P * refs[:, :, l, 3] * 0.5
+    n_tap = M * L * P
+    o = off[:, :, None, :, None, :].expand(B, Lq, M, L, P, 2)
+    offlog[..., :2 * n_tap] = o.reshape(B, Lq, 2 * n_tap).float()
+    m = torch.arange(M)
+    hot_l = (q[:, None] + m[None]) % L
+    hot_p = (q[:, None] // L + m[None]) % P
+    lg = torch.full((B, Lq, M, L * P), MSDA_COLD)
+    lg.scatter_(3, (hot_l * P + hot_p)[None, :, :, None].expand(B, -1, -1, -1), 0.0)
+    offlog[..., 2 * n_tap:] = lg.reshape(B, Lq, n_tap)
+    return {'value': value, 'offlog': offlog, 'refs': refs.float(), 'refs64': refs, 'cat': cat,
+            'hot': hot_l[None].expand(B, -1, -1)}
+
+
+def msda_addr_counts(case, loc, shapes, plan=None, order=None):
+    """From the f64 locations: how many hot samples of each staged (or every, without a plan) level fall in
+    each category -- recomputed from floor(h), floor(w), not taken from the construction.
+    -> {(level, category name): count}."""
+    B, Lq, M, L, P, _ = loc.shape
+    fl, n = plan if plan is not None else (0, 1)
+    caps = msda_enc_caps(shapes, fl, n)
+    S = sum(h * w for h, w in shapes)
+    strip_of, win = msda_enc_windows(shapes, fl, n, order) if plan is not None and Lq == S else (None, None)
+    q = torch.arange(Lq)
+    m = torch.arange(M)
+    hot_l = (q[:, None] + m[None]) % L
+    hot_p = (q[:, None] // L + m[None]) % P
+    counts = {}
+    _, meta = msda_pixel_refs(shapes, 1) if Lq == S else (None, None)
+    for l, (H, W) in enumerate(shapes):
+        sel = hot_l == l                                                         # (Lq, M)
+        lp = loc[:, :, :, l].gather(3, hot_p[None, :, :, None, None].expand(B, -1, -1, 1, 2))[:, :, :, 0]   # (B, Lq, M, 2)
+        hl = torch.floor(lp[..., 1] * H - 0.5 + 1e-3)      # targets sit on multiples of 1/2
+        wl = torch.floor(lp[..., 0] * W - 0.5 + 1e-3)
+        sel = sel[None].expand(B, -1, -1)
+        c = {'row-1': hl == -1, 'rowH-1': hl == H - 1, 'col-1': wl == -1, 'colW-1': wl == W - 1}
+        if meta is not None:
+            own = torch.floor((meta[:, 1].double() + 0.5) / torch.tensor([shapes[i][0] for i in meta[:, 0].tolist()]) * H)
+            dist = (hl - own[None, :, None]).abs()
+            c['near'] = dist <= 2
+            if plan is not None and l >= fl and H > caps[l]:
+                c['far'] = dist > caps[l]
+            if strip_of is not None and l >= fl:
+                r0 = torch.as_tensor(win[strip_of[(q // 16).numpy()], l]).double()[None, :, None]
+                c['win_first'] = (hl >= r0) & (hl <= r0 + 1)
+                c['win_last'] = (hl >= r0 + caps[l] - 3) & (hl <= r0 + caps[l] - 1)
+                c['surely_staged'] = (hl >= r0 + 1) & (hl < r0 + caps[l] - 2)
+                c['surely_far'] = (hl < r0 - 1) | (hl >= r0 + caps[l])
+        for name, mask in c.items():
+            counts[(l, name)] = int((mask & sel).sum())
+    return counts
+
+
+@functools.lru_cache(maxsize=None)
+def msda_generic_case(shapes, B, M, Lq, ref_dim, noise, logits, dtype, D=32, P=4, masked=True, seed=0, f16_offlog=False):
+    """The generic class: randn values rounded to `dtype`, offsets noise * randn (raw units: about `noise`
+    pixels), logits randn or +-8, references the pixel centres (Lq = S) or uniform, 10 % masked queries."""
+    g = torch.Generator().manual_seed(seed + Lq * 13 + M + int(noise * 10) + ref_dim)
+    L = len(shapes)
+    S = sum(h * w for h, w in shapes)
+    value = torch.randn(B, S, M, D, generator=g).to(dtype)
+    n_tap = M * L * P
+    off = noise * torch.randn(B, Lq, 2 * n_tap, generator=g)
+    lg = torch.randn(B, Lq, n_tap, generator=g) if logits == 'randn' else \
+        torch.where(torch.rand(B, Lq, n_tap, generator=g) < 0.5, -8.0, 8.0)
+    offlog = torch.cat([off, lg], -1)
+    if f16_offlog:
+        offlog = offlog.half().float()
+    if Lq == S and ref_dim == 2:
+        refs = msda_pixel_refs(shapes, B)[0].float()
+    else:
+        refs = torch.rand(B, Lq, L, ref_dim, generator=g)
+        if ref_dim == 4:
+            refs[..., 2:] = refs[..., 2:] * 0.5 + 0.05
+    qmask = (torch.rand(B, Lq, generator=g) < 0.1) if masked else None
+    return {'value': value, 'offlog': offlog, 'refs': refs, 'qmask': qmask}
+
+
+def msda_chain_ref(case, shapes, M, P=4):
+    """raw offsets / logits / references / mask -> msda_prep_ref -> msda_sample_ref, nothing else."""
+    L = len(shapes)
+    ss = torch.tensor(shapes, dtype=torch.int64)
+    prep = msda_prep_ref(case['offlog'], case['refs'], ss, case.get('qmask'), M, L, P)
+    samp = msda_sample_ref(case['value'].double(), shapes, prep['loc'], prep['attw'])
+    return prep, samp
+
+
+# ---- bounds ----
+LOC_OPS = 7
+F16_W = 2.0 ** -11            # one rounding of a tap weight to f16
+F16_W_ABS = 2.0 ** -25        # ... of a subnormal one (spacing 2^-24): kinet_amd/build.py passes no flush or
+#                               fast-math flag, and the AMDGPU default float mode keeps f16 subnormals
+
+
+def msda_loc_delta(prep, shapes):
+    """(L,) pixels: the most a kernel's f32 tap location (h, w) of level l can differ from the f64 one.
+    Counted on the longest variant, per axis: the offset term -- 1 / H (a reciprocal), the product with
+    it, or / P * wh * 0.5 -- at most 3 roundings, the sum with the reference point 1, the product with the
+    level size 1, the subtraction of 0.5 1: 6, each relative to at most |ref| + |offset term| (locA of
+    msda_prep_ref) times the level size, + 0.5;  + 1 for the addressing class, whose reference points are
+    themselves rounded to f32 from the exact target: LOC_OPS = 7."""
+    d = []
+    for l, (H, W) in enumerate(shapes):
+        A = prep['locA'][:, :, :, l]
+        d.append(LOC_OPS * U32 * max((A[..., 0] * W).max().item(), (A[..., 1] * H).max().item()) + LOC_OPS * U32)
+    return torch.tensor(d, dtype=torch.float64)
+
+
+# c_acc: relative to A, read off each kernel.
+#   f32 weights, f32 accumulation (msda_fwd_kernel, msda_fused_kernel): 1 - lh, two products: 3; the fma
+#     chain over 16 taps x 4 corners: 64                                           -> 67 * 2^-24
+#   msda_fused_fast_kernel: the same, and the weight rounded to f16                -> + 2^-11
+#   msda_enc_kernel: the weight to f16 (2^-11); per level 16 packed-f16 multiply-adds, each rounding a
+#     partial sum bounded by that level's A: 16 * 2^-11 * A_lvl; the levels' f32 adds, the tail's quad sum: 8
+#   records front end: two packed-f16 products make a weight                       -> 2 * 2^-11
+#   f16 subnormals (results below 2^-14, spacing 2^-24) round absolutely: F16_W_ABS per tap weight (times the
+#     corner's |v|: V), per packed-f16 multiply-add (64 behind an element of the strip kernel) and for an f16 output
+C_ACC_F32 = 67 * U32
+
+
+def msda_addr_bound(samp, shapes, kernel, locA):
+    """The addressing class through offsets and references: |d| <= sum_l G_l d_l, plus what keeps the bound
+    sound where G is 0 (a flat neighbourhood): the hot corner's weight product, C_ACC_F32 A, and for the
+    kernels that round it to f16 F16_W A -- at most 2^-11 * 32 = 1/64.  No accumulation or output term:
+    the expected values are integers of at most 6 bits, every partial sum and the output lie within the
+    terms above of one, and rounding to nearest cannot move a number away from a representable
+    neighbour.  A wrong pixel is off by at least 1 (corner targets) or 4 (centre targets)."""
+    d = msda_loc_delta({'locA': locA}, shapes)
+    assert d.max().item() < 0.125, 'the geometry is wrong, not the bound'
+    c = C_ACC_F32 + (0.0 if kernel == 'f32' else F16_W)
+    return (samp['G_lvl'] * d.view(-1, 1, 1, 1)).sum(0) + c * samp['A'] + 1e-30
+
+
+def msda_bound(samp, shapes, kernel, out_dtype, locA=None, attw_c=None):
+    """Per-element bound of |kernel - samp['out']|: c_acc A + out_round |ref| + the subnormal tap weights'
+    F16_W_ABS V (f16-weight kernels) + sum_l G_l d_l (locA given: msda_loc_delta) + the attention weights'
+    (attw_c + 2) u A (attw_c of msda_prep_ref given; + 2: a reciprocal and a product for the divide).
+    kernel: 'f32', 'fast', 'strip' or 'records'.  The records front end passes neither: its reference
+    samples the decoded records.  The addressing class passes no attw_c: its softmax is exactly (1, 0, ...)."""
+    A, ref = samp['A'], samp['out']
+    # an f16 result below 2^-14 is subnormal: its rounding is absolute, F16_W_ABS, not relative -- the output
+    # itself, and in the strip kernel each of the 64 packed-f16 multiply-adds behind an element
+    b = OUT_ROUND[out_dtype] * ref.abs() + (F16_W_ABS if out_dtype == torch.float16 else 0.0)
+    if kernel == 'f32':
+        b = b + C_ACC_F32 * A
+    elif kernel == 'fast':
+        b = b + (C_ACC_F32 + F16_W) * A + F16_W_ABS * samp['V']
+    else:
+        nw = 2 if kernel == 'records' else 1
+        b = b + (nw * F16_W + 8 * U32) * A + 16 * F16_W * samp['A_lvl'].sum(0) + nw * F16_W_ABS * samp['V'] + 64 * F16_W_ABS
+    if locA is not None:
+        b = b + (samp['G_lvl'] * msda_loc_delta({'locA': locA}, shapes).view(-1, 1, 1, 1)).sum(0)
+    if attw_c is not None:
+        B, Lq, M = attw_c.shape[:3]
+        c = (attw_c.amax((3, 4)) + 2) * U32
+        b = b + (c[..., None] * A.reshape(B, Lq, M, -1)).reshape(A.shape)
+    return b + 1e-30

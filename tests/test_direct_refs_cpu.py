@@ -1,5 +1,6 @@
 """CPU checks of tests/direct_refs.py: the references the direct kernel tests compare against,
 so a wrong helper cannot be blamed on a kernel."""
+import functools
 import math
 
 import numpy as np
@@ -920,3 +921,245 @@ def test_rw_conv_cases_exact_and_bounded(name):
         # the rows of one output row taken from the row above (a wrong carry at the row's end) leave it
         bad = torch.roll(v.view(2, 4, 33, Cout), 1, 1).reshape(-1, Cout)
         assert ((bad.to(dt).double() - pre).abs() > bound).float().mean() > 0.25
+
+
+# ============================================================ MSDA forward sampling
+def _shapes(a):
+    return tuple((int(h), int(w)) for h, w in np.asarray(a).tolist())
+
+
+@pytest.mark.parametrize('name', ['msda_kat_f32.npz', 'msda_kat_f64.npz', 'msda_mid_d32.npz', 'msda_mid_d36.npz'])
+def test_msda_sample_ref_equals_both_oracles(golden_dir, name):
+    import os
+    from oracle import msda_oracle as O
+    d = dict(np.load(os.path.join(golden_dir, name)))
+    v, loc, aw = (torch.from_numpy(d[k]).double() for k in ('value', 'loc', 'attw'))
+    r = R.msda_sample_ref(v, _shapes(d['shapes']), loc, aw)
+    scale = r['A'].max().item()
+    assert (r['out'] - torch.from_numpy(O.fwd(v.numpy(), d['shapes'], loc.numpy(), aw.numpy()))).abs().max().item() <= 1e-14 * scale
+    assert (r['out'] - O.core_pytorch(v, d['shapes'], loc, aw)).abs().max().item() <= 1e-13 * scale
+    assert (r['out'].abs() <= r['A'] * (1 + 1e-12)).all() and torch.allclose(r['A_lvl'].sum(0), r['A'])
+
+
+def test_msda_sample_ref_on_the_padding_edges():
+    """Samples exactly at h = -1, -0.5, H - 0.5 and H (and the same in w): the validity test's open
+    ends and the half-outside footprints, against both oracles."""
+    from oracle import msda_oracle as O
+    shapes = ((5, 7), (3, 4))
+    g = torch.Generator().manual_seed(3)
+    S = sum(h * w for h, w in shapes)
+    B, M, D, P = 1, 2, 4, 4
+    v = torch.randn(B, S, M, D, generator=g).double()
+    hs = [-1.0, -0.5, 0.0, 'H-0.5', 'H']
+    loc = torch.zeros(B, len(hs) ** 2, M, 2, P, 2, dtype=torch.float64)
+    for l, (H, W) in enumerate(shapes):
+        for i, hh in enumerate(hs):
+            for j, ww in enumerate(hs):
+                h = {'H-0.5': H - 0.5, 'H': float(H)}.get(hh, hh)
+                w = {'H-0.5': W - 0.5, 'H': float(W)}.get(ww, ww)
+                loc[0, i * len(hs) + j, :, l, :, 0] = (w + 0.5) / W
+                loc[0, i * len(hs) + j, :, l, :, 1] = (h + 0.5) / H
+    aw = torch.rand(B, len(hs) ** 2, M, 2, P, generator=g).double()
+    r = R.msda_sample_ref(v, shapes, loc, aw)
+    ss = np.array(shapes, dtype=np.int64)
+    assert (r['out'] - torch.from_numpy(O.fwd(v.numpy(), ss, loc.numpy(), aw.numpy()))).abs().max().item() <= 1e-14
+    # grid_sample's own coordinate arithmetic (2 loc - 1, unnormalised again) moves a knot by an ulp: its
+    # error is the slope times that, not f64 rounding of the sum
+    assert ((r['out'] - O.core_pytorch(v, ss, loc, aw)).abs() <= r['G'] * 1e-13 + 1e-14).all()
+    # h = -1 and h = H add nothing; h = -0.5 keeps half of row 0
+    assert (r['out'][0, :len(hs)] == 0).all() and (r['out'][0, -len(hs):] == 0).all()
+    assert (r['out'][0, len(hs) + 2] != 0).all()
+
+
+def test_msda_slope_covers_a_location_error():
+    """G d bounds the change under a perturbation of every tap by up to d pixels per axis, across cell
+    borders and the padding edges: 1,000 random taps, d from 1e-6 to 0.9."""
+    shapes = ((6, 9), (4, 5), (3, 3), (2, 2))
+    g = torch.Generator().manual_seed(11)
+    S = sum(h * w for h, w in shapes)
+    B, Lq, M, D, P = 1, 63, 1, 3, 4            # 63 * 16 = 1,008 taps
+    v = torch.randn(B, S, M, D, generator=g).double()
+    loc = torch.rand(B, Lq, M, 4, P, 2, generator=g).double() * 1.6 - 0.3
+    # a third of the taps on cell borders and the padding edges
+    for l, (H, W) in enumerate(shapes):
+        knots = (torch.randint(-1, H + 1, (B, Lq, M, P), generator=g).double() + 0.5) / H
+        on = torch.rand(B, Lq, M, P, generator=g) < 0.33
+        loc[:, :, :, l, :, 1] = torch.where(on, knots, loc[:, :, :, l, :, 1])
+    aw = torch.rand(B, Lq, M, 4, P, generator=g).double()
+    r = R.msda_sample_ref(v, shapes, loc, aw)
+    size = torch.tensor([[w, h] for h, w in shapes], dtype=torch.float64).view(1, 1, 1, 4, 1, 2)
+    for d in (1e-6, 1e-3, 0.124, 0.9):
+        for _ in range(3):
+            step = (torch.rand(loc.shape, generator=g).double() * 2 - 1) * d
+            step = torch.where(torch.rand(loc.shape, generator=g) < 0.5, step.sign() * d, step)
+            moved = R.msda_sample_ref(v, shapes, loc + step / size, aw)['out']
+            assert ((moved - r['out']).abs() <= r['G'] * d * (1 + 1e-9) + 1e-14).all(), d
+    # and it is not vacuous: a full pixel exceeds G * 1e-3 nearly everywhere
+    moved = R.msda_sample_ref(v, shapes, loc + 1.0 / size, aw)['out']
+    assert ((moved - r['out']).abs() > r['G'] * 1e-3).float().mean() > 0.9
+
+
+@pytest.fixture
+def strips():
+    """msda_encoder_set_strips for one test, restored afterwards."""
+    from kinet_amd import kernels as K
+    old = K.msda_encoder_set_strips(0)
+    yield K.msda_encoder_set_strips
+    K.msda_encoder_set_strips(old)
+
+
+@pytest.mark.parametrize('case', R.MSDA_ENC_CASES, ids=lambda c: '-'.join(map(str, c[:5])))
+def test_msda_encoder_plan_table(strips, case):
+    """Every literal row of MSDA_ENC_CASES against kinet_msda_encoder_plan_ex (no GPU: the planner
+    assumes 256 compute units), and the windows' restatement against the plan's size."""
+    from kinet_amd import kernels as K
+    name, B, M, ch, forced, want = case
+    shapes = R.MSDA_ENC_GEO[name]
+    S = sum(h * w for h, w in shapes)
+    strips(forced)
+    got = K.msda_encoder_plan(shapes, B, M, S, ch)
+    assert got is not None and got[:3] == want and got[3] == B * M * want[1], (got, want)
+    fl, n, used = want
+    caps = R.msda_enc_caps(shapes, fl, n)
+    ceil16 = lambda x: (x + 15) // 16 * 16
+    assert used == ceil16(max(w for _, w in shapes[fl:]) + 2) + sum(ceil16(c * w + 2) for c, (_, w) in zip(caps, shapes) if c)
+    assert used <= (R.ENC_TAIL if ch == 36 else R.ENC_MAIN)
+    strip_of, win = R.msda_enc_windows(shapes, fl, n)
+    assert sorted(set(strip_of.tolist())) == list(range(n))
+    for l in range(fl, 4):
+        assert ((win[:, l] >= -1) & (win[:, l] + caps[l] - 1 <= shapes[l][0])).all()
+
+
+def test_msda_encoder_plan_refusal(strips):
+    from kinet_amd import kernels as K
+    shapes = R.MSDA_ENC_REFUSED
+    S = sum(h * w for h, w in shapes)
+    for forced in (0, 4):
+        strips(forced)
+        assert K.msda_encoder_plan(shapes, 1, 8, S) is None and K.msda_encoder_plan(shapes, 1, 8, S, 36) is None
+
+
+def test_msda_plan_table_reaches_every_plan():
+    fls = {(c[5][0], c[3]) for c in R.MSDA_ENC_CASES}
+    assert {(f, 32) for f in range(4)} <= fls and (3, 36) in fls and (1, 36) in fls
+    # staged levels taller than their window (the far path is reachable) under fl = 0 and fl >= 1
+    tall = {c[5][0] for c in R.MSDA_ENC_CASES
+            if any(cap and cap < h for cap, (h, _) in zip(R.msda_enc_caps(R.MSDA_ENC_GEO[c[0]], c[5][0], c[5][1]),
+                                                         R.MSDA_ENC_GEO[c[0]]))}
+    assert {0, 1} <= tall
+    # 8 and 10 fraction bits of the records
+    assert max(w for _, w in R.MSDA_ENC_GEO['wide1']) > 128 >= max(w for _, w in R.MSDA_ENC_GEO['all'])
+
+
+# ---- the tests can fail: emulated defects in a copy of the reference chain ----
+def _defective_chain(case, shapes, M, defect, plan=None, P=4):
+    """msda_prep_ref + msda_sample_ref restated with one defect switched on (None: the faithful copy)."""
+    L = len(shapes)
+    offlog, refs, qmask = case['offlog'].double(), case['refs'].double(), case.get('qmask')
+    B, Lq = offlog.shape[:2]
+    n = M * L * P
+    o = offlog[..., :2 * n].reshape(B, Lq, M, L, P, 2)
+    lg = offlog[..., 2 * n:].reshape(B, Lq, M, L, P)
+    a = (torch.softmax(lg, -1) if defect == 'softmax4' else torch.softmax(lg.reshape(B, Lq, M, L * P), -1)).reshape(B, Lq, M, L, P)
+    if qmask is not None and defect != 'mask':
+        a = a.masked_fill(qmask[:, :, None, None, None], 0.0)
+    if defect == 'drop23':
+        a = a.clone()
+        a[:, :, :, 2, 3] = 0
+    sh = torch.tensor(shapes, dtype=torch.float64)
+    div = sh.flip(1) if defect == 'xbyW' else sh
+    rxy = refs[..., :2][:, :, None, :, None, :]
+    loc = rxy + (o / div[None, None, None, :, None, :] if refs.shape[-1] == 2
+                 else o / P * refs[..., 2:][:, :, None, :, None, :] * 0.5)
+    value = case['value'].double()
+    D = value.shape[-1]
+    fl, ns = plan if plan is not None else (L, 1)
+    caps = R.msda_enc_caps(shapes, fl, ns)
+    strip_of, win = R.msda_enc_windows(shapes, fl, ns) if plan is not None else (None, None)
+    bi, mi = torch.arange(B).view(B, 1, 1, 1), torch.arange(M).view(1, 1, M, 1)
+    out = torch.zeros(B, Lq, M, D, dtype=torch.float64)
+    start = 0
+    for l, (H, W) in enumerate(shapes):
+        s0 = start + (W if defect == 'start' and l else 0)
+        v = value[:, s0:s0 + H * W]
+        v = torch.cat([v, value[:, :H * W - v.shape[1]]], 1)            # (the shifted last level wraps)
+        h = loc[:, :, :, l, :, 1] * H - 0.5
+        w = loc[:, :, :, l, :, 0] * W - 0.5
+        valid = (h > -1) & (w > -1) & (h < H) & (w < W)
+        hl, wl = torch.floor(h), torch.floor(w)
+        lh, lw = h - hl, w - wl
+        if defect == 'swap':
+            lw = 1 - lw
+        far = short = torch.zeros_like(valid)
+        if strip_of is not None and l >= fl:
+            r0 = torch.as_tensor(win[strip_of[(torch.arange(Lq) // 16).numpy()], l]).double()[None, :, None, None]
+            far = (hl < r0) | (hl >= r0 + caps[l] - 1)
+            short = hl == r0 + caps[l] - 2
+        for dy, wy in ((0, 1 - lh), (1, lh)):
+            for dx, wx in ((0, 1 - lw), (1, lw)):
+                r, c = hl + dy, wl + dx
+                ok = valid & (r >= 0) & (r < H) & (c >= 0) & (c < W) if defect != 'clamp' else valid
+                if defect == 'short' and dy == 1:
+                    ok = ok & ~short
+                idx = (r.clamp(0, H - 1) * W + c.clamp(0, W - 1)).long()
+                if defect == 'far' and dy == 1 and dx == 1:
+                    idx = torch.where(far, (idx + 1).clamp(max=H * W - 1), idx)
+                vc = v[bi, idx, mi]
+                if defect == 'tail':
+                    vc = torch.cat([vc[..., :32], v[bi, (idx + 1).clamp(max=H * W - 1), mi][..., 32:]], -1)
+                out += ((a[:, :, :, l] * wy * wx * ok)[..., None] * vc).sum(3)
+        start += H * W
+    return out.reshape(B, Lq, M * D)
+
+
+# defect -> (class, head_dim, the named case): 'addr' = MSDA_ENC_GEO['all'] with 3 strips (Lq = S, B = 1,
+# M = 8), 'generic' = the same geometry, 3-pixel offsets, randn logits, 10 % masked queries
+DEFECTS = {'xbyW': ('addr', 32), 'start': ('addr', 32), 'short': ('addr', 32), 'swap': ('generic', 32),
+           'clamp': ('addr', 32), 'drop23': ('addr', 32), 'tail': ('addr', 36), 'mask': ('generic', 32),
+           'far': ('addr', 32), 'softmax4': ('generic', 32)}
+
+
+@functools.lru_cache(maxsize=None)
+def _defect_case(cls, D):
+    shapes, M, plan = R.MSDA_ENC_GEO['all'], 8, (0, 3)
+    S = sum(h * w for h, w in shapes)
+    if cls == 'addr':
+        case = R.msda_addr_case(shapes, 1, M, S, 2, D=D, plan=plan)
+    else:
+        case = R.msda_generic_case(shapes, 1, M, S, 2, 3.0, 'randn', torch.float16, D=D)
+    prep, samp = R.msda_chain_ref(case, shapes, M)
+    # the loosest bound a test of this class applies (the strip kernel's, bf16 output)
+    bound = R.msda_addr_bound(samp, shapes, 'strip', prep['locA']) if cls == 'addr' else \
+        R.msda_bound(samp, shapes, 'strip', torch.bfloat16, prep['locA'], prep['attw_c'])
+    return case, shapes, M, plan, samp, bound
+
+
+@pytest.mark.parametrize('defect', [None] + sorted(DEFECTS))
+def test_msda_emulated_defects_are_caught(defect):
+    cls, D = DEFECTS.get(defect, ('addr', 32))
+    for c in ([cls] if defect else ['addr', 'generic']):
+        case, shapes, M, plan, samp, bound = _defect_case(c, D)
+        out = _defective_chain(case, shapes, M, defect, plan)
+        bad = (out - samp['out']).abs() > bound
+        if defect is None:
+            assert (out - samp['out']).abs().max().item() <= 1e-12      # the copy is faithful
+        else:
+            assert bad.any(), defect
+            print(defect, c, 'elements outside the bound:', int(bad.sum()), 'of', bad.numel())
+
+
+@pytest.mark.parametrize('noise,logits', [(0.5, 'randn'), (3.0, 'pm8'), (25.0, 'randn')])
+def test_msda_generic_bound_has_headroom(noise, logits):
+    """torch's own f32 evaluation (softmax, locations, grid_sample) stays inside the TIGHTEST generic bound
+    (f32 weights and accumulation, f32 output)."""
+    from oracle import msda_oracle as O
+    shapes, M = R.MSDA_ENC_GEO['all'], 8
+    S = sum(h * w for h, w in shapes)
+    case = R.msda_generic_case(shapes, 1, M, S, 2, noise, logits, torch.float32)
+    prep, samp = R.msda_chain_ref(case, shapes, M)
+    loc, aw = O.prep(case['offlog'], case['refs'], shapes, case['qmask'], M, 4, 4)
+    out = O.core_pytorch(case['value'], shapes, loc, aw)
+    bound = R.msda_bound(samp, shapes, 'f32', torch.float32, prep['locA'], prep['attw_c'])
+    ratio = ((out.double() - samp['out']).abs() / bound).max().item()
+    print('torch f32 err / bound:', ratio)
+    assert ratio < 1
