@@ -69,6 +69,22 @@ int kinet_segm_out_conv(const void* x, const float* wt, const float* bias, float
 int kinet_segm_postprocess(const float* logits, void* out, int Q, int h, int w, int max_h, int max_w, int img_h,
                            int img_w, int oh, int ow, float threshold, int return_probs, kinet_stream_t stream);
 
+/* Tracker masks (the reference tracker's stack / argmax / compare, tracker.py:515-527) for one frame,
+ * without the per-track probability maps: every output pixel gets the slot of the track that owns it.
+ *   p_t = fresh slot (src[t] >= 0):  the probability kinet_segm_postprocess gives row src[t] of logits
+ *         stale slot (src[t] <  0):  1.0f where prev_labels[Y, X] == -src[t]-1, else 0.0f
+ *   best = the first t of maximal p_t (torch.argmax: NaN is the greatest, the first occurrence wins)
+ *   labels[Y, X] = p_best > threshold ? best : -1
+ * so track slot t's exclusive mask is labels == t.  A stale slot is a track that kept last frame's
+ * resolved bool mask: torch.stack promotes it to 1.0 / 0.0 among the fresh probabilities.
+ * logits (n, h, w) f32 (NULL when n == 0); src T ints on the device (NULL when T == 0); prev_labels
+ * (oh, ow) int16 or NULL (every stale slot is then empty); labels (oh, ow) int16, another buffer
+ * than prev_labels.  T <= 32767; T == 0 writes -1 everywhere.  A fresh slot >= n counts as 0.0 and
+ * reads nothing.  Every pixel is local: reruns are bit-identical. */
+int kinet_segm_track_resolve(const float* logits, const int32_t* src, const int16_t* prev_labels, int16_t* labels,
+                             int T, int n, int h, int w, int max_h, int max_w, int img_h, int img_w, int oh, int ow,
+                             float threshold, kinet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,6 +112,7 @@ _SIGS = {
     'kinet_segm_gn_relu_up_add': [P] * 5 + [I] * 10 + [F, I, P, P],
     'kinet_segm_out_conv': [P, P, P, P, I, I, I, I, I, P],
     'kinet_segm_postprocess': [P, P] + [I] * 9 + [F, I, P],
+    'kinet_segm_track_resolve': [P, P, P, P] + [I] * 10 + [F, P],
     'kinet_last_error': [],
     'kinet_version': [],
 }

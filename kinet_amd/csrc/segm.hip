@@ -362,6 +362,36 @@ __device__ __forceinline__ void bilinear_src(int dst, float scale, int in, int& 
     i1 = i0 + (i0 < in - 1 ? 1 : 0);
 }
 
+// One output pixel's four taps and weights: the legacy-nearest map of (oy, ox) into the cropped
+// (img_h, img_w) probability map, then the bilinear source position in the (h, w) logits.
+struct SegmTap {
+    long o00, o01, o10, o11;   // offsets inside one (h, w) row of logits
+    float ly, lx;
+};
+
+__device__ __forceinline__ SegmTap segm_tap(int oy, int ox, int h, int w, int img_h, int img_w, float bh, float bw,
+                                            float nh, float nw) {
+    // nearest source pixel inside the cropped (img_h, img_w) probability map
+    const int my = min((int)floorf((float)oy * nh), img_h - 1);
+    const int mx = min((int)floorf((float)ox * nw), img_w - 1);
+    int y0, y1, x0, x1;
+    SegmTap t;
+    bilinear_src(my, bh, h, y0, y1, t.ly);
+    bilinear_src(mx, bw, w, x0, x1, t.lx);
+    t.o00 = (long)y0 * w + x0, t.o01 = (long)y0 * w + x1;
+    t.o10 = (long)y1 * w + x0, t.o11 = (long)y1 * w + x1;
+    return t;
+}
+
+// sigmoid of the bilinear sample of one row of logits: the per-pixel probability of PostProcessSegm,
+// shared by segm_postprocess_kernel and segm_track_resolve_kernel so that both round alike
+__device__ __forceinline__ float segm_prob(const float* __restrict__ p, const SegmTap& t) {
+    const float top = (1.f - t.lx) * p[t.o00] + t.lx * p[t.o01];
+    const float bot = (1.f - t.lx) * p[t.o10] + t.lx * p[t.o11];
+    const float v = (1.f - t.ly) * top + t.ly * bot;
+    return 1.f / (1.f + expf(-v));
+}
+
 template <bool PROBS>
 __global__ __launch_bounds__(256) void segm_postprocess_kernel(const float* __restrict__ logits, void* __restrict__ out,
                                                                long total, int h, int w, int img_h, int img_w, int oh,
@@ -372,20 +402,46 @@ __global__ __launch_bounds__(256) void segm_postprocess_kernel(const float* __re
         const long t = i / ow;
         const int oy = (int)(t % oh);
         const long q = t / oh;
-        // nearest source pixel inside the cropped (img_h, img_w) probability map
-        const int my = min((int)floorf((float)oy * nh), img_h - 1);
-        const int mx = min((int)floorf((float)ox * nw), img_w - 1);
-        int y0, y1, x0, x1;
-        float ly, lx;
-        bilinear_src(my, bh, h, y0, y1, ly);
-        bilinear_src(mx, bw, w, x0, x1, lx);
-        const float* p = logits + q * h * w;
-        const float top = (1.f - lx) * p[(long)y0 * w + x0] + lx * p[(long)y0 * w + x1];
-        const float bot = (1.f - lx) * p[(long)y1 * w + x0] + lx * p[(long)y1 * w + x1];
-        const float v = (1.f - ly) * top + ly * bot;
-        const float prob = 1.f / (1.f + expf(-v));
+        const SegmTap tap = segm_tap(oy, ox, h, w, img_h, img_w, bh, bw, nh, nw);
+        const float prob = segm_prob(logits + q * h * w, tap);
         if (PROBS) ((float*)out)[i] = prob;
         else ((uint8_t*)out)[i] = prob > threshold ? 1 : 0;
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// Tracker masks: one thread per output pixel resolves the T track slots into one label.  Slot t is
+// fresh (src[t] >= 0: the probability of row src[t] of logits) or stale (src[t] < 0: 1.0 where the
+// previous label map holds slot -src[t]-1, else 0.0); the label is torch's argmax over the slots
+// (first occurrence of the maximum, NaN the greatest) where that maximum exceeds the threshold.
+// The taps are formed once per pixel; src is read with wave-uniform addresses.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void segm_track_resolve_kernel(const float* __restrict__ logits,
+                                                                 const int32_t* __restrict__ src,
+                                                                 const int16_t* __restrict__ prev,
+                                                                 int16_t* __restrict__ labels, int T, int n, long total,
+                                                                 int h, int w, int img_h, int img_w, int ow, float bh,
+                                                                 float bw, float nh, float nw, float threshold) {
+    const long hw = (long)h * w;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int ox = (int)(i % ow);
+        const int oy = (int)(i / ow);
+        const SegmTap tap = segm_tap(oy, ox, h, w, img_h, img_w, bh, bw, nh, nw);
+        const int was = prev ? (int)prev[i] : -1;
+        int best = -1;
+        float pbest = 0.f;
+        for (int t = 0; t < T; ++t) {
+            const int s = src[t];
+            float p;
+            if (s >= 0) p = s < n ? segm_prob(logits + (long)s * hw, tap) : 0.f;   // (a row outside logits is never read)
+            else p = was == -s - 1 ? 1.f : 0.f;
+            // argmax: a NaN is taken once and then kept; otherwise strictly greater replaces
+            if (best < 0 || (pbest == pbest && (p > pbest || p != p))) {
+                best = t;
+                pbest = p;
+            }
+        }
+        labels[i] = pbest > threshold ? (int16_t)best : (int16_t)-1;
     }
 }
 
@@ -505,6 +561,27 @@ extern "C" int kinet_segm_postprocess(const float* logits, void* out, int Q, int
     else
         hipLaunchKernelGGL((segm_postprocess_kernel<false>), dim3(segm_grid(total)), dim3(256), 0, (hipStream_t)stream,
                            logits, out, total, h, w, img_h, img_w, oh, ow, bh, bw, nh, nw, threshold);
+    KINET_LAUNCH_CHECK();
+    return KINET_OK;
+}
+
+extern "C" int kinet_segm_track_resolve(const float* logits, const int32_t* src, const int16_t* prev_labels,
+                                        int16_t* labels, int T, int n, int h, int w, int max_h, int max_w, int img_h,
+                                        int img_w, int oh, int ow, float threshold, kinet_stream_t stream) {
+    KINET_CHECK_ARG(T >= 0 && n >= 0 && h > 0 && w > 0 && max_h > 0 && max_w > 0 && oh > 0 && ow > 0,
+                    "segm_track_resolve: bad geometry");
+    KINET_CHECK_ARG(T <= 32767, "segm_track_resolve: at most 32767 track slots (labels are int16)");
+    KINET_CHECK_ARG(img_h > 0 && img_h <= max_h && img_w > 0 && img_w <= max_w,
+                    "segm_track_resolve: the frame's size must lie inside (max_h, max_w)");
+    KINET_CHECK_ARG(labels != nullptr, "segm_track_resolve: null pointer (labels)");
+    KINET_CHECK_ARG(T == 0 || src != nullptr, "segm_track_resolve: null pointer (src)");
+    KINET_CHECK_ARG(n == 0 || logits != nullptr, "segm_track_resolve: null pointer (logits)");
+    KINET_CHECK_ARG(labels != prev_labels, "segm_track_resolve: labels and prev_labels must be two buffers");
+    const long total = (long)oh * ow;
+    const float bh = (float)h / (float)max_h, bw = (float)w / (float)max_w;
+    const float nh = (float)img_h / (float)oh, nw = (float)img_w / (float)ow;
+    hipLaunchKernelGGL(segm_track_resolve_kernel, dim3(segm_grid(total)), dim3(256), 0, (hipStream_t)stream, logits, src,
+                       prev_labels, labels, T, n, total, h, w, img_h, img_w, ow, bh, bw, nh, nw, threshold);
     KINET_LAUNCH_CHECK();
     return KINET_OK;
 }

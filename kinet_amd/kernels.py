@@ -1681,3 +1681,40 @@ def segm_postprocess(logits, max_hw, img_hw, out_hw, threshold=0.5, return_probs
            int(img_hw[0]), int(img_hw[1]), oh, ow, float(threshold), int(return_probs), N.stream(logits.device),
            work={'family': 'segm', 'bytes': out.numel() * out.element_size()})
     return out
+
+
+def segm_track_resolve(logits, src, prev_labels, max_hw, img_hw, out_hw, threshold=0.5, out=None):
+    """The tracker's overlap resolution for one frame (kinet_segm_track_resolve): logits (n, h, w) f32
+    fresh mask logits, `src` a HOST sequence of T ints (>= 0: a row of logits, < 0: slot -s-1 of
+    prev_labels), prev_labels (oh, ow) int16 or None -> (oh, ow) int16 labels, -1 = background,
+    labels == t the exclusive mask of slot t.  `src` may also be a device int32 tensor (not checked)."""
+    N.require_gpu(logits, prev_labels, out)
+    logits = logits.float().contiguous()
+    n, h, w = logits.shape
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    if torch.is_tensor(src):
+        if src.dtype != torch.int32 or not src.is_cuda:
+            raise RuntimeError('segm_track_resolve: a tensor src must be int32 on the GPU')
+        src_dev, T = src.contiguous(), src.numel()
+    else:
+        src = [int(s) for s in src]
+        T = len(src)
+        if any(s >= n for s in src):
+            raise RuntimeError(f'segm_track_resolve: a fresh slot names a row outside the {n} rows of logits')
+        if any(s < 0 for s in src):
+            if prev_labels is None:
+                raise RuntimeError('segm_track_resolve: a stale slot needs prev_labels')
+            if any(-s - 1 > 32767 for s in src):
+                raise RuntimeError('segm_track_resolve: a stale slot names a slot beyond int16')
+        src_dev = torch.tensor(src, dtype=torch.int32, device=logits.device) if T else None
+    if prev_labels is not None and (prev_labels.dtype != torch.int16 or tuple(prev_labels.shape) != (oh, ow)
+                                    or not prev_labels.is_contiguous()):
+        raise RuntimeError('segm_track_resolve: prev_labels must be contiguous int16 (oh, ow)')
+    if out is None:
+        out = torch.empty((oh, ow), dtype=torch.int16, device=logits.device)
+    elif out.dtype != torch.int16 or tuple(out.shape) != (oh, ow) or not out.is_contiguous():
+        raise RuntimeError('segm_track_resolve: out must be contiguous int16 (oh, ow)')
+    N.call('kinet_segm_track_resolve', N.ptr(logits) if n else None, N.ptr(src_dev), N.ptr(prev_labels), N.ptr(out),
+           T, n, h, w, int(max_hw[0]), int(max_hw[1]), int(img_hw[0]), int(img_hw[1]), oh, ow, float(threshold),
+           N.stream(logits.device), work={'family': 'segm', 'bytes': out.numel() * 4})
+    return out

@@ -18,6 +18,10 @@ Rows are frame-major (row b*Q + q, `_expand` of :101-102).  The head runs over c
 (`mask_query_chunk`, None = sized to `MASK_WORKSPACE_BYTES`); nothing reduces across rows and no
 kernel choice depends on the chunk (split-K is off), so pred_masks does not depend on the chunking.
 
+`defer_masks` (the tracker's MOTS path): forward returns `out` without 'pred_masks' and keeps the
+head's operands until the next forward; `mask_logits(rows, frame)` then runs the attention map and
+the head on the chosen query rows only, bit-identical to those rows of the full head.
+
 Not built (NotImplementedError): the training forward and the mask losses, vanilla DETRSegm,
 masks with two_stage, PostProcessPanoptic.  Reference defect: DETRSegmBase.forward(samples,
 targets) drops `prev_features`, so the reference tracker's three-argument call (tracker.py:309) is
@@ -136,8 +140,10 @@ class MaskHeadSmallConv(nn.Module):
         if not fast_path(self):
             raise NotImplementedError('the segmentation head runs the inference path only (eval mode under '
                                       'torch.no_grad())')
-        frame = self.frame_part(src)
-        adapted = self.adapters(fpns)
+        return self.run(att, self.frame_part(src), self.adapters(fpns), Q, chunk)
+
+    def run(self, att, frame, adapted, Q, chunk=None):
+        """The head over all rows of att in chunks, on per-frame operands that are already computed."""
         R = att.shape[0]
         H, W = adapted[2].shape[1:3]
         out = torch.empty((R, H, W), dtype=torch.float32, device=att.device)
@@ -171,6 +177,8 @@ class DETRSegmBase(nn.Module):
         self.mask_query_chunk = None    # rows of (frame, query) per pass of the head; None = by workspace bound
         self.keep_attention = False     # True: keep the last attention map as self.last_attention
         self.last_attention = None
+        self.defer_masks = False        # True: forward returns no 'pred_masks'; mask_logits(rows) runs the head
+        self._mask_ctx = None           # the last deferred forward's operands, valid until the next forward
 
     @property
     def fpn_channels(self):
@@ -202,6 +210,11 @@ class DETRSegmBase(nn.Module):
             raise RuntimeError('segmentation head: memory level and layer-3 feature differ in size')
         Q = hs.shape[2]
         k_rows = memory.flatten(2).permute(0, 2, 1)                       # (B, h*w, d) rows of the level
+        self._mask_ctx = None
+        if self.defer_masks:
+            self._mask_ctx = {'hs': hs[-1], 'k_rows': k_rows, 'mask': mask.flatten(1), 'src': src, 'fpns': fpns,
+                              'hw': (h, w)}
+            return out, targets, features, memory, hs
         att = self.bbox_attention(hs[-1], k_rows, mask.flatten(1))        # (B*Q, h*w, heads)
         att = att.view(B * Q, h, w, -1)
         if self.keep_attention:
@@ -209,6 +222,41 @@ class DETRSegmBase(nn.Module):
         seg = self.mask_head(src, att, fpns, Q, self.mask_query_chunk)
         out['pred_masks'] = seg.view(B, Q, seg.shape[-2], seg.shape[-1])
         return out, targets, features, memory, hs
+
+    @torch.no_grad()
+    def mask_logits(self, rows, frame=0):
+        """pred_masks[frame, rows] of the last forward run with defer_masks: rows is a device int64
+        tensor of query rows (any order, repeats allowed) -> (len(rows), H/4, W/4) f32, bit-identical
+        to the rows of the full head.  The per-frame operands (k_linear of the level, lay1's frame
+        part, the adapters) and q_linear over ALL rows are computed at the first call after a forward,
+        by the calls the full head makes, so no GEMM sees another shape than there; the attention map
+        and the head then run on the chosen rows as one frame of len(rows) queries."""
+        ctx = self._mask_ctx
+        if ctx is None:
+            raise RuntimeError('mask_logits needs a forward with defer_masks set (and none since without it)')
+        hs = ctx['hs']
+        B, Q, d = hs.shape
+        if not 0 <= int(frame) < B:
+            raise IndexError(f'mask_logits: frame {frame} outside the {B} frames of the last forward')
+        if rows.dtype != torch.int64 or rows.dim() != 1:
+            raise RuntimeError('mask_logits: rows must be a 1-d int64 tensor')
+        n = rows.numel()
+        if n == 0:      # (no launch: the stride-4 backbone feature has the logits' size)
+            return torch.empty((0,) + tuple(ctx['fpns'][2].shape[1:3]), dtype=torch.float32, device=hs.device)
+        if 'qp' not in ctx:
+            att_mod = self.bbox_attention
+            ctx['qp'] = K.linear(hs.reshape(B * Q, d), att_mod.q_linear.weight, att_mod.q_linear.bias)
+            ctx['kp'] = K.linear(ctx['k_rows'].reshape(-1, d), att_mod.k_linear.weight,
+                                 att_mod.k_linear.bias).view(B, -1, att_mod.hidden_dim)
+            ctx['frame'] = self.mask_head.frame_part(ctx['src'])
+            ctx['adapted'] = self.mask_head.adapters(ctx['fpns'])
+        b = int(frame)
+        h, w = ctx['hw']
+        qp = ctx['qp'].view(B, Q, -1)[b].index_select(0, rows.to(hs.device))
+        att = K.segm_attention(qp, ctx['kp'][b:b + 1], ctx['mask'][b:b + 1], n, self.bbox_attention.num_heads)
+        att = att.view(n, h, w, -1)
+        return self.mask_head.run(att, ctx['frame'][b:b + 1], [a[b:b + 1] for a in ctx['adapted']], n,
+                                  self.mask_query_chunk)
 
 
 class DeformableDETRSegm(DETRSegmBase, DeformableDETR):

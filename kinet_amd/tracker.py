@@ -15,9 +15,20 @@ tracks; detection NMS; results.  Thresholds come from the reference's `tracker_c
 MI355X-side choices: the detector, post-process, clipping, thresholding and NMS
 (kernels.nms, a one-workgroup HIP kernel with torchvision.ops.nms semantics) run on the GPU;
 the track bookkeeping is host Python as in the reference, fed by ONE batched device->host
-copy of the small per-frame decision arrays instead of a sync per track.  Segmentation masks
-and attention maps are outside the detection hot path (generate_attention_maps asserts in
-the reference for Deformable DETR, tracker.py:38-40).
+copy of the small per-frame decision arrays instead of a sync per track.  Attention maps are
+not built (generate_attention_maps asserts in the reference for Deformable DETR,
+tracker.py:38-40).
+
+Segmentation masks (tracker_cfg['masks'], MOTS; tracker.py:316-327, :339-379, :425-486, :515-545):
+the reference post-processes every query's mask to the original size and keeps those of the
+tracks alive at the end of the frame.  Here each track records the ROW of the frame's output its
+mask comes from; after the last NMS the mask head runs on those rows only
+(DETRSegmBase.mask_logits) and kinet_segm_track_resolve writes one int16 label map (the slot of
+the owning track per pixel, -1 background), which rides in the end-of-frame results copy.  A
+track that stays active without being re-detected (steps_termination > 1) keeps last frame's
+RESOLVED mask in the reference, which torch.stack promotes to 1.0 / 0.0 among the fresh
+probabilities: its slot is "stale" and names its slot in the previous label map (two maps,
+ping-pong).  results[id][frame]['mask'] is a numpy bool (oh, ow), as in the reference.
 """
 import math
 from collections import deque
@@ -58,6 +69,9 @@ class Track:
         self.last_pos = deque([pos.clone()])
         self.last_pos_relative = deque([-1] if pos_rel is None else [pos_rel.clone()])
         self.score = score
+        self.mask_row = None      # masks: the row of this frame's detector output the mask comes from
+        self.mask_slot = None     # masks: the track's slot in the previous frame's label map
+        self.mask_size = None     # masks: the (oh, ow) of that label map
         self.ims = deque([])
         self.count_inactive = 0
         self.count_termination = 0
@@ -94,11 +108,14 @@ class Tracker:
         if generate_attention_maps:
             raise NotImplementedError('attention maps (tracker.py:38-40) need the decoder\'s attention '
                                       'probabilities, which the fused attention kernels do not export')
-        if 'segm' in obj_detector_post:
-            # the reference's own three-argument detector call (tracker.py:309) is a TypeError with a
-            # masks model (DETRSegmBase.forward takes no prev_features)
-            raise NotImplementedError('the tracker does not carry segmentation masks: run the masks model and '
-                                      'PostProcessSegm per frame, or give the tracker the \'bbox\' postprocessor alone')
+        self.masks = bool(tracker_cfg.get('masks', False))
+        if 'segm' in obj_detector_post and not self.masks:
+            # opt-in: the reference's own three-argument detector call (tracker.py:309) is a TypeError
+            # with a masks model (DETRSegmBase.forward takes no prev_features)
+            raise NotImplementedError('the tracker carries segmentation masks only with tracker_cfg[\'masks\'] = True: '
+                                      'set it, or give the tracker the \'bbox\' postprocessor alone')
+        if self.masks and 'segm' not in obj_detector_post:
+            raise ValueError('tracker_cfg[\'masks\'] needs the \'segm\' postprocessor of a masks model')
         self.obj_detector = obj_detector
         self.obj_detector_post = obj_detector_post
         self.detection_obj_score_thresh = tracker_cfg['detection_obj_score_thresh']
@@ -133,6 +150,8 @@ class Tracker:
         self.tracks = []
         self.inactive_tracks = []
         self._prev_features = deque([None], maxlen=self.prev_frame_dist)
+        self._label_maps = [None, None]     # masks: this frame's and the previous frame's labels (ping-pong)
+        self._label_cur = 0
         if hard:
             self.track_num = 0
             self.results = {}
@@ -158,10 +177,12 @@ class Tracker:
             track.repeat_last_pos()
         self.inactive_tracks += inactive_tracks
 
-    def add_tracks(self, pos, scores, hs_embeds, indices):
+    def add_tracks(self, pos, scores, hs_embeds, indices, rows=None):
         new_track_ids = []
         for i in range(len(pos)):
             self.tracks.append(Track(pos[i], scores[i], self.track_num + i, hs_embeds[i], indices[i]))
+            if rows is not None:
+                self.tracks[-1].mask_row = rows[i]
             new_track_ids.append(self.track_num + i)
         self.track_num += len(new_track_ids)
         if new_track_ids:
@@ -171,11 +192,15 @@ class Tracker:
 
     def public_detections_mask(self, new_det_boxes, public_det_boxes):
         """tracker.py:127-170."""
+        return self._public_detections_mask(new_det_boxes, public_det_boxes).to(self.device)
+
+    def _public_detections_mask(self, new_det_boxes, public_det_boxes):
+        """The mask on the host (step reads it there too: the rows that survive are host knowledge)."""
         n = new_det_boxes.size(0)
         if not self.public_detections:
-            return torch.ones(n, dtype=torch.bool, device=self.device)
+            return torch.ones(n, dtype=torch.bool)
         if not len(public_det_boxes) or not n:
-            return torch.zeros(n, dtype=torch.bool, device=self.device)
+            return torch.zeros(n, dtype=torch.bool)
         mask = torch.zeros(n, dtype=torch.bool)
         if self.public_detections == 'center_distance':
             nb = new_det_boxes.cpu()
@@ -197,14 +222,18 @@ class Tracker:
                     mask[i] = True
         else:
             raise NotImplementedError(self.public_detections)
-        return mask.to(self.device)
+        return mask
 
-    def reid(self, new_det_boxes, new_det_scores, new_det_hs_embeds):
-        """tracker.py:172-267: re-identify inactive tracks with the new detections."""
+    def reid(self, new_det_boxes, new_det_scores, new_det_hs_embeds, new_det_rows=None):
+        """tracker.py:172-267: re-identify inactive tracks with the new detections.  new_det_rows
+        (masks): the detections' rows of the frame's output; a matched track takes its detection's."""
+        return self._reid(new_det_boxes, new_det_scores, new_det_hs_embeds, new_det_rows).to(self.device)
+
+    def _reid(self, new_det_boxes, new_det_scores, new_det_hs_embeds, new_det_rows=None):
         self._prune_inactive()
         n = new_det_boxes.size(0)
         if not self.inactive_tracks or not n:
-            return torch.ones(n, dtype=torch.bool, device=self.device)
+            return torch.ones(n, dtype=torch.bool)
         if self.reid_greedy_matching:
             nb = box_xyxy_to_cxcywh(new_det_boxes).cpu().numpy()
             ib = box_xyxy_to_cxcywh(torch.stack([t.pos for t in self.inactive_tracks])).cpu().numpy()
@@ -238,6 +267,8 @@ class Tracker:
                 track.score = new_det_scores[c]
                 track.hs_embed.append(new_det_hs_embeds[c])
                 track.reset_last_pos(self.reference_clear_last_pos_relative)
+                if new_det_rows is not None:
+                    track.mask_row = new_det_rows[int(c)]
                 assigned.append(int(c))
                 remove_inactive.append(track)
                 self.tracks.append(track)
@@ -247,7 +278,7 @@ class Tracker:
         mask = torch.ones(n, dtype=torch.bool)
         for c in assigned:
             mask[c] = False
-        return mask.to(self.device)
+        return mask
 
     # ------------------------------------------------------------------ one frame
     @torch.no_grad()
@@ -260,6 +291,9 @@ class Tracker:
         img = blob['img'].to(self.device)
         orig_size = blob['orig_size'].to(self.device)
         Q = self.num_object_queries
+        if self.masks and 'size' not in blob:
+            raise ValueError('tracker masks need blob[\'size\'], the (1, 2) network-input frame size '
+                             '(max_target_sizes of PostProcessSegm, tracker.py:322)')
 
         target = None
         prev = self.tracks + self.inactive_tracks
@@ -272,7 +306,15 @@ class Tracker:
                        'image_id': torch.tensor([1], device=self.device),
                        'track_query_hs_embeds': torch.stack([t.hs_embed[-1] for t in prev])}]
 
-        outputs, _, features, _, _ = self.obj_detector(img, target, self._prev_features[0])
+        defer = self.masks and hasattr(self.obj_detector, 'mask_logits')
+        if defer:
+            # the head runs after the bookkeeping, on the surviving tracks' rows only
+            was_deferred, self.obj_detector.defer_masks = self.obj_detector.defer_masks, True
+        try:
+            outputs, _, features, _, _ = self.obj_detector(img, target, self._prev_features[0])
+        finally:
+            if defer:
+                self.obj_detector.defer_masks = was_deferred
         hs_embeds = outputs['hs_embed'][0]
         result = self.obj_detector_post['bbox'](outputs, orig_size)[0]
         boxes = result['boxes'] if self.obj_detector.overflow_boxes else clip_boxes_to_image(result['boxes'],
@@ -281,7 +323,18 @@ class Tracker:
         person = labels == 0
         # every threshold decision of this frame in ONE device -> host copy
         dec = torch.stack([scores > self.track_obj_score_thresh, scores > self.reid_score_thresh,
-                           scores > self.detection_obj_score_thresh, person]).cpu()
+                           scores > self.detection_obj_score_thresh, person])
+        if self.masks:
+            # the two frame sizes ride in the same copy when they live on the device
+            sizes = [blob['orig_size'].reshape(-1)[:2], blob['size'].reshape(-1)[:2]]
+            if any(t.is_cuda for t in sizes):
+                packed = torch.cat([dec.flatten().to(torch.int32)] + [t.to(self.device, torch.int32) for t in sizes]).cpu()
+                dec, sizes = packed[:-4].view(dec.shape).bool(), [packed[-4:-2], packed[-2:]]
+            else:
+                dec = dec.cpu()
+            out_hw, net_hw = (tuple(int(v) for v in t.tolist()) for t in sizes)
+        else:
+            dec = dec.cpu()
 
         if num_prev_track:
             nt = num_prev_track
@@ -294,6 +347,7 @@ class Tracker:
                     track.hs_embed.append(hs_embeds[i])
                     track.pos = boxes[i]
                     track.count_termination = 0
+                    track.mask_row = i
                 else:
                     track.count_termination += 1
                     if track.count_termination >= self.steps_termination:
@@ -303,6 +357,7 @@ class Tracker:
                     track.score = scores[i]
                     track.hs_embed.append(hs_embeds[i])
                     track.pos = boxes[i]
+                    track.mask_row = i
                     from_inactive.append(track)
             if to_inactive:
                 self._logger(f'NEW INACTIVE TRACK IDS (track_obj_score_thresh={self.track_obj_score_thresh}): '
@@ -322,18 +377,26 @@ class Tracker:
                 self.tracks = [t for t in self.tracks if t not in remove]
 
         # new detections (tracker.py:456-505)
-        det_keep = (dec[2, -Q:] & dec[3, -Q:]).nonzero().flatten().to(self.device)
+        det_keep = (dec[2, -Q:] & dec[3, -Q:]).nonzero().flatten()
+        det_rows = (det_keep + (scores.shape[0] - Q)).tolist() if self.masks else None
+        det_keep = det_keep.to(self.device)
         new_det_boxes = boxes[-Q:][det_keep]
         new_det_scores = scores[-Q:][det_keep]
         new_det_hs_embeds = hs_embeds[-Q:][det_keep]
         new_det_indices = det_keep[:, None]                 # .float().nonzero() indices (:469)
-        pub = self.public_detections_mask(new_det_boxes, blob['dets'][0] if 'dets' in blob else [])
+        pub = self._public_detections_mask(new_det_boxes, blob['dets'][0] if 'dets' in blob else [])
+        if det_rows is not None:
+            det_rows = [r for r, k in zip(det_rows, pub.tolist()) if k]
+        pub = pub.to(self.device)
         new_det_boxes, new_det_scores = new_det_boxes[pub], new_det_scores[pub]
         new_det_hs_embeds, new_det_indices = new_det_hs_embeds[pub], new_det_indices[pub]
-        reid_mask = self.reid(new_det_boxes, new_det_scores, new_det_hs_embeds)
+        reid_mask = self._reid(new_det_boxes, new_det_scores, new_det_hs_embeds, det_rows)
+        if det_rows is not None:
+            det_rows = [r for r, k in zip(det_rows, reid_mask.tolist()) if k]
+        reid_mask = reid_mask.to(self.device)
         new_det_boxes, new_det_scores = new_det_boxes[reid_mask], new_det_scores[reid_mask]
         new_det_hs_embeds, new_det_indices = new_det_hs_embeds[reid_mask], new_det_indices[reid_mask]
-        new_track_ids = self.add_tracks(new_det_boxes, new_det_scores, new_det_hs_embeds, new_det_indices)
+        new_track_ids = self.add_tracks(new_det_boxes, new_det_scores, new_det_hs_embeds, new_det_indices, det_rows)
 
         if self.detection_nms_thresh and self.tracks:
             t_boxes = torch.stack([t.pos for t in self.tracks])
@@ -354,17 +417,60 @@ class Tracker:
             if not self.obj_detector.overflow_boxes:
                 pos = clip_boxes_to_image(pos, orig_size[0])
             packed = torch.cat([pos.float(), torch.stack([t.score for t in self.tracks]).float()[:, None],
-                                torch.stack([t.obj_ind.reshape(()) for t in self.tracks]).float()[:, None]],
-                               1).cpu().numpy()
-            for track, row in zip(self.tracks, packed):
+                                torch.stack([t.obj_ind.reshape(()) for t in self.tracks]).float()[:, None]], 1)
+            if self.masks:
+                # the label map rides in the same copy, as bytes behind the packed rows
+                labels = self._resolve_masks(outputs, out_hw, net_hw)
+                nb = packed.numel() * 4
+                both = torch.cat([packed.contiguous().view(torch.uint8).flatten(),
+                                  labels.view(torch.uint8).flatten()]).cpu().numpy()
+                packed = both[:nb].view(np.float32).reshape(len(self.tracks), 6)
+                labels = both[nb:].view(np.int16).reshape(out_hw)
+            else:
+                packed = packed.cpu().numpy()
+            for slot, (track, row) in enumerate(zip(self.tracks, packed)):
                 self.results.setdefault(track.id, {})[self.frame_index] = {
                     'bbox': row[:4].copy(), 'score': np.float32(row[4]), 'obj_ind': int(row[5])}
+                if self.masks:
+                    self.results[track.id][self.frame_index]['mask'] = labels == slot
         for t in self.inactive_tracks:
             t.count_inactive += 1
         self.frame_index += 1
         self._prev_features.append(features)
         if self.reid_sim_only:
             self.move_tracks_to_inactive(self.tracks)
+
+    def _resolve_masks(self, outputs, out_hw, net_hw):
+        """tracker.py:515-527 for the tracks alive at the end of the frame: slot t of the label map
+        is self.tracks[t].  A track with a row of this frame is fresh; one that stayed active without
+        being re-detected names its slot in the previous frame's map.  The head runs once, on the
+        fresh rows; 0.5 is the reference's constant (:522), not the post-processor's threshold."""
+        prev = self._label_maps[1 - self._label_cur]
+        rows, src = {}, []
+        for track in self.tracks:
+            if track.mask_row is not None:
+                src.append(rows.setdefault(track.mask_row, len(rows)))
+            elif track.mask_slot is not None:
+                if track.mask_size != out_hw:
+                    raise RuntimeError(f'track {track.id} keeps a mask of size {track.mask_size}, the frame is '
+                                       f'{out_hw} (the reference\'s torch.stack fails there too)')
+                src.append(-track.mask_slot - 1)
+            else:
+                raise RuntimeError(f'track {track.id} has neither a mask row of this frame nor a kept mask')
+        idx = torch.tensor(list(rows), dtype=torch.int64, device=self.device)
+        if hasattr(self.obj_detector, 'mask_logits'):
+            logits = self.obj_detector.mask_logits(idx, 0)
+        else:
+            logits = outputs['pred_masks'][0].index_select(0, idx)
+        cur = self._label_maps[self._label_cur]
+        if cur is None or tuple(cur.shape) != out_hw:
+            cur = self._label_maps[self._label_cur] = torch.empty(out_hw, dtype=torch.int16, device=self.device)
+        stale = any(s < 0 for s in src)
+        K.segm_track_resolve(logits, src, prev if stale else None, net_hw, net_hw, out_hw, 0.5, out=cur)
+        for slot, track in enumerate(self.tracks):
+            track.mask_row, track.mask_slot, track.mask_size = None, slot, out_hw
+        self._label_cur = 1 - self._label_cur
+        return cur
 
 
 # ---------------------------------------------------------------------------------- KineT
@@ -494,6 +600,9 @@ class TrackerKinematic(Tracker):
 
     def __init__(self, obj_detector, obj_detector_post, tracker_cfg, obj_detector_args, generate_attention_maps=False,
                  logger=None, verbose=False):
+        if tracker_cfg.get('masks', False):
+            # (the reference's own mask code in TrackerKinematic.step is commented out)
+            raise NotImplementedError('TrackerKinematic does not carry segmentation masks')
         super().__init__(obj_detector, obj_detector_post, tracker_cfg, generate_attention_maps, logger, verbose)
         self.n_classes = tracker_cfg['n_classes']
         self.dim_metadata = 1 + self.n_classes if obj_detector_args.use_class else 1
