@@ -219,6 +219,43 @@ int kinet_msda_encoder_set_strips(int strips);
 int kinet_msda_encoder_plan_ex(const int64_t* spatial_shapes_host, int batch, int num_heads, int num_query,
                                int channels, int32_t* plan_out);
 
+/* The launch kinet_msda_forward (kind 0), kinet_msda_fused_forward (kind 1) or kinet_msda_backward
+ * (kind 2) would make for a described problem on a device of `cus` compute units (host only, no
+ * GPU call; csrc/msda_plan.h).  problem: KINET_MSDAP_FIELDS int64 values in the order of the enum
+ * below; the backward tune knobs and the debug word are arguments here, not the calling thread's
+ * (kinet_msda_backward_tune).  plan_out: KINET_MSDAPL_FIELDS int32 values in the order of the
+ * second enum.  KINET_ERR_ARG with the entry point's own message when it would refuse the call. */
+enum kinet_msda_plan_problem_field {
+    KINET_MSDAP_KIND = 0,       /* 0 forward, 1 fused forward, 2 backward */
+    KINET_MSDAP_N, KINET_MSDAP_S, KINET_MSDAP_M, KINET_MSDAP_D, KINET_MSDAP_L, KINET_MSDAP_LQ, KINET_MSDAP_P,
+    KINET_MSDAP_VALUE_DTYPE,    /* kinet_dtype of value */
+    KINET_MSDAP_OUT_DTYPE,      /* of the output (fused; else = value) */
+    KINET_MSDAP_LOC_DTYPE,      /* of sampling_loc / attn_weight, or of offsets_logits (fused) */
+    KINET_MSDAP_VSB, KINET_MSDAP_VSS, KINET_MSDAP_VSM,   /* value strides in elements (fused: all 0 = row-major;
+                                                            forward: VSS = the row stride, 0 = M*D) */
+    KINET_MSDAP_VALUE_ALIGN,    /* value pointer % 16 (fused) */
+    KINET_MSDAP_TUNE_MODE, KINET_MSDAP_TUNE_LOG2_ROWS, KINET_MSDAP_TUNE_QC, KINET_MSDAP_TUNE_THREADS,
+    KINET_MSDAP_TUNE_FLUSH_AT,  /* the five arguments of kinet_msda_backward_tune */
+    KINET_MSDAP_DEBUG,          /* kinet_msda_backward_debug word */
+    KINET_MSDAP_FIELDS
+};
+enum kinet_msda_plan_field {
+    KINET_MSDAPL_FAMILY = 0,    /* 0 none (an empty call), 1 msda_fwd_kernel, 2 msda_fused_kernel,
+                                   3 msda_fused_fast_kernel, 4 msda_bwd_list_kernel, 5 msda_bwd_kernel */
+    /* template selectors, 0 where the family has none */
+    KINET_MSDAPL_VEC, KINET_MSDAPL_FUSED, KINET_MSDAPL_L, KINET_MSDAPL_NJ, KINET_MSDAPL_SP, KINET_MSDAPL_POW2,
+    KINET_MSDAPL_ALN, KINET_MSDAPL_SG,
+    KINET_MSDAPL_GRID_X, KINET_MSDAPL_GRID_Y, KINET_MSDAPL_GRID_Z, KINET_MSDAPL_BLOCK,
+    KINET_MSDAPL_LDS,           /* dynamic LDS bytes */
+    /* run-time scalars of the launch */
+    KINET_MSDAPL_QT, KINET_MSDAPL_LPQ, KINET_MSDAPL_NA, KINET_MSDAPL_QT_WAVE, KINET_MSDAPL_MH, KINET_MSDAPL_QP,
+    KINET_MSDAPL_QC, KINET_MSDAPL_LOG2NS, KINET_MSDAPL_BLOCKED, KINET_MSDAPL_HEAD_BYTES,
+    KINET_MSDAPL_LAST,          /* the kinet_msda_fused_last_kernel / kinet_msda_backward_last_kernel code the
+                                   call records (-2: the record is left as it is) */
+    KINET_MSDAPL_FIELDS
+};
+int kinet_msda_launch_plan(const int64_t* problem, int cus, int32_t* plan_out);
+
 #ifdef __cplusplus
 }
 #endif

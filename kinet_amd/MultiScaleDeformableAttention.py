@@ -16,6 +16,7 @@ in ms_deform_attn_func.py:11.
 import torch
 
 from kinet_amd import _native as _n
+from kinet_amd.kernels import MSDA_BWD_LAST as _BWD_LAST
 
 
 def _dims(value, spatial_shapes, sampling_loc, attn_weight):
@@ -80,7 +81,6 @@ def ms_deform_attn_backward(value, spatial_shapes, sampling_loc, attn_weight, gr
             _n.ptr(attn_weight), _n.ptr(grad_output), _n.ptr(grad_value), _n.ptr(grad_loc),
             _n.ptr(grad_attw), _n.ptr(ws), N, S, M, D, L, Lq, P, int(im2col_step),
             _n.dtype_code(value.dtype), _n.dtype_code(sampling_loc.dtype), _n.stream(value.device), work=work)
-    # the launcher's own choice (csrc/msda.hip): the list kernel sums grad_value rows on chip
-    work['kernel'] = {1: 'msda_bwd_list_kernel', 0: 'msda_bwd_kernel'}.get(
-        _n.lib().kinet_msda_backward_last_kernel(), 'none')
+    # the planner's choice (csrc/msda_plan.h): the list kernel sums grad_value rows on chip
+    work['kernel'] = _BWD_LAST.get(_n.lib().kinet_msda_backward_last_kernel(), 'none')
     return [grad_value, grad_loc, grad_attw]

@@ -31,6 +31,7 @@ _SIGS = {
     'kinet_msda_encoder_plan': [P, I, I, I, P],
     'kinet_msda_encoder_set_strips': [I],
     'kinet_msda_encoder_plan_ex': [P, I, I, I, I, P],
+    'kinet_msda_launch_plan': [P, I, P],
     'kinet_msda_encoder_forward_split': [P, I64, I64, P, I64, I64, P, P, P, I, P, P] + [I] * 8 + [P, P],
     'kinet_msda_sample_records': [P, P, P, P, I, I, I, I, I, P, I, P, P, I, I, I, P, I, P],
     'kinet_msda_encoder_forward_records': [P, I64, I64, P, P, I, P] + [I] * 8 + [P, P],

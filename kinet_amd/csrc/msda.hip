@@ -28,6 +28,7 @@
 
 #include "../../include/kinet_msda.h"
 #include "common.h"
+#include "msda_plan.h"
 #include "msda_util.h"
 
 namespace kinet {
@@ -1152,29 +1153,50 @@ __global__ void f32_to_kernel(const float* __restrict__ src, T* __restrict__ dst
 }
 
 // ---------------------------------------------------------------------------------
-// launch configuration
+// launchers: fill an MsdaProblem, plan it (msda_plan.h), expand the plan
 // ---------------------------------------------------------------------------------
-struct Cfg {
-    int vec, lpq, qt;
-};
+static_assert(kThreads == kMsdaThreads && kMaxLevels == kMsdaMaxLevels, "msda_plan.h plans these workgroups");
+static_assert(sizeof(LevelInfo) == kLevelInfoBytes, "msda_plan.h: LDS formulas");
+static_assert(sizeof(Tap4) == kTap4Bytes && sizeof(Tap4d) == kTap4dBytes, "msda_plan.h: LDS formulas");
+static_assert(sizeof(BwdTap<float>) == kBwdTapF32Bytes && sizeof(BwdTap<double>) == kBwdTapF64Bytes, "msda_plan.h: LDS formulas");
+static_assert(sizeof(HTap) == kHTapBytes && sizeof(int2) == 8, "msda_plan.h: LDS formulas");
 
-Cfg pick_cfg(int D, int M, size_t esize) {
-    Cfg c{1, D, 1};
-    const int maxvec = (int)(16 / esize);
-    for (int v = maxvec; v >= 1; v >>= 1) {
-        if (D % v == 0) { c.vec = v; break; }
-    }
-    c.lpq = D / c.vec;
-    const int groups = kThreads / c.lpq;
-    c.qt = groups / M;
-    return c;
+template <typename T> constexpr int dtype_of() {
+    return std::is_same<T, float>::value ? KINET_F32 : std::is_same<T, double>::value ? KINET_F64
+         : std::is_same<T, bf16_t>::value ? KINET_BF16 : KINET_F16;
+}
+
+// f(integral_constant<int, VEC>) for the planned vector width.  A plan never names a vector wider
+// than 16 bytes of T.  BUILT: the widest VEC a family is instantiated with -- the forward, fused and
+// direct backward kernels are built at every width for every T (the widths beyond 16 bytes are never
+// launched), the list kernel only up to 16 bytes of T
+template <typename T, int BUILT = 8, typename F>
+void dispatch_vec(int vec, F&& f) {
+    dispatch_int<1, 2, 4, 8>(vec, [&](auto V) {
+        if constexpr (decltype(V)::value <= BUILT) {
+            if (16 / sizeof(T) >= decltype(V)::value) f(V);
+        }
+    });
+}
+
+int refused(const MsdaPlan& pl) {
+    const long long* a = pl.why_arg;
+    set_error(pl.why, a[0], a[1], a[2], a[3], a[4], a[5], a[6]);
+    return KINET_ERR_ARG;
+}
+
+MsdaProblem describe(int kind, int N, int S, int M, int D, int L, int Lq, int P, int value_dtype) {
+    MsdaProblem p{};
+    p.kind = kind;
+    p.N = N; p.S = S; p.M = M; p.D = D; p.L = L; p.Lq = Lq; p.P = P;
+    p.value_dtype = p.out_dtype = value_dtype;
+    p.loc_dtype = KINET_F32;
+    return p;
 }
 
 int common_checks(int N, int S, int M, int D, int L, int Lq, int P, int im2col_step) {
-    KINET_CHECK_ARG(N >= 0 && S >= 0 && M > 0 && D > 0 && L > 0 && Lq >= 0 && P > 0,
-                    "msda: invalid sizes N=%d S=%d M=%d D=%d L=%d Lq=%d P=%d", N, S, M, D, L, Lq, P);
-    KINET_CHECK_ARG(L <= kMaxLevels, "msda: num_levels %d > %d", L, kMaxLevels);
-    KINET_CHECK_ARG((long long)S * M * D < (1LL << 31), "msda: S*M*D too large for one image");
+    MsdaPlan pl{};
+    if (!msda_check_sizes(describe(MSDA_FORWARD, N, S, M, D, L, Lq, P, KINET_F32), pl)) return refused(pl);
     if (N > 0) {
         const int step = im2col_step < N ? im2col_step : N;   // cu:46
         KINET_CHECK_ARG(step > 0 && N % step == 0, "batch(%d) must divide im2col_step(%d)", N, step);   // cu:48
@@ -1182,44 +1204,26 @@ int common_checks(int N, int S, int M, int D, int L, int Lq, int P, int im2col_s
     return KINET_OK;
 }
 
-template <typename T, typename TL, int FUSED>
-int launch_fwd(const void* value, const int64_t* shapes, const void* loc, const void* attw,
-               const void* offlog, int ld_off, const float* ref, int ref_dim, const uint8_t* qmask,
-               float* loc_out, float* attw_out, void* out, int N, int S, int M, int D, int L, int Lq,
-               int P, hipStream_t stream, int vld = 0) {
-    const Cfg c = pick_cfg(D, M, sizeof(T));
-    KINET_CHECK_ARG(c.qt >= 1, "msda: heads*channels/vec (%d*%d) exceeds one workgroup", M, c.lpq);
-    if (vld == 0) vld = M * D;
-    KINET_CHECK_ARG(vld >= M * D && vld % c.vec == 0, "msda: value row stride %d invalid", vld);
-    KINET_CHECK_ARG((long long)S * vld < (1LL << 31), "msda: S*value_ld too large for one image");
-    if (N == 0 || Lq == 0) return KINET_OK;
-    using Acc = typename Acc<T>::type;
-    const size_t tap = sizeof(Acc) == 8 ? sizeof(Tap4d) : sizeof(Tap4);
-    const size_t nsamp = (size_t)c.qt * M * L * P;
-    size_t lds = sizeof(LevelInfo) + nsamp * tap + (FUSED ? nsamp * sizeof(float) : 0);
-    KINET_CHECK_ARG(lds <= 160 * 1024, "msda: LDS request %zu too large", lds);
-    dim3 grid((Lq + c.qt - 1) / c.qt, N);
-#define KF(VEC)                                                                                             \
-    hipLaunchKernelGGL((msda_fwd_kernel<T, TL, VEC, FUSED>), grid, dim3(kThreads), lds, stream,             \
-                       (const T*)value, shapes, (const TL*)loc, (const TL*)attw, (const float*)offlog, ld_off,  \
-                       ref, ref_dim, qmask, loc_out, attw_out, (T*)out, S, M, D, L, Lq, P, c.qt, c.lpq, vld)
-    switch (c.vec) {
-        case 1: KF(1); break;
-        case 2: KF(2); break;
-        case 4: if (16 / sizeof(T) >= 4) { KF(4); } break;
-        case 8: if (16 / sizeof(T) >= 8) { KF(8); } break;
-    }
-#undef KF
+template <typename T, typename TL>
+int launch_fwd(const void* value, const int64_t* shapes, const void* loc, const void* attw, void* out, int N, int S,
+               int M, int D, int L, int Lq, int P, hipStream_t stream) {
+    MsdaProblem pb = describe(MSDA_FORWARD, N, S, M, D, L, Lq, P, dtype_of<T>());
+    pb.loc_dtype = dtype_of<TL>();
+    pb.vss = (long long)M * D;
+    MsdaPlan pl;
+    if (!msda_plan(pb, pl)) return refused(pl);
+    if (pl.family == MSDA_K_NONE) return KINET_OK;
+    const dim3 grid(pl.grid[0], pl.grid[1]);
+    dispatch_vec<T>(pl.vec, [&](auto V) {
+        hipLaunchKernelGGL((msda_fwd_kernel<T, TL, decltype(V)::value, 0>), grid, dim3(pl.block), pl.lds, stream,
+                           (const T*)value, shapes, (const TL*)loc, (const TL*)attw, (const float*)nullptr, 0,
+                           (const float*)nullptr, 0, (const uint8_t*)nullptr, (float*)nullptr, (float*)nullptr, (T*)out,
+                           S, M, D, L, Lq, P, pl.qt, pl.lpq, (int)pb.vss);
+    });
     KINET_LAUNCH_CHECK();
     return KINET_OK;
 }
 
-// backward kernel choice for the calling thread (kinet_msda_backward_tune; 0 = automatic):
-// mode -1 = the direct-atomic kernel, 1 = the list kernel for any call; log2ns = hash rows,
-// qc = queries per workgroup, threads = workgroup size, flush_at = queries per pass
-struct BwdTune {
-    int mode, log2ns, qc, threads, flush_at;
-};
 thread_local BwdTune bwd_tune = {0, 0, 0, 0, 0};
 // timing-only phase knobs of msda_bwd_list_kernel (kinet_msda_backward_debug; results wrong
 // when set): 1 = phase 2 without its value loads, 2 = phase 3 without its global atomics,
@@ -1235,8 +1239,14 @@ int launch_bwd(const void* value, const int64_t* shapes, const void* loc, const 
                int M, int D, int L, int Lq, int P, hipStream_t stream) {
     using Acc = typename Acc<T>::type;
     using GA = typename std::conditional<sizeof(Acc) == 8, double, float>::type;
-    const Cfg c = pick_cfg(D, M, sizeof(T));
-    KINET_CHECK_ARG(c.qt >= 1, "msda: heads*channels/vec (%d*%d) exceeds one workgroup", M, c.lpq);
+    MsdaProblem pb = describe(MSDA_BACKWARD, N, S, M, D, L, Lq, P, dtype_of<T>());
+    pb.loc_dtype = dtype_of<TL>();
+    pb.tune = bwd_tune;
+    pb.dbg = bwd_dbg;
+    pb.cus = cu_count();
+    MsdaPlan pl;
+    const bool planned = msda_plan(pb, pl);
+    if (!planned && pl.why_early) return refused(pl);
     const size_t nval = (size_t)N * S * M * D;
     GA* acc_buf;
     const bool direct = std::is_same<T, float>::value || std::is_same<T, double>::value;
@@ -1247,101 +1257,39 @@ int launch_bwd(const void* value, const int64_t* shapes, const void* loc, const 
         acc_buf = (GA*)workspace;
     }
     if (nval) KINET_CHECK_HIP(hipMemsetAsync(acc_buf, 0, nval * sizeof(GA), stream));
-    const int LP = L * P;
-    const int nj = (D + 15) / 16;
-    const BwdTune tn = bwd_tune;
-    bool hashed = false;
-    if constexpr (sizeof(GA) == 4) {
-    // encoder calls (queries = the value pixels, Lq == S): rows summed on chip per pass
-    // (msda_bwd_list_kernel); mode 1 forces it, mode -1 forbids it
-    if (N > 0 && Lq > 0 && tn.mode >= 0 && (Lq == S || tn.mode == 1) && c.lpq <= 16 && nj <= 4) {
-        hashed = true;
-        // 256 threads, passes of 16 queries (8 x 2 pixel blocks), 1024-row hash: 35 KB of LDS,
-        // 4 workgroups per CU -- 1.03 ms at the config-4 encoder call; 512 threads x 32 queries
-        // 1.05, 512 x 16 1.40 (tools/msda_bwd_probe.py --sweep, profiles/r03p_msda_bwd_probe.log)
-        const int threads = tn.threads ? tn.threads : 256;
-        const int QP = tn.flush_at > 0 ? tn.flush_at : threads / 16;   // queries per pass
-        const int log2ns = tn.log2ns ? tn.log2ns : 10;
-        const size_t nsmp = (size_t)QP * LP;
-        const size_t lds = sizeof(LevelInfo) + ((size_t)3 << log2ns) * sizeof(int) + 4 * sizeof(int) +
-                           nsmp * 4 * (sizeof(int2) + sizeof(int)) + (size_t)QP * D * sizeof(float) + nsmp * sizeof(HTap);
-        KINET_CHECK_ARG(threads % 64 == 0 && threads <= 512 && QP >= 1 && lds <= 160 * 1024,
-                        "msda backward: pass of %d queries x %d samples does not fit LDS", QP, LP);
-        // query chunk per workgroup: as long as the grid still fills the chip 4 times over
-        int qc = tn.qc;
-        if (qc <= 0) {
-            qc = QP;   // one pass per workgroup: 1.08 ms at the config-4 encoder call (2 passes 1.11, 4 1.18)
-            while (qc > QP && (long)N * M * ((Lq + qc - 1) / qc) < 4L * cu_count()) qc >>= 1;
+    if (pl.last != kMsdaKeepLast) bwd_last = pl.last;
+    if (!planned) return refused(pl);
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+    if (pl.family == MSDA_K_BWD_LIST) {
+        if constexpr (sizeof(GA) == 4) {
+            dispatch_vec<T, 16 / sizeof(T)>(pl.vec, [&](auto V) {
+                dispatch_int<1, 2, 3, 4>(pl.nj, [&](auto NJ) {
+                    dispatch_int<2, 4>(pl.sp, [&](auto SP) {
+                        hipLaunchKernelGGL((msda_bwd_list_kernel<T, TL, decltype(V)::value, decltype(NJ)::value, decltype(SP)::value>),
+                                           grid, dim3(pl.block), pl.lds, stream, (const T*)value, shapes, (const TL*)loc,
+                                           (const TL*)attw, (const T*)gout, (float*)acc_buf, (TL*)gloc, (TL*)gattw, S, M, D,
+                                           L, Lq, P, pl.qc, pl.QP, pl.na, pl.log2ns, pl.blocked, pl.dbg);
+                    });
+                });
+            });
+            KINET_LAUNCH_CHECK();
         }
-        qc = std::max(QP, qc / QP * QP);
-        // encoder calls: queries in 8 x QP/8 pixel blocks (fewer distinct rows per pass than a
-        // run of QP pixels); the grid over-covers the block count (edge blocks) and each
-        // workgroup loops over chunks, so any level geometry is covered
-        const int blocked = (Lq == S && QP % 8 == 0 && tn.mode != 2) ? 1 : 0;
-        const int nq = blocked ? (S + QP - 1) / QP : (Lq + qc - 1) / qc;
-        dim3 grid(blocked ? nq + nq / 8 + 2 * L : nq, N, M);
-#define KH(VEC, NJ)                                                                                             \
-    if (tn.mode == 3)                                                                                           \
-        hipLaunchKernelGGL((msda_bwd_list_kernel<T, TL, VEC, NJ, 4>), grid, dim3(threads), lds, stream,         \
-                           (const T*)value, shapes, (const TL*)loc, (const TL*)attw, (const T*)gout,            \
-                           (float*)acc_buf, (TL*)gloc, (TL*)gattw, S, M, D, L, Lq, P, qc, QP, c.lpq, log2ns,    \
-                           blocked, bwd_dbg);                                                                   \
-    else                                                                                                        \
-    hipLaunchKernelGGL((msda_bwd_list_kernel<T, TL, VEC, NJ>), grid, dim3(threads), lds, stream, (const T*)value, \
-                       shapes, (const TL*)loc, (const TL*)attw, (const T*)gout, (float*)acc_buf, (TL*)gloc,     \
-                       (TL*)gattw, S, M, D, L, Lq, P, qc, QP, c.lpq, log2ns, blocked, bwd_dbg)
-#define KHJ(VEC) switch (nj) { case 1: KH(VEC, 1); break; case 2: KH(VEC, 2); break; case 3: KH(VEC, 3); break; default: KH(VEC, 4); }
-        switch (c.vec) {
-            case 1: KHJ(1); break;
-            case 2: KHJ(2); break;
-            case 4: if constexpr (16 / sizeof(T) >= 4) { KHJ(4); } break;
-            case 8: if constexpr (16 / sizeof(T) >= 8) { KHJ(8); } break;
-        }
-#undef KHJ
-#undef KH
-        KINET_LAUNCH_CHECK();
-    }
-    }
-    bwd_last = hashed ? 1 : (N > 0 && Lq > 0 ? 0 : -1);
-    if (hashed) {
-    } else if (N > 0 && Lq > 0) {
-        // groups padded to a power of two (reductions by shuffles instead of LDS atomics)
-        int lpq = c.lpq, qt = c.qt;
-        if ((lpq & (lpq - 1)) != 0) {
-            int p2 = 1;
-            while (p2 < lpq) p2 <<= 1;
-            if (p2 <= 64 && (kThreads / p2) / M >= 1) {
-                lpq = p2;
-                qt = (kThreads / p2) / M;
+    } else if (pl.family == MSDA_K_BWD) {
+        auto launch = [&](auto V, auto POW2, auto ALN) {
+            hipLaunchKernelGGL((msda_bwd_kernel<T, TL, GA, decltype(V)::value, decltype(POW2)::value, decltype(ALN)::value>),
+                               grid, dim3(pl.block), pl.lds, stream, (const T*)value, shapes, (const TL*)loc,
+                               (const TL*)attw, (const T*)gout, acc_buf, (TL*)gloc, (TL*)gattw, S, M, D, L, Lq, P, pl.qt,
+                               pl.lpq, pl.na);
+        };
+        using I0 = std::integral_constant<int, 0>;
+        using I1 = std::integral_constant<int, 1>;
+        dispatch_vec<T>(pl.vec, [&](auto V) {
+            if constexpr (decltype(V)::value == 4) {   // the only width with an ALN scatter
+                if (pl.aln) return launch(V, I1{}, I1{});
             }
-        }
-        const bool pow2 = (lpq & (lpq - 1)) == 0 && lpq <= 64;
-        const bool aln = sizeof(GA) == 4 && lpq == 16 && c.vec == 4 && (M * D) % 16 == 0 && D <= 48;
-        const size_t nsamp = (size_t)qt * M * L * P;
-        const size_t lds = sizeof(LevelInfo) + nsamp * sizeof(BwdTap<Acc>) + (pow2 ? 0 : nsamp * 3 * sizeof(Acc));
-        KINET_CHECK_ARG(lds <= 160 * 1024, "msda backward: LDS request %zu too large", lds);
-        dim3 grid((Lq + qt - 1) / qt, N);
-#define KB(VEC, P2, AL)                                                                                      \
-    hipLaunchKernelGGL((msda_bwd_kernel<T, TL, GA, VEC, P2, AL>), grid, dim3(kThreads), lds, stream,            \
-                       (const T*)value, shapes, (const TL*)loc, (const TL*)attw, (const T*)gout, acc_buf,   \
-                       (TL*)gloc, (TL*)gattw, S, M, D, L, Lq, P, qt, lpq, c.lpq)
-#define KBV(VEC) if (pow2) { KB(VEC, 1, 0); } else { KB(VEC, 0, 0); }
-        switch (c.vec) {
-            case 1: KBV(1); break;
-            case 2: KBV(2); break;
-            case 4:
-                if (16 / sizeof(T) >= 4) {
-                    if (aln) { KB(4, 1, 1); } else { KBV(4); }
-                }
-                break;
-            case 8: if (16 / sizeof(T) >= 8) { KBV(8); } break;
-        }
-#undef KBV
-#undef KB
+            dispatch_int<0, 1>(pl.pow2, [&](auto POW2) { launch(V, POW2, I0{}); });
+        });
         KINET_LAUNCH_CHECK();
-    } else if (N * Lq * M * L * P > 0) {
-        KINET_CHECK_HIP(hipMemsetAsync(gloc, 0, (size_t)N * Lq * M * L * P * 2 * sizeof(TL), stream));
-        KINET_CHECK_HIP(hipMemsetAsync(gattw, 0, (size_t)N * Lq * M * L * P * sizeof(TL), stream));
     }
     if (!direct && nval) {
         const long n = (long)nval;
@@ -1351,6 +1299,55 @@ int launch_bwd(const void* value, const int64_t* shapes, const void* loc, const 
         KINET_LAUNCH_CHECK();
     }
     return KINET_OK;
+}
+
+template <typename T, typename TO = T, typename TL = float>
+int launch_fused(const void* value, long vsb, int vss, long vsm, const int64_t* shapes, const void* offlog,
+                 int ld_off, const float* ref, int ref_dim, const uint8_t* qmask, void* out, float* loc_out,
+                 float* attw_out, int N, int S, int M, int D, int L, int Lq, int P, const int* torder,
+                 hipStream_t stream) {
+    MsdaProblem pb = describe(MSDA_FUSED, N, S, M, D, L, Lq, P, dtype_of<T>());
+    pb.out_dtype = dtype_of<TO>();
+    pb.loc_dtype = dtype_of<TL>();
+    pb.vsb = vsb; pb.vss = vss; pb.vsm = vsm;
+    pb.value_align = (int)((uintptr_t)value % 16);
+    MsdaPlan pl;
+    const bool planned = msda_plan(pb, pl);
+    msda_fused_last = -1;
+    if (!planned) return refused(pl);
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+    if (pl.family == MSDA_K_FUSED_FAST) {
+        if constexpr (sizeof(T) == 2) {
+            dispatch_int<4, 8>(pl.l, [&](auto LV) {
+                constexpr int Lc = decltype(LV)::value, MH = Lc == 4 ? 2 : kThreads / 64, SG = Lc == 4 ? 2 : 4;
+                hipLaunchKernelGGL((msda_fused_fast_kernel<T, TO, TL, Lc, 4, MH, SG>), grid, dim3(pl.block), 0, stream,
+                                   (const T*)value, vsb, vss, vsm, pl.head_bytes, shapes, (const TL*)offlog, ld_off, ref,
+                                   ref_dim, qmask, loc_out, attw_out, (TO*)out, S, M, Lq, torder);
+            });
+        }
+    } else if (pl.family == MSDA_K_FUSED) {
+        if constexpr (std::is_same<T, TO>::value && std::is_same<TL, float>::value) {   // the only ones planned
+            dispatch_vec<T>(pl.vec, [&](auto V) {
+                hipLaunchKernelGGL((msda_fused_kernel<T, decltype(V)::value>), grid, dim3(pl.block), pl.lds, stream,
+                                   (const T*)value, vsb, vss, vsm, shapes, (const float*)offlog, ld_off, ref, ref_dim, qmask,
+                                   loc_out, attw_out, (T*)out, S, M, D, L, Lq, P, pl.QT, pl.lpq, pl.MH);
+            });
+        }
+    } else {
+        return KINET_OK;
+    }
+    KINET_LAUNCH_CHECK();
+    msda_fused_last = pl.last;
+    return KINET_OK;
+}
+
+// all three strides 0 = row-major (N, S, M, D)
+void default_strides(int64_t& sb, int64_t& ss, int64_t& sm, int S, int M, int D) {
+    if (sb == 0 && ss == 0 && sm == 0) {
+        ss = (int64_t)M * D;
+        sm = D;
+        sb = ss * S;
+    }
 }
 
 }  // namespace
@@ -1365,83 +1362,16 @@ extern "C" int kinet_msda_forward(const void* value, const int64_t* spatial_shap
     int rc = common_checks(batch, spatial_size, num_heads, channels, num_levels, num_query, num_point, im2col_step);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-#define ARGS value, spatial_shapes, sampling_loc, attn_weight, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, \
-             output, batch, spatial_size, num_heads, channels, num_levels, num_query, num_point, s
-    if (value_dtype == KINET_F32 && loc_dtype == KINET_F32) return launch_fwd<float, float, 0>(ARGS);
-    if (value_dtype == KINET_F64 && loc_dtype == KINET_F64) return launch_fwd<double, double, 0>(ARGS);
-    if (value_dtype == KINET_BF16 && loc_dtype == KINET_F32) return launch_fwd<bf16_t, float, 0>(ARGS);
-    if (value_dtype == KINET_F16 && loc_dtype == KINET_F32) return launch_fwd<f16_t, float, 0>(ARGS);
+#define ARGS value, spatial_shapes, sampling_loc, attn_weight, output, batch, spatial_size, num_heads, channels, \
+             num_levels, num_query, num_point, s
+    if (value_dtype == KINET_F32 && loc_dtype == KINET_F32) return launch_fwd<float, float>(ARGS);
+    if (value_dtype == KINET_F64 && loc_dtype == KINET_F64) return launch_fwd<double, double>(ARGS);
+    if (value_dtype == KINET_BF16 && loc_dtype == KINET_F32) return launch_fwd<bf16_t, float>(ARGS);
+    if (value_dtype == KINET_F16 && loc_dtype == KINET_F32) return launch_fwd<f16_t, float>(ARGS);
 #undef ARGS
     set_error("msda forward: unsupported dtype pair value=%d loc=%d", value_dtype, loc_dtype);
     return KINET_ERR_ARG;
 }
-
-namespace kinet {
-namespace {
-template <typename T, typename TO = T, typename TL = float>
-int launch_fused(const void* value, long vsb, int vss, long vsm, const int64_t* shapes, const void* offlog_v,
-                 int ld_off, const float* ref, int ref_dim, const uint8_t* qmask, void* out, float* loc_out,
-                 float* attw_out, int N, int S, int M, int D, int L, int Lq, int P, const int* torder,
-                 hipStream_t stream) {
-    const Cfg c = pick_cfg(D, M, sizeof(T));
-    msda_fused_last = -1;
-    KINET_CHECK_ARG(c.lpq <= 64, "msda fused: head_dim/vec (%d) exceeds a wave", c.lpq);
-    if (N == 0 || Lq == 0) return KINET_OK;
-    if constexpr (sizeof(T) == 2) {
-        // specialised kernel: head_dim 32, (L, P) in {(4, 4), (8, 4)}, 16-byte aligned vectors
-        const long long head_bytes = ((long long)(S - 1) * vss + D) * (long long)sizeof(T);
-        if (D == 32 && P == 4 && (L == 4 || L == 8) && vss % 8 == 0 && vsb % 8 == 0 && vsm % 8 == 0 &&
-            ((uintptr_t)value % 16) == 0 && head_bytes < (1LL << 31)) {
-            dim3 grid((Lq + 15) / 16, N, (M + 3) / 4);
-            if (L == 4) {
-                // 2 heads (waves) per workgroup, 2 samples per gather group: 12.5 KiB LDS and
-                // 52 VGPRs, 12 workgroups per CU (encoder call 271 -> 258 us vs 4 heads x 4)
-                dim3 g2((Lq + 15) / 16, N, (M + 1) / 2);
-                hipLaunchKernelGGL((msda_fused_fast_kernel<T, TO, TL, 4, 4, 2, 2>), g2, dim3(128), 0, stream,
-                                   (const T*)value, vsb, vss, vsm, (int)head_bytes, shapes, (const TL*)offlog_v,
-                                   ld_off, ref, ref_dim, qmask, loc_out, attw_out, (TO*)out, S, M, Lq, torder);
-            } else
-                hipLaunchKernelGGL((msda_fused_fast_kernel<T, TO, TL, 8, 4>), grid, dim3(kThreads), 0, stream,
-                                   (const T*)value, vsb, vss, vsm, (int)head_bytes, shapes, (const TL*)offlog_v, ld_off,
-                                   ref, ref_dim, qmask, loc_out,
-                                   attw_out, (TO*)out, S, M, Lq, torder);
-            KINET_LAUNCH_CHECK();
-            msda_fused_last = kFusedFast << 8 | L;
-            return KINET_OK;
-        }
-    }
-    KINET_CHECK_ARG((std::is_same<T, TO>::value && std::is_same<TL, float>::value),
-                    "msda fused: output dtype != value dtype or f16 offsets/logits need head_dim 32, "
-                    "L*P in {16, 32}, P = 4 and aligned strides");
-    const float* offlog = (const float*)offlog_v;
-    KINET_CHECK_ARG(vsb % c.vec == 0 && vss % c.vec == 0 && vsm % c.vec == 0 && ((uintptr_t)value % 16) == 0,
-                    "msda fused: value strides must keep %d-element vectors aligned", c.vec);
-    const int QT = 64 / c.lpq;          // queries per wave (= per workgroup)
-    const int MH = kThreads / 64;       // one head per wave
-    const int LP = L * P;
-    const size_t nsamp = (size_t)MH * QT * LP;
-    const bool pow2 = (LP & (LP - 1)) == 0 && LP <= 64;
-    const size_t lds = sizeof(LevelInfo) + nsamp * sizeof(Tap4) + (pow2 ? 0 : nsamp * sizeof(float));
-    KINET_CHECK_ARG(lds <= 160 * 1024, "msda fused: LDS request %zu too large", lds);
-    dim3 grid((Lq + QT - 1) / QT, N, (M + MH - 1) / MH);
-    if constexpr (!std::is_same<T, TO>::value || !std::is_same<TL, float>::value) return KINET_ERR_ARG;   // (rejected above)
-#define KF(VEC)                                                                                                  \
-    hipLaunchKernelGGL((msda_fused_kernel<T, VEC>), grid, dim3(kThreads), lds, stream, (const T*)value, vsb, vss, \
-                       vsm, shapes, offlog, ld_off, ref, ref_dim, qmask, loc_out, attw_out, (T*)out, S, M, D, L,   \
-                       Lq, P, QT, c.lpq, MH)
-    switch (c.vec) {
-        case 1: KF(1); break;
-        case 2: KF(2); break;
-        case 4: if (16 / sizeof(T) >= 4) { KF(4); } break;
-        case 8: if (16 / sizeof(T) >= 8) { KF(8); } break;
-    }
-#undef KF
-    KINET_LAUNCH_CHECK();
-    msda_fused_last = kFusedGeneric << 8 | c.vec;
-    return KINET_OK;
-}
-}  // namespace
-}  // namespace kinet
 
 extern "C" int kinet_msda_fused_forward(const void* value, int64_t value_sb, int64_t value_ss, int64_t value_sm,
                                         const int64_t* spatial_shapes, const void* offsets_logits, int ld_off,
@@ -1455,16 +1385,9 @@ extern "C" int kinet_msda_fused_forward(const void* value, int64_t value_sb, int
     KINET_CHECK_ARG(ref_dim == 2 || ref_dim == 4, "Last dim of reference_points must be 2 or 4, but get %d instead.", ref_dim);
     KINET_CHECK_ARG(ld_off >= num_heads * num_levels * num_point * 3, "msda fused: ld_off %d too small", ld_off);
     KINET_CHECK_ARG((loc_out == nullptr) == (attw_out == nullptr), "msda fused: loc_out/attw_out must both be set or both NULL");
-    if (value_sb == 0 && value_ss == 0 && value_sm == 0) {   // row-major (N, S, M, D)
-        value_ss = (int64_t)num_heads * channels;
-        value_sm = channels;
-        value_sb = value_ss * spatial_size;
-    }
+    default_strides(value_sb, value_ss, value_sm, spatial_size, num_heads, channels);
     KINET_CHECK_ARG(value_ss >= channels && value_sm >= 0 && value_sb >= 0, "msda fused: invalid value strides");
     KINET_CHECK_ARG((long long)spatial_size * value_ss < (1LL << 31), "msda fused: S*value_ss too large");
-    const size_t es = dtype_size(value_dtype);
-    const int vec_el = (int)(16 / (es ? es : 1));
-    (void)vec_el;
     hipStream_t s = (hipStream_t)stream;
 #define ARGS value, (long)value_sb, (int)value_ss, (long)value_sm, spatial_shapes, offsets_logits, ld_off, \
              ref_points, ref_dim, query_attn_mask, output, loc_out, attw_out, batch, spatial_size, num_heads, channels, \
@@ -1506,6 +1429,40 @@ extern "C" int kinet_msda_backward(const void* value, const int64_t* spatial_sha
 #undef ARGS
     set_error("msda backward: unsupported dtype pair value=%d loc=%d", value_dtype, loc_dtype);
     return KINET_ERR_ARG;
+}
+
+extern "C" int kinet_msda_launch_plan(const int64_t* problem, int cus, int32_t* plan_out) {
+    KINET_CHECK_ARG(problem != nullptr && plan_out != nullptr && cus > 0, "msda launch plan: invalid arguments");
+    const int64_t* f = problem;
+    for (int i = 0; i < KINET_MSDAP_FIELDS; ++i)
+        KINET_CHECK_ARG(i == KINET_MSDAP_VSB || i == KINET_MSDAP_VSS || i == KINET_MSDAP_VSM ||
+                            (f[i] >= INT32_MIN && f[i] <= INT32_MAX),
+                        "msda launch plan: field %d out of range", i);
+    KINET_CHECK_ARG(f[KINET_MSDAP_VSB] >= 0 && f[KINET_MSDAP_VSS] >= 0 && f[KINET_MSDAP_VSM] >= 0 &&
+                        f[KINET_MSDAP_VSS] <= INT32_MAX,
+                    "msda launch plan: invalid value strides");
+    MsdaProblem pb{};
+    pb.kind = (int)f[KINET_MSDAP_KIND];
+    pb.N = (int)f[KINET_MSDAP_N]; pb.S = (int)f[KINET_MSDAP_S]; pb.M = (int)f[KINET_MSDAP_M]; pb.D = (int)f[KINET_MSDAP_D];
+    pb.L = (int)f[KINET_MSDAP_L]; pb.Lq = (int)f[KINET_MSDAP_LQ]; pb.P = (int)f[KINET_MSDAP_P];
+    pb.value_dtype = (int)f[KINET_MSDAP_VALUE_DTYPE];
+    pb.out_dtype = (int)f[KINET_MSDAP_OUT_DTYPE];
+    pb.loc_dtype = (int)f[KINET_MSDAP_LOC_DTYPE];
+    int64_t sb = f[KINET_MSDAP_VSB], ss = f[KINET_MSDAP_VSS], sm = f[KINET_MSDAP_VSM];
+    if (pb.kind == MSDA_FUSED) default_strides(sb, ss, sm, pb.S, pb.M, pb.D);
+    pb.vsb = sb; pb.vss = ss; pb.vsm = sm;
+    pb.value_align = (int)f[KINET_MSDAP_VALUE_ALIGN];
+    pb.tune = BwdTune{(int)f[KINET_MSDAP_TUNE_MODE], (int)f[KINET_MSDAP_TUNE_LOG2_ROWS], (int)f[KINET_MSDAP_TUNE_QC],
+                      (int)f[KINET_MSDAP_TUNE_THREADS], (int)f[KINET_MSDAP_TUNE_FLUSH_AT]};
+    pb.dbg = (int)f[KINET_MSDAP_DEBUG];
+    pb.cus = cus;
+    MsdaPlan pl;
+    if (!msda_plan(pb, pl)) return refused(pl);
+    const int rec[KINET_MSDAPL_FIELDS] = {pl.family, pl.vec, pl.fused, pl.l, pl.nj, pl.sp, pl.pow2, pl.aln, pl.sg,
+                                          pl.grid[0], pl.grid[1], pl.grid[2], pl.block, pl.lds, pl.qt, pl.lpq, pl.na,
+                                          pl.QT, pl.MH, pl.QP, pl.qc, pl.log2ns, pl.blocked, pl.head_bytes, pl.last};
+    for (int i = 0; i < KINET_MSDAPL_FIELDS; ++i) plan_out[i] = rec[i];
+    return KINET_OK;
 }
 
 extern "C" int kinet_msda_backward_last_kernel(void) { return bwd_last; }

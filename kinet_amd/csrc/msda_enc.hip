@@ -37,26 +37,19 @@
 
 #include "../../include/kinet_msda.h"
 #include "common.h"
+#include "msda_plan.h"
 #include "msda_util.h"
 
 namespace kinet {
 namespace {
 
 constexpr int EW = 16;             // waves per workgroup (one workgroup per CU)
-constexpr int EQT = 16;            // queries per wave tile
-constexpr int EMAP_PIX = 2544;     // LDS map pixels of 64 B (162,816 B; the level table fits beside)
-// head_dim 36 (TAIL): the value as a 32-channel plane + a 4-channel TAIL plane (8 B per pixel,
-// kinet_gemm_headmajor_split); the LDS map holds both, 72 B per pixel: 2256 main pixels, then the
-// tail map (pixel x at ETB + 8x, the same pixel indexing as the main map).  Both fills round up
-// (main: pieces of 16 pixels, tail: 256-byte pieces), so the main budget is a multiple of 16 (its
-// last piece must not reach the tail map) and the tail's rounded fill stays inside the array
-constexpr int EMAP_T = 2256;
+// (EQT, EMAP_PIX, EMAP_T, EL, EHALO: msda_plan.h, with the strip planner)
 constexpr int ETB = EMAP_T * 64;
 static_assert(EMAP_T % 16 == 0 && ETB + (EMAP_T * 2 + 63) / 64 * 256 <= EMAP_PIX * 64, "tail map layout");
 constexpr int EWT = 12;   // TAIL: waves per workgroup (3 per SIMD: the tail's registers need > 128 VGPRs)
-constexpr int EL = 4, EP = 4;      // levels, points (the configs' values; host-checked)
+constexpr int EP = 4;              // points (the configs' value; host-checked)
 constexpr int EREC = EL * EP * 3;  // head-major offsets/logits per query and head (48)
-constexpr int EHALO = 4;           // rows staged beyond a strip's query rows on each side
 constexpr uint32_t TAF = 0x80000000u;
 #ifndef KINET_ENC_DYN
 #define KINET_ENC_DYN 1
@@ -78,13 +71,6 @@ struct EncLevels {
     int lb[EL];   // LDS level: map pixel of (row r, col c) = lb + r*W + c
     LevelRec rec[EL];
     int next_tile;   // the strip's next unclaimed tile (waves claim tiles as they finish one)
-};
-
-// launch plan (host): levels [0, fl) are gathered from the head map, levels [fl, EL) staged
-// per strip: region l = 1 margin pixel + cap[l] rows x W + 1 margin pixel at map pixel base[l]
-struct EncPlan {
-    int fl, nstrip, zpix, used;
-    int cap[EL], base[EL];
 };
 
 struct EncArgs {
@@ -792,62 +778,9 @@ __global__ __launch_bounds__(NW * 64) void msda_enc_kernel(const EncArgs a) {
     enc_tiles<TO, FL, REFD, QM, REC, TAIL, NW>(a, lv, vmap, b, m, strip, wave, lane);
 }
 
-// LDS regions for strips of 1/n of the image: rows ceil(H/n) + 3 (pixel centres, the +1 corner
-// row, a tile spilling into the next row) + 2*EHALO, at most the whole level + the two zero rows
-bool plan_layout(const int64_t* shapes, int fl, int n, EncPlan& pl, int budget = EMAP_PIX) {
-    int wmax = 0;
-    for (int l = fl; l < EL; ++l) wmax = std::max<int>(wmax, (int)shapes[2 * l + 1]);
-    long long pos = ((long long)wmax + 2 + 15) / 16 * 16;   // zero margin: a whole 2x2 footprint of any level
-    pl.zpix = (int)pos;
-    for (int l = 0; l < EL; ++l) pl.cap[l] = pl.base[l] = 0;
-    for (int l = fl; l < EL; ++l) {
-        const long long H = shapes[2 * l], W = shapes[2 * l + 1];
-        const long long cap = std::min<long long>(H + 2, (H + n - 1) / n + 3 + 2 * EHALO);
-        pl.cap[l] = (int)cap;
-        pl.base[l] = (int)pos;
-        pos += (cap * W + 2 + 15) / 16 * 16;
-        if (pos > budget) return false;
-    }
-    pl.used = (int)pos;
-    pl.fl = fl;
-    pl.nstrip = n;
-    return true;
-}
-
 // strips per head map requested by kinet_msda_encoder_set_strips for the calling thread (0 = the
 // plan's own choice; honoured when that many strips fit the LDS map)
 thread_local int enc_strips = 0;
-
-// the fewest gathered levels whose staged levels fit with strips of at least 16 tiles, then the
-// fewest strips (>= what fits) whose workgroups fill >= 90 % of their last round of one per CU
-bool enc_plan(const int64_t* shapes, int batch, int heads, int num_query, EncPlan& pl, bool tail = false) {
-    const int budget = tail ? EMAP_T : EMAP_PIX;
-    const int cus = cu_count();
-    const int maps = batch * heads;
-    const int ntile = (num_query + EQT - 1) / EQT;
-    const int nmax = std::max(1, ntile / EQT);
-    for (int fl = 0; fl < EL; ++fl) {
-        int nmin = 0;
-        for (int n = 1; n <= nmax && n <= 64; ++n)
-            if (plan_layout(shapes, fl, n, pl, budget)) {
-                nmin = n;
-                break;
-            }
-        if (!nmin) continue;
-        int n = nmin;
-        for (int c = nmin; c <= std::min(nmax, 2 * nmin + cus / std::max(1, maps)); ++c) {
-            const long long wgs = (long long)maps * c, rounds = (wgs + cus - 1) / cus;
-            if (wgs * 10 >= rounds * cus * 9) {
-                n = c;
-                break;
-            }
-        }
-        if (enc_strips >= nmin && enc_strips <= std::min(nmax, 64) && plan_layout(shapes, fl, enc_strips, pl, budget))
-            return true;
-        return plan_layout(shapes, fl, n, pl, budget);
-    }
-    return false;
-}
 
 }  // namespace
 }  // namespace kinet
@@ -863,22 +796,7 @@ extern "C" int kinet_msda_encoder_set_strips(int strips) {
 
 extern "C" int kinet_msda_encoder_plan(const int64_t* spatial_shapes_host, int batch, int num_heads, int num_query,
                                        int32_t* plan_out) {
-    KINET_CHECK_ARG(spatial_shapes_host != nullptr && batch > 0 && num_heads > 0 && num_query > 0,
-                    "msda encoder plan: bad arguments");
-    for (int l = 0; l < EL; ++l)
-        KINET_CHECK_ARG(spatial_shapes_host[2 * l] > 0 && spatial_shapes_host[2 * l + 1] > 0 &&
-                            spatial_shapes_host[2 * l] * spatial_shapes_host[2 * l + 1] < (1LL << 30),
-                        "msda encoder plan: bad level shape");
-    EncPlan pl{};
-    KINET_CHECK_ARG(enc_plan(spatial_shapes_host, batch, num_heads, num_query, pl),
-                    "msda encoder: no strip plan fits the LDS map (use kinet_msda_fused_forward)");
-    if (plan_out) {
-        plan_out[0] = pl.fl;
-        plan_out[1] = pl.nstrip;
-        plan_out[2] = pl.used;
-        plan_out[3] = batch * num_heads * pl.nstrip;
-    }
-    return KINET_OK;
+    return kinet_msda_encoder_plan_ex(spatial_shapes_host, batch, num_heads, num_query, 32, plan_out);
 }
 
 namespace {
@@ -923,7 +841,7 @@ int encoder_forward(const void* value, int64_t value_sb, int64_t value_sm, const
                     spatial_size);
     if (batch == 0 || num_query == 0) return KINET_OK;
     EncPlan pl{};
-    KINET_CHECK_ARG(enc_plan(spatial_shapes_host, batch, num_heads, num_query, pl, has_tail),
+    KINET_CHECK_ARG(enc_plan(spatial_shapes_host, batch, num_heads, num_query, pl, has_tail, cu_count(), enc_strips),
                     "msda encoder: no strip plan fits the LDS map (use kinet_msda_fused_forward)");
     const long long head_bytes = (long long)spatial_size * 64;
     // the tail plane's range stays below TAF >> 3 (an invalid gathered sample's offset)
@@ -969,55 +887,31 @@ int encoder_forward(const void* value, int64_t value_sb, int64_t value_sm, const
     const long long maps = (long long)batch * num_heads;
     KINET_CHECK_ARG(maps * pl.nstrip < (1LL << 31), "msda encoder: grid too large");
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)(maps * pl.nstrip)), block(EW * 64);
-    if (has_tail) {
-        const dim3 tblock(EWT * 64);
-#define TK(TO_, FL_, RD_, QM_) hipLaunchKernelGGL((msda_enc_kernel<TO_, FL_, RD_, QM_, false, true, EWT>), grid, tblock, 0, s, a)
-#define TK_QM(TO_, FL_, RD_) if (query_attn_mask) TK(TO_, FL_, RD_, true); else TK(TO_, FL_, RD_, false)
-#define TK_RD(TO_, FL_) if (ref_dim == 2) { TK_QM(TO_, FL_, 2); } else { TK_QM(TO_, FL_, 4); }
-#define TK_FL(TO_)                        \
-    switch (pl.fl) {                      \
-        case 0: TK_RD(TO_, 0) break;      \
-        case 1: TK_RD(TO_, 1) break;      \
-        case 2: TK_RD(TO_, 2) break;      \
-        default: TK_RD(TO_, 3) break;     \
-    }
-        if (output_dtype == KINET_BF16) {
-            TK_FL(bf16_t)
-        } else {
-            TK_FL(f16_t)
+    const dim3 grid((unsigned)(maps * pl.nstrip));
+    // msda_enc_kernel<TO, FL, REFD, QM, REC, TAIL, NW>: the three front ends
+    auto launch = [&](auto to, auto FL) {
+        using TO = decltype(to);
+        constexpr int fl = decltype(FL)::value;
+        if (rec) {
+            hipLaunchKernelGGL((msda_enc_kernel<TO, fl, 2, false, true>), grid, dim3(EW * 64), 0, s, a);
+            return;
         }
-#undef TK_FL
-#undef TK_RD
-#undef TK_QM
-#undef TK
-        KINET_LAUNCH_CHECK();
-        msda_fused_last = kFusedEncoder << 8 | 32 | pl.fl;
-        return KINET_OK;
-    }
-#define EK(TO_, FL_, RD_, QM_) hipLaunchKernelGGL((msda_enc_kernel<TO_, FL_, RD_, QM_>), grid, block, 0, s, a)
-#define EK_QM(TO_, FL_, RD_) if (query_attn_mask) EK(TO_, FL_, RD_, true); else EK(TO_, FL_, RD_, false)
-#define EK_RD(TO_, FL_)                                                                                  \
-    if (rec) hipLaunchKernelGGL((msda_enc_kernel<TO_, FL_, 2, false, true>), grid, block, 0, s, a);     \
-    else if (ref_dim == 2) { EK_QM(TO_, FL_, 2); } else { EK_QM(TO_, FL_, 4); }
-#define EK_FL(TO_)                        \
-    switch (pl.fl) {                      \
-        case 0: EK_RD(TO_, 0) break;      \
-        case 1: EK_RD(TO_, 1) break;      \
-        case 2: EK_RD(TO_, 2) break;      \
-        default: EK_RD(TO_, 3) break;     \
-    }
-    if (output_dtype == KINET_BF16) {
-        EK_FL(bf16_t)
-    } else {
-        EK_FL(f16_t)
-    }
-#undef EK_FL
-#undef EK_RD
-#undef EK_QM
-#undef EK
+        dispatch_int<2, 4>(ref_dim, [&](auto RD) {
+            dispatch_int<0, 1>(query_attn_mask != nullptr, [&](auto QM) {
+                constexpr int rd = decltype(RD)::value;
+                constexpr bool qm = decltype(QM)::value != 0;
+                if (has_tail)
+                    hipLaunchKernelGGL((msda_enc_kernel<TO, fl, rd, qm, false, true, EWT>), grid, dim3(EWT * 64), 0, s, a);
+                else
+                    hipLaunchKernelGGL((msda_enc_kernel<TO, fl, rd, qm>), grid, dim3(EW * 64), 0, s, a);
+            });
+        });
+    };
+    dispatch_int<0, 1, 2, 3>(pl.fl, [&](auto FL) {
+        if (output_dtype == KINET_BF16) launch(bf16_t{}, FL); else launch(f16_t{}, FL);
+    });
     KINET_LAUNCH_CHECK();
-    msda_fused_last = kFusedEncoder << 8 | (rec ? 16 : 0) | pl.fl;
+    msda_fused_last = kFusedEncoder << 8 | (has_tail ? 32 : rec ? 16 : 0) | pl.fl;
     return KINET_OK;
 }
 }  // namespace
@@ -1051,8 +945,12 @@ extern "C" int kinet_msda_encoder_plan_ex(const int64_t* spatial_shapes_host, in
     KINET_CHECK_ARG(channels == 32 || channels == 36, "msda encoder plan: head_dim 32 or 36 (got %d)", channels);
     KINET_CHECK_ARG(spatial_shapes_host != nullptr && batch > 0 && num_heads > 0 && num_query > 0,
                     "msda encoder plan: bad arguments");
+    for (int l = 0; l < EL; ++l)
+        KINET_CHECK_ARG(spatial_shapes_host[2 * l] > 0 && spatial_shapes_host[2 * l + 1] > 0 &&
+                            spatial_shapes_host[2 * l] * spatial_shapes_host[2 * l + 1] < (1LL << 30),
+                        "msda encoder plan: bad level shape");
     EncPlan pl{};
-    KINET_CHECK_ARG(enc_plan(spatial_shapes_host, batch, num_heads, num_query, pl, channels == 36),
+    KINET_CHECK_ARG(enc_plan(spatial_shapes_host, batch, num_heads, num_query, pl, channels == 36, cu_count(), enc_strips),
                     "msda encoder: no strip plan fits the LDS map (use kinet_msda_fused_forward)");
     if (plan_out) {
         plan_out[0] = pl.fl;

@@ -3,6 +3,7 @@
 // separate widening instruction).
 #pragma once
 #include "common.h"
+#include "msda_plan.h"
 
 namespace kinet {
 
@@ -12,7 +13,14 @@ typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 // the forward sampling kernel the calling thread's last fused / encoder call launched, in the
 // packing of kinet_msda_fused_last_kernel (defined in msda.hip; host-side bookkeeping only)
 extern thread_local int msda_fused_last;
-constexpr int kFusedGeneric = 1, kFusedFast = 2, kFusedEncoder = 3;
+
+// Run-time value -> compile-time constant for the launchers: f(std::integral_constant<int, V>{}) for
+// the V among Vs... that equals v (no call when none does), so a generic lambda names the kernel
+// instantiation once instead of one macro layer per template argument.
+template <int... Vs, typename F>
+inline void dispatch_int(int v, F&& f) {
+    (void)((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
 
 // acc += f16(half of x) * f16(half of w) in f32 (both multiplicands 16-bit sources)
 __device__ __forceinline__ float fma_mix16_lo_lo(float acc, uint32_t x, uint32_t w) {

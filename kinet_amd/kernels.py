@@ -1016,6 +1016,67 @@ def msda_encoder_plan(shapes, batch, n_heads, Lq, channels=32):
     return _enc_plans[key]
 
 
+# field order of kinet_msda_launch_plan's plan record (include/kinet_msda.h, kinet_msda_plan_field)
+MSDA_PLAN_FIELDS = ('family', 'vec', 'fused', 'l', 'nj', 'sp', 'pow2', 'aln', 'sg', 'grid_x', 'grid_y', 'grid_z', 'block',
+                    'lds', 'qt', 'lpq', 'na', 'QT', 'MH', 'QP', 'qc', 'log2ns', 'blocked', 'head_bytes', 'last')
+MSDA_FAMILIES = ('none', 'msda_fwd_kernel', 'msda_fused_kernel', 'msda_fused_fast_kernel', 'msda_bwd_list_kernel',
+                 'msda_bwd_kernel')
+MSDA_BWD_LAST = {1: 'msda_bwd_list_kernel', 0: 'msda_bwd_kernel'}   # kinet_msda_backward_last_kernel codes
+_launch_plans = {}
+
+
+def msda_launch_plan(kind, N_, S, M_, D, L, Lq, P_, value_dtype, out_dtype=None, loc_dtype=None, strides=(0, 0, 0),
+                     value_align=0, tune=(0, 0, 0, 0, 0), debug=0, cus=256):
+    """The launch kinet_msda_forward ('forward'), kinet_msda_fused_forward ('fused') or kinet_msda_backward
+    ('backward') makes for this problem (kinet_msda_launch_plan, csrc/msda_plan.h; no GPU call): a dict of
+    MSDA_PLAN_FIELDS with 'family' the kernel's name, or None when the entry point refuses it (the message
+    through kinet_last_error).  dtypes as torch dtypes; strides = value (sb, ss, sm) in elements; tune = the
+    arguments of kinet_msda_backward_tune.  Cached."""
+    loc_dtype = loc_dtype or (value_dtype if value_dtype in (torch.float32, torch.float64) else torch.float32)
+    key = (kind, N_, S, M_, D, L, Lq, P_, value_dtype, out_dtype or value_dtype, loc_dtype, tuple(strides),
+           value_align, tuple(tune), debug, cus)
+    if key not in _launch_plans:
+        f = [('forward', 'fused', 'backward').index(kind), N_, S, M_, D, L, Lq, P_, N.dtype_code(value_dtype),
+             N.dtype_code(out_dtype or value_dtype), N.dtype_code(loc_dtype), *strides, value_align, *tune, debug]
+        prob = (ctypes.c_int64 * len(f))(*[int(v) for v in f])
+        out = (ctypes.c_int32 * len(MSDA_PLAN_FIELDS))()
+        rc = N.lib().kinet_msda_launch_plan(ctypes.cast(prob, ctypes.c_void_p), int(cus), ctypes.cast(out, ctypes.c_void_p))
+        plan = None
+        if rc == 0:
+            plan = dict(zip(MSDA_PLAN_FIELDS, out))
+            plan['family'] = MSDA_FAMILIES[plan['family']]
+        _launch_plans[key] = plan
+    return _launch_plans[key]
+
+
+def _template_name(kernel, args, defaults):
+    """`kernel<args>` as rocprofv3 prints an instantiation: trailing arguments at their defaults dropped."""
+    args = list(args)
+    while defaults and args[-1] == defaults[-1]:
+        args, defaults = args[:-1], defaults[:-1]
+    return '%s<%s>' % (kernel, ', '.join(str(a).lower() if isinstance(a, bool) else str(a) for a in args))
+
+
+def msda_fused_kernel_name(plan, value_dtype, out_dtype, offlog_dtype):
+    """work['kernel'] of an msda_fused call from its launch plan."""
+    if plan is None or plan['family'] == 'none':
+        return 'none'
+    if plan['family'] == 'msda_fused_fast_kernel':
+        # template <T, TO, TL, L, P, MH = 4, SG = 4>
+        return _template_name(plan['family'], [_KT[value_dtype], _KT[out_dtype], _KT[offlog_dtype], plan['l'], 4,
+                                               plan['MH'], plan['sg']], [4, 4])
+    return '%s<%s, *>' % (plan['family'], _KT[value_dtype])
+
+
+def msda_encoder_kernel_name(out_dtype, fl, ref_dim, masked, front):
+    """work['kernel'] of an encoder sampler call: msda_enc_kernel<TO, FL, REFD, QM, REC = false, TAIL = false,
+    NW = 16> for the plan's gathered levels `fl` and the front end ('offlog', 'records' or 'split', as
+    msda_fused_last_kernel names them; the split kernel runs 12 waves)."""
+    rec, tail = front == 'records', front == 'split'
+    return _template_name('msda_enc_kernel', [_KT[out_dtype], fl, 2 if rec else ref_dim, bool(masked) and not rec, rec,
+                                              tail, 12 if tail else 16], [False, False, 16])
+
+
 # head_dim-36 encoder calls through the split value planes + kinet_msda_encoder_forward_split
 # when eligible; False keeps the generic fused kernel on the (M, B, S, 36) value (A/B and tests)
 MSDA_SPLIT = [True]
@@ -1059,8 +1120,7 @@ def msda_encoder_split(value, shapes, offlog_hm, reference_points, n_heads, quer
     offlog_hm = offlog_hm.contiguous()
     nsamp = B * Lq * M_ * 16
     plan = msda_encoder_plan(key, B, M_, Lq, 36)
-    kname = 'msda_enc_kernel<%s, %d, %d, %s, false, true, 12>' % (_KT[od], plan[0] if plan else -1, ref.shape[-1],
-                                                                  'true' if qm is not None else 'false')
+    kname = msda_encoder_kernel_name(od, plan[0] if plan else -1, ref.shape[-1], qm is not None, 'split')
     N.call('kinet_msda_encoder_forward_split', N.ptr(main), main.stride(1), main.stride(0), N.ptr(tail),
            tail.stride(1), tail.stride(0), N.ptr(hs), N.ptr(offlog_hm), N.ptr(ref), ref.shape[-1], N.ptr(qm),
            N.ptr(out), B, S, M_, D, 4, Lq, 4, N.dtype_code(od), N.ptr(query_tile_order), N.stream(main.device),
@@ -1156,8 +1216,7 @@ def msda_encoder(value, shapes, offlog_hm, reference_points, n_heads, query_attn
     nsamp = B * Lq * M_ * 16
     plan = msda_encoder_plan(key, B, M_, Lq)
     # the instantiation kinet_msda_encoder_forward launches (as rocprofv3 names it)
-    kname = 'msda_enc_kernel<%s, %d, %d, %s>' % (_KT[od], plan[0] if plan else -1, ref.shape[-1],
-                                                   'true' if qm is not None else 'false')
+    kname = msda_encoder_kernel_name(od, plan[0] if plan else -1, ref.shape[-1], qm is not None, 'offlog')
     N.call('kinet_msda_encoder_forward', N.ptr(value), value.stride(1), value.stride(0), N.ptr(hs), N.ptr(offlog_hm),
            N.ptr(ref), ref.shape[-1], N.ptr(qm), N.ptr(out), B, S, M_, D, 4, Lq, 4, N.dtype_code(od),
            N.ptr(query_tile_order), N.stream(value.device),
@@ -1238,7 +1297,7 @@ def msda_encoder_records(value, shapes, records, frac_bits, out_dtype=None, quer
     records = records.contiguous()
     nsamp = B * Lq * M_ * 16
     plan = msda_encoder_plan(key, B, M_, Lq)
-    kname = 'msda_enc_kernel<%s, %d, 2, false, true>' % (_KT[od], plan[0] if plan else -1)
+    kname = msda_encoder_kernel_name(od, plan[0] if plan else -1, 2, False, 'records')
     N.call('kinet_msda_encoder_forward_records', N.ptr(value), value.stride(1), value.stride(0), N.ptr(hs),
            N.ptr(records), int(frac_bits), N.ptr(out), B, S, M_, D, 4, Lq, 4, N.dtype_code(od),
            N.ptr(query_tile_order), N.stream(value.device),
@@ -1301,13 +1360,10 @@ def msda_fused(value, spatial_shapes, offlog, reference_points, n_heads, n_level
         raise RuntimeError('msda_fused: the offsets/logits projection must be f32 or f16')
     ev = value.element_size()
     nsamp = B * Lq * n_heads * n_levels * n_points
-    # the instantiation launch_fused (csrc/msda.hip) picks, as rocprofv3 names it
-    if (ev == 2 and D == 32 and n_points == 4 and n_levels in (4, 8) and vss % 8 == 0 and vsb % 8 == 0
-            and vsm % 8 == 0):
-        kname = 'msda_fused_fast_kernel<%s, %s, %s, %s>' % (_KT[value.dtype], _KT[od], _KT[offlog.dtype],
-                                                             '4, 4, 2, 2' if n_levels == 4 else '8, 4')
-    else:
-        kname = 'msda_fused_kernel<%s, *>' % _KT[value.dtype]
+    # the instantiation kinet_msda_fused_forward launches, as rocprofv3 names it
+    kname = msda_fused_kernel_name(
+        msda_launch_plan('fused', B, S, n_heads, D, n_levels, Lq, n_points, value.dtype, od, offlog.dtype,
+                         (vsb, vss, vsm), value.data_ptr() % 16), value.dtype, od, offlog.dtype)
     N.call('kinet_msda_fused_forward', N.ptr(value), vsb, vss, vsm, N.ptr(spatial_shapes), N.ptr(offlog),
            offlog.shape[-1], N.ptr(ref), ref.shape[-1], N.ptr(qm), N.ptr(out), N.ptr(loc), N.ptr(attw), B, S,
            n_heads, D, n_levels, Lq, n_points, N.dtype_code(value.dtype), N.dtype_code(od), N.dtype_code(offlog.dtype),

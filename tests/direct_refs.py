@@ -1594,3 +1594,153 @@ def msda_bound(samp, shapes, kernel, out_dtype, locA=None, attw_c=None):
         c = (attw_c.amax((3, 4)) + 2) * U32
         b = b + (c[..., None] * A.reshape(B, Lq, M, -1)).reshape(A.shape)
     return b + 1e-30
+
+
+# ----------------------------------------------------------------------------------------------
+# MSDA launch plans (csrc/msda_plan.h through kinet_msda_launch_plan), worked by hand from the rules
+# ----------------------------------------------------------------------------------------------
+# sizeof the device structs the LDS formulas count (msda_plan.h; msda.hip static_asserts them)
+MSDA_LDS_LIMIT = 160 * 1024
+MSDA_LEVELINFO, MSDA_TAP4, MSDA_TAP4D, MSDA_BWDTAP32, MSDA_BWDTAP64, MSDA_HTAP = 256, 32, 48, 40, 64, 32
+MSDA_FUSED_GENERIC, MSDA_FUSED_FAST = 1 << 8, 2 << 8     # kinet_msda_fused_last_kernel: family << 8 | detail
+MSDA_KEEP_LAST = -2                                       # the plain forward records no last kernel
+
+# (element size, D, M) -> (vec, lanes per (query, head), queries per workgroup); qt 0 = refused
+MSDA_CFG_CASES = [
+    (4, 32, 8, (4, 8, 4)),
+    (2, 36, 8, (4, 9, 3)), (4, 36, 8, (4, 9, 3)),
+    (8, 32, 8, (2, 16, 2)),
+    (4, 33, 8, (1, 33, 0)), (2, 33, 8, (1, 33, 0)),
+]
+
+# the level set of test_backward_list_kernel_vs_oracle
+MSDA_BWD_LEVELS = ((20, 33), (10, 17), (5, 9), (3, 5))
+MSDA_BWD_S = 890
+
+
+def msda_plan_row(family, **f):
+    """A full plan record: every field 0 but grid (1, 1, 1) and the ones named."""
+    import kinet_amd.kernels as K
+    row = dict.fromkeys(K.MSDA_PLAN_FIELDS, 0)
+    row.update(family=family, grid_x=1, grid_y=1, grid_z=1, last=MSDA_KEEP_LAST)
+    grid = f.pop('grid', None)
+    if grid:
+        row.update(zip(('grid_x', 'grid_y', 'grid_z'), tuple(grid) + (1,) * (3 - len(grid))))
+    row.update(f)
+    return row
+
+
+def msda_list_lds(QP, LP, D, log2ns):
+    """LevelInfo | keys, head, plist [2^log2ns] | npass[4] | cinfo (int2) + next per corner | G[QP][D] | taps"""
+    return MSDA_LEVELINFO + 3 * (1 << log2ns) * 4 + 16 + QP * LP * 4 * (8 + 4) + QP * D * 4 + QP * LP * MSDA_HTAP
+
+
+def _bwd_list(D, grid, block=256, QP=16, qc=16, log2ns=10, blocked=1, sp=2):
+    return msda_plan_row('msda_bwd_list_kernel', vec=4, nj=(D + 15) // 16, sp=sp, grid=grid, block=block,
+                         lds=msda_list_lds(QP, 16, D, log2ns), na=D // 4, QP=QP, qc=qc, log2ns=log2ns, blocked=blocked,
+                         last=1)
+
+
+def _bwd_direct(D, Lq):
+    """f32, M = 8, L*P = 16: D = 32 -> 8 lanes x 4 queries; D = 36 -> 9 lanes padded to 16 x 2 queries, ALN."""
+    lpq, qt = (8, 4) if D == 32 else (16, 2)
+    return msda_plan_row('msda_bwd_kernel', vec=4, pow2=1, aln=int(D == 36), qt=qt, lpq=lpq, na=D // 4,
+                         grid=(-(-Lq // qt), 2), block=256, lds=MSDA_LEVELINFO + qt * 8 * 16 * MSDA_BWDTAP32, last=0)
+
+
+# (name, value dtype, D, Lq, tune (mode, log2_rows, queries per block, threads, queries per pass)) -> plan;
+# N = 2, M = 8, L = P = 4, S = 890.  Blocked grid: ceil(S / QP) blocks + 1/8 + 2 per level.
+MSDA_BWD_CASES = [
+    ('auto', 'f32', 32, 890, (0, 0, 0, 0, 0), _bwd_list(32, (56 + 7 + 8, 2, 8))),
+    ('auto Lq != S', 'f32', 32, 947, (0, 0, 0, 0, 0), _bwd_direct(32, 947)),
+    ('auto D36 Lq != S', 'f32', 36, 947, (0, 0, 0, 0, 0), _bwd_direct(36, 947)),
+    ('mode -1', 'f32', 32, 890, (-1, 0, 0, 0, 0), _bwd_direct(32, 890)),
+    ('mode 1 Lq != S', 'f32', 32, 947, (1, 0, 0, 0, 0), _bwd_list(32, (60, 2, 8), blocked=0)),
+    ('mode 2', 'f32', 32, 890, (2, 0, 0, 0, 0), _bwd_list(32, (56, 2, 8), blocked=0)),
+    ('mode 3', 'f32', 32, 890, (3, 0, 0, 0, 0), _bwd_list(32, (71, 2, 8), sp=4)),
+    # f64: 16 lanes x 2 doubles, 2 queries; f64 sums: never the list kernel, no ALN
+    ('f64', 'f64', 32, 890, (0, 0, 0, 0, 0),
+     msda_plan_row('msda_bwd_kernel', vec=2, pow2=1, qt=2, lpq=16, na=16, grid=(445, 2), block=256,
+                   lds=MSDA_LEVELINFO + 2 * 8 * 16 * MSDA_BWDTAP64, last=0)),
+    ('f64 mode 1', 'f64', 32, 890, (1, 0, 0, 0, 0),
+     msda_plan_row('msda_bwd_kernel', vec=2, pow2=1, qt=2, lpq=16, na=16, grid=(445, 2), block=256,
+                   lds=MSDA_LEVELINFO + 2 * 8 * 16 * MSDA_BWDTAP64, last=0)),
+    # D = 80: nj = 5 > 4; 20 lanes padded to 32, one query per workgroup
+    ('D80', 'f32', 80, 890, (0, 0, 0, 0, 0),
+     msda_plan_row('msda_bwd_kernel', vec=4, pow2=1, qt=1, lpq=32, na=20, grid=(890, 2), block=256,
+                   lds=MSDA_LEVELINFO + 8 * 16 * MSDA_BWDTAP32, last=0)),
+]
+# every (tune, extra queries) of test_backward_list_kernel_vs_oracle at D = 32 and 36
+MSDA_BWD_TUNE_CASES = []
+for _D in (32, 36):
+    MSDA_BWD_TUNE_CASES += [
+        ((0, 0, 0, 0, 0), 0, _D, _bwd_list(_D, (71, 2, 8))),
+        ((1, 0, 0, 0, 0), 57, _D, _bwd_list(_D, (60, 2, 8), blocked=0)),
+        ((1, 6, 32, 256, 0), 57, _D, _bwd_list(_D, (30, 2, 8), qc=32, log2ns=6, blocked=0)),
+        ((1, 6, 64, 512, 16), 57, _D, _bwd_list(_D, (15, 2, 8), block=512, qc=64, log2ns=6, blocked=0)),
+        # passes of 64 queries: ceil(890 / 64) = 14 blocks + 1 + 8
+        ((1, 10, 512, 512, 64), 0, _D, _bwd_list(_D, (23, 2, 8), block=512, QP=64, qc=512)),
+        ((2, 0, 0, 0, 0), 0, _D, _bwd_list(_D, (56, 2, 8), blocked=0)),
+        ((0, 0, 0, 0, 0), 57, _D, _bwd_direct(_D, 947)),
+        ((-1, 0, 0, 0, 0), 0, _D, _bwd_direct(_D, 890)),
+        ((3, 0, 0, 0, 0), 0, _D, _bwd_list(_D, (71, 2, 8), sp=4)),
+    ]
+
+
+def _fused_fast(L, Lq, N, M, S, vss=256):
+    MH = 2 if L == 4 else 4
+    return msda_plan_row('msda_fused_fast_kernel', l=L, sg=MH, QT=16, MH=MH, grid=(-(-Lq // 16), N, -(-M // MH)),
+                         block=64 * MH, lds=0, head_bytes=((S - 1) * vss + 32) * 2, last=MSDA_FUSED_FAST | L)
+
+
+def _fused_generic(vec, lpq, LP, Lq, N, M):
+    """one head per wave, 64 // lpq queries per wave, 4 waves; logits staged (4 B) unless L*P is a power of two"""
+    QT = 64 // lpq
+    pow2 = LP & (LP - 1) == 0 and LP <= 64
+    return msda_plan_row('msda_fused_kernel', vec=vec, lpq=lpq, QT=QT, MH=4, grid=(-(-Lq // QT), N, -(-M // 4)),
+                         block=256, lds=MSDA_LEVELINFO + 4 * QT * LP * (MSDA_TAP4 + (0 if pow2 else 4)),
+                         last=MSDA_FUSED_GENERIC | vec)
+
+
+MSDA_ALIGN_MSG = 'msda fused: value strides must keep 8-element vectors aligned'
+MSDA_F16_MSG = ('msda fused: output dtype != value dtype or f16 offsets/logits need head_dim 32, '
+                'L*P in {16, 32}, P = 4 and aligned strides')
+# (name, dict(value, out, offlog dtypes, D, L, P, S, Lq, N, M, strides (sb, ss, sm), align)) -> plan, or the
+# refusal's message.  Row-major strides of (N, S, 8, 32): (S * 256, 256, 32).
+_FB = dict(value='bf16', out='bf16', offlog='f32', D=32, L=4, P=4, S=890, Lq=947, N=2, M=8, strides=(890 * 256, 256, 32),
+           align=0)
+MSDA_FUSED_CASES = [
+    ('fast L4', _FB, _fused_fast(4, 947, 2, 8, 890)),
+    ('fast L4 f16 -> bf16, f16 offsets', dict(_FB, value='f16', offlog='f16'), _fused_fast(4, 947, 2, 8, 890)),
+    ('fast L4 M5', dict(_FB, M=5, strides=(890 * 160, 160, 32)), _fused_fast(4, 947, 2, 5, 890, 160)),
+    ('fast L8', dict(_FB, L=8), _fused_fast(8, 947, 2, 8, 890)),
+    ('fast L8 M5', dict(_FB, L=8, M=5, strides=(890 * 160, 160, 32)), _fused_fast(8, 947, 2, 5, 890, 160)),
+    ('fast head-major', dict(_FB, strides=(890 * 32, 32, 2 * 890 * 32)), _fused_fast(4, 947, 2, 8, 890, 32)),
+    # one condition of the fast kernel broken at a time: the generic kernel (8 bf16 per lane, 4 lanes, 16 queries
+    # per wave) -- which itself needs 8-element alignment
+    ('pixel stride % 8', dict(_FB, strides=(890 * 260, 260, 32)), MSDA_ALIGN_MSG),
+    ('batch stride % 8', dict(_FB, strides=(890 * 256 + 4, 256, 32)), MSDA_ALIGN_MSG),
+    ('head stride % 8', dict(_FB, strides=(890 * 256, 256, 36)), MSDA_ALIGN_MSG),
+    ('pointer % 16', dict(_FB, align=8), MSDA_ALIGN_MSG),
+    ('head_bytes 2^31 + 64', dict(_FB, S=(1 << 22) + 1, strides=(((1 << 22) + 1) * 256, 256, 32)),
+     _fused_generic(8, 4, 16, 947, 2, 8)),
+    ('head_bytes 2^31 - 448', dict(_FB, S=1 << 22, strides=((1 << 22) * 256, 256, 32)), _fused_fast(4, 947, 2, 8, 1 << 22)),
+    ('P = 2', dict(_FB, P=2), _fused_generic(8, 4, 8, 947, 2, 8)),
+    ('L = 3, P = 5', dict(_FB, L=3, P=5), _fused_generic(8, 4, 15, 947, 2, 8)),
+    ('D = 36', dict(_FB, D=36, strides=(890 * 288, 288, 36)), _fused_generic(4, 9, 16, 947, 2, 8)),
+    ('f32', dict(_FB, value='f32', out='f32'), _fused_generic(4, 8, 16, 947, 2, 8)),
+    ('f16 offsets, D = 36', dict(_FB, D=36, strides=(890 * 288, 288, 36), offlog='f16'), MSDA_F16_MSG),
+    ('f16 -> bf16, P = 2', dict(_FB, value='f16', P=2), MSDA_F16_MSG),
+    ('empty', dict(_FB, Lq=0), msda_plan_row('none', last=-1)),
+]
+
+# plain forward: (value dtype, D, Lq) -> plan; N = 2, M = 8, L = P = 4
+MSDA_FWD_CASES = [
+    ('f32', 32, 947, msda_plan_row('msda_fwd_kernel', vec=4, qt=4, lpq=8, grid=(237, 2), block=256,
+                                    lds=MSDA_LEVELINFO + 4 * 8 * 16 * MSDA_TAP4)),
+    ('bf16', 36, 947, msda_plan_row('msda_fwd_kernel', vec=4, qt=3, lpq=9, grid=(316, 2), block=256,
+                                     lds=MSDA_LEVELINFO + 3 * 8 * 16 * MSDA_TAP4)),
+    ('f64', 32, 947, msda_plan_row('msda_fwd_kernel', vec=2, qt=2, lpq=16, grid=(474, 2), block=256,
+                                    lds=MSDA_LEVELINFO + 2 * 8 * 16 * MSDA_TAP4D)),
+    ('f32', 32, 0, msda_plan_row('none')),
+]

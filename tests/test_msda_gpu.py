@@ -132,11 +132,18 @@ def test_backward_list_kernel_vs_oracle(MSDA, tune, extra, D):
     attw = torch.rand(N, Lq, M, L, P, generator=g)
     go = torch.randn(N, Lq, M * D, generator=g)
     lib = _native.lib()
+    from kinet_amd import kernels as K
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
     lib.kinet_msda_backward_tune(*tune)
     try:
         gv, gl, ga = MSDA.ms_deform_attn_backward(value.cuda(), shapes.cuda(), loc.cuda(), attw.cuda(), go.cuda(), 64)
+        # the kernel the plan names is the kernel the call launched
+        plan = K.msda_launch_plan('backward', N, S, M, D, L, Lq, P, torch.float32, tune=tune, cus=cus)
+        assert plan['family'] == K.MSDA_BWD_LAST[lib.kinet_msda_backward_last_kernel()]
         gvh, _, _ = MSDA.ms_deform_attn_backward(value.cuda().bfloat16(), shapes.cuda(), loc.cuda(), attw.cuda(),
                                                  go.cuda().bfloat16(), 64)
+        plan = K.msda_launch_plan('backward', N, S, M, D, L, Lq, P, torch.bfloat16, tune=tune, cus=cus)
+        assert plan['family'] == K.MSDA_BWD_LAST[lib.kinet_msda_backward_last_kernel()]
         torch.cuda.synchronize()
     finally:
         lib.kinet_msda_backward_tune(0, 0, 0, 0, 0)
