@@ -10,10 +10,11 @@
  * tensor round-tripping through HBM.
  *
  * Weights are packed once (kinet_ffn_pack) from the PyTorch layouts W1 (F, D), W2 (D, F)
- * into a fragment-major stream: for each 32-unit hidden chunk c, 2*(D/32) 1-KiB fragments
- * of W1 rows [32c, 32c+32) followed by D/16 fragments of W2 columns [32c, 32c+32), each
- * fragment laid out exactly as the 64 lanes of a v_mfma_f32_16x16x32 operand read it, so the
- * kernel moves it with LDS-DMA and reads it conflict-free.  packed size = 2*D*F elements.
+ * into a fragment-major stream of 1-KiB fragments, each laid out exactly as the 64 lanes of a
+ * v_mfma_f32_16x16x32 operand read it, so the kernel moves it with LDS-DMA and reads it
+ * conflict-free.  packed size = 2*D*F elements.  The layout of this and the three other packed
+ * streams below is defined in one place, ffn_pack_src (csrc/ffn_plan.h); kinet_ffn_pack_map
+ * writes it out as an index map.
  *
  * dtype: KINET_BF16 or KINET_F16 for X, the packed weights and Y (f32 accumulation, the
  * hidden activations rounded to dtype exactly where the unfused GEMM would store them).
@@ -48,9 +49,9 @@ int kinet_ffn_fused(const void* X, int ldx, const void* packed, const float* b1,
  * ascending k, in another order than the GEMM's, so a rounding of x may differ from the
  * two-launch path's by one ulp of dtype.
  * kinet_ffn_pack_attn: Wo (D, D), W1 (F, D), W2 (D, F) of dtype -> D*D + 2*D*F elements: first
- * Wo as (D/32) * (D/16) 1-KiB MFMA operand fragments, k-step major (fragment (ks, nt), lane
- * (g, c), element j = Wo[32 (nt / 2) + 8 (c / 4) + 4 (nt % 2) + c % 4][32 ks + 8 g + j]), i.e. at
- * D = 256 four ring chunks of 32 fragments; then exactly the stream kinet_ffn_pack writes.
+ * Wo as (D/32) * (D/16) 1-KiB MFMA operand fragments, k-step major (ffn_pack_src, kind
+ * KINET_FFN_PACK_ATTN), i.e. at D = 256 four ring chunks of 32 fragments; then exactly the stream
+ * kinet_ffn_pack writes.
  * kinet_attn_out_ffn_fused: D = 256 only (at D = 288 Wo does not fill whole ring chunks:
  * KINET_ERR_ARG), F % 32 == 0, F <= 2048; lda, ldr, ldy >= D and multiples of 8; every pointer
  * 16-byte aligned; every tensor below 2 GiB; bo, ln1_gamma, ln1_beta (D) f32 required; b1 (F),
@@ -106,6 +107,45 @@ int kinet_bottleneck_pack_ds(const float* W3, const float* Wds, const float* W1,
 int kinet_bottleneck_pair_ds(const void* X, int ldx, const void* X0, int ldx0, const void* packed,
                              const float* b3ds, const float* b1, void* Y, void* T, int M, int D, int F,
                              int DB, int dtype, kinet_stream_t stream);
+
+/* Diagnostics and planning (host side, per calling thread; no reference counterpart).
+ * kinet_ffn_set_debug: A/B and test knobs, the FfnDebug bits of csrc/ffn_plan.h; returns the
+ * previous value.
+ * kinet_ffn_launch_plan: the launch kinet_ffn_fused, kinet_attn_out_ffn_fused, kinet_bottleneck_pair
+ * or kinet_bottleneck_pair_ds makes for a described problem on a device of `cus` compute units,
+ * under the calling thread's debug bits and the kinet_set_solo_launch policy as a real call reads
+ * them (csrc/ffn_plan.h; no GPU call).  problem: KINET_FFNP_FIELDS ints, plan_out: KINET_FFNPL_FIELDS
+ * ints.  KINET_ERR_ARG with the entry point's message where it refuses D or DB (its other argument
+ * checks are not repeated here).  M = 0: grid 0, nothing would be launched.
+ * kinet_ffn_last_kernel: KINET_FFNPL_KERNEL of the calling thread's last launch of these four entry
+ * points (-1: none yet); kinet_ffn_kernel_name: the instantiation's name but for the element type
+ * (NULL: no such index).
+ * kinet_ffn_pack_map: the whole layout of a packed stream of `kind` as (source matrix in the pack
+ * call's argument order, row, column) per packed element: out holds 3 ints for each of the stream's
+ * elements (kinet_ffn_pack: 2 D F; _pack_attn: D D + 2 D F; kinet_bottleneck_pack: (D + DB) F;
+ * _pack_ds: (2 D + DB) F).  D, F, DB multiples of 32; DB = D but for KINET_FFN_PACK_PAIR. */
+enum kinet_ffn_problem_field {
+    KINET_FFNP_KIND = 0,   /* 0 kinet_ffn_fused, 1 kinet_attn_out_ffn_fused, 2 kinet_bottleneck_pair, 3 _pair_ds */
+    KINET_FFNP_M, KINET_FFNP_D, KINET_FFNP_F, KINET_FFNP_DB,
+    KINET_FFNP_FIELDS
+};
+enum kinet_ffn_plan_field {
+    KINET_FFNPL_KERNEL = 0,   /* index into the table of instantiations (kinet_ffn_kernel_name) */
+    KINET_FFNPL_TILES,        /* row tiles of KINET_FFNPL_TILE_ROWS rows */
+    KINET_FFNPL_GRID, KINET_FFNPL_BLOCK, KINET_FFNPL_WAVES,
+    KINET_FFNPL_TILE_ROWS,
+    KINET_FFNPL_WG_TILES,     /* row tiles a workgroup works on at a time */
+    KINET_FFNPL_WG_PER_CU,    /* resident workgroups per CU the grid is sized for */
+    KINET_FFNPL_LDS,          /* LDS bytes of a workgroup */
+    KINET_FFNPL_FIELDS
+};
+enum kinet_ffn_pack_kind { KINET_FFN_PACK_FFN = 0, KINET_FFN_PACK_PAIR, KINET_FFN_PACK_DS, KINET_FFN_PACK_ATTN };
+
+int kinet_ffn_set_debug(int flags);
+int kinet_ffn_launch_plan(const int* problem, int cus, int* plan_out);
+int kinet_ffn_last_kernel(void);
+const char* kinet_ffn_kernel_name(int kernel);
+int kinet_ffn_pack_map(int kind, int D, int F, int DB, int32_t* out);
 
 #ifdef __cplusplus
 }

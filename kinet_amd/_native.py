@@ -57,6 +57,10 @@ _SIGS = {
     'kinet_gemm_splitk': [P, P, P] + [I] * 7 + [P, P, P, I, I, P, P, F, I, P, P, I, P],
     'kinet_ffn_pack': [P, P, P, I, I, I, P],
     'kinet_ffn_set_debug': [I],
+    'kinet_ffn_launch_plan': [P, I, P],
+    'kinet_ffn_last_kernel': [],
+    'kinet_ffn_kernel_name': [I],
+    'kinet_ffn_pack_map': [I, I, I, I, P],
     'kinet_ffn_fused': [P, I, P, P, P, P, P, F, P, I, I, I, I, I, P],
     'kinet_ffn_pack_attn': [P, P, P, P, I, I, I, P],
     'kinet_attn_out_ffn_fused': [P, I, P, I, P, P, P, P, F, P, P, P, P, F, P, I, I, I, I, I, P],
@@ -117,7 +121,7 @@ _SIGS = {
     'kinet_last_error': [],
     'kinet_version': [],
 }
-_RESTYPES = {'kinet_last_error': ctypes.c_char_p, 'kinet_version': ctypes.c_char_p,
+_RESTYPES = {'kinet_last_error': ctypes.c_char_p, 'kinet_version': ctypes.c_char_p, 'kinet_ffn_kernel_name': ctypes.c_char_p,
              'kinet_msda_backward_workspace_bytes': ctypes.c_int64, 'kinet_msda_backward_tune': None,
              'kinet_groupnorm_workspace': ctypes.c_long, 'kinet_segm_gn_workspace': ctypes.c_long,
              'kinet_gemm_tn_workspace': ctypes.c_int64, 'kinet_colsum_workspace': ctypes.c_int64,

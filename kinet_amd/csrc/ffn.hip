@@ -25,6 +25,7 @@
 
 #include "../../include/kinet_ffn.h"
 #include "common.h"
+#include "ffn_plan.h"
 #include "gemm_common.h"
 
 namespace kinet {
@@ -41,13 +42,7 @@ struct FfnArgs {
     float eps;
     int ldx, ldy, M, F;
     int x_bytes, w_bytes, y_bytes;
-    int dbg;   // diagnostic knobs (kinet_ffn_set_debug): 1 = no weight DMA after the prologue
-               // (timing only, results are garbage); 2 = the 4-wave x 32-row tile at D = 256;
-               // 8 = the 8-wave x 16-row tile (default: 8 waves x 32 rows, ffn_fused_rt2_kernel);
-               // 64 = kinet_attn_out_ffn_fused stages its residual loads under the Wo chunks (RV = 1);
-               // 16 = kinet_bottleneck_pair at D = 64 on the LDS-ring kernel (bneck_pair_kernel);
-               // 128 / 256 = kinet_bottleneck_pair at D = 128 / 256 on 1- / 2-row-tile waves;
-               // 512 = kinet_bottleneck_pair_ds on 2-row-tile waves (bneck64_ds_kernel<T, 2>)
+    int dbg;   // FfnDebug bits of the calling thread (ffn_plan.h); the kernels read FFN_DBG_NO_DMA
     // kinet_attn_out_ffn_fused only (ffn_fused_rt2_kernel<.., PRE>): x = LN1(R + A Wo^T + bo)
     const void* A;   // attention output (M, D), row stride lda
     const void* R;   // residual (M, D), row stride ldr
@@ -58,16 +53,20 @@ struct FfnArgs {
     int lda, ldr, a_bytes, r_bytes;
 };
 
-thread_local int ffn_debug = 0;   // test-only knob (kinet_ffn_set_debug), per calling thread
+thread_local int ffn_debug = 0;    // test-only knobs (kinet_ffn_set_debug, FfnDebug), per calling thread
+thread_local int ffn_last = -1;    // kFfnKernels index of the calling thread's last launch (kinet_ffn_last_kernel)
 
-template <int D>
-struct FfnGeo {
-    static_assert(D % 32 == 0, "D must be a multiple of 32");
-    static constexpr int KS = D / 32;        // 32-deep K steps of linear1
-    static constexpr int NT = D / 16;        // 16-wide output tiles of linear2
-    static constexpr int FR = 2 * KS + NT;   // 1-KiB fragments per 32-unit hidden chunk
-    static constexpr int CHUNK = FR * 1024;
-};
+// the table entry of an instantiation (ffn_plan.h): each kernel checks its tile and its LDS against it
+template <int FAMILY, int D, int RT, int WAVES, int DB = 0, bool PRE = false, int RV = 0>
+constexpr FfnKernel ffn_entry() {
+    constexpr int i = ffn_kernel_index(FAMILY, D, RT, WAVES, DB, PRE, RV);
+    static_assert(i >= 0, "an instantiation the table does not list");
+    return kFfnKernels[i];
+}
+template <int LDS, int ROWS, int NS>
+constexpr bool ffn_entry_is(const FfnKernel k) {
+    return ffn_kernel_lds(k) == LDS && LDS * k.wg_per_cu <= kFfnLdsLimit && k.tile_rows == ROWS && k.ns == NS;
+}
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
@@ -122,13 +121,6 @@ __device__ __forceinline__ void dma16s(__amdgpu_buffer_rsrc_t r, char* dst, unsi
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)dst, 16, voff, soff, 0, 0);
 }
 
-constexpr int FFN_MAX_F = 2048;
-
-// output column of MFMA row m of phase-B tile nt: lane group g holds, for the tile pair
-// (2kp, 2kp+1), the 8 consecutive columns 32kp + 8g .. +7 -- the same columns its phase-A
-// x fragment xr[kp] holds, so the residual comes from registers and stores are 16 bytes
-__host__ __device__ constexpr int ffn_sigma(int nt, int m) { return 32 * (nt >> 1) + 8 * (m >> 2) + 4 * (nt & 1) + (m & 3); }
-
 template <typename T, int D, int RT, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void ffn_fused_kernel(const FfnArgs p, const int ntiles) {
     using G = FfnGeo<D>;
@@ -144,6 +136,7 @@ __global__ __launch_bounds__(WAVES * 64) void ffn_fused_kernel(const FfnArgs p, 
     constexpr unsigned OOB = 0x80000000u;
     constexpr int PAR = (FFN_MAX_F + 3 * D) * 4;
     __shared__ __attribute__((aligned(16))) char lds[PAR + NS * G::CHUNK];
+    static_assert(ffn_entry_is<sizeof(lds), ROWS, NS>(ffn_entry<FFN_K_FUSED, D, RT, WAVES>()), "ffn_plan.h");
     float* const pb1 = reinterpret_cast<float*>(lds);
     float* const pb2 = pb1 + FFN_MAX_F;
     float* const pg = pb2 + D;
@@ -439,6 +432,7 @@ __global__ __launch_bounds__(512) void ffn_fused_rt2_kernel(const FfnArgs p, con
     static_assert(!PRE || (FR % NT == 0 && KS % (FR / NT) == 0), "whole k-steps per Wo chunk");
     constexpr int PAR = (FFN_MAX_F + (PRE ? 6 : 3) * D) * 4;
     __shared__ __attribute__((aligned(16))) char lds[PAR + NS * G::CHUNK];
+    static_assert(ffn_entry_is<sizeof(lds), ROWS, NS>(ffn_entry<FFN_K_RT2, D, RT, WAVES, 0, PRE, RV>()), "ffn_plan.h");
     float* const pb1 = reinterpret_cast<float*>(lds);
     float* const pb2 = pb1 + FFN_MAX_F;
     float* const pg = pb2 + D;
@@ -812,6 +806,7 @@ __global__ __launch_bounds__(WAVES * 64) void bneck_pair_kernel(const PairArgs p
     constexpr int PAR = (F4 + D) * 4;
     constexpr unsigned OOB = 0x80000000u;
     __shared__ __attribute__((aligned(16))) char lds[PAR + NS * SLOT];
+    static_assert(ffn_entry_is<sizeof(lds), ROWS, NS>(ffn_entry<FFN_K_PAIR, D, RT, WAVES, D>()), "ffn_plan.h");
     float* const pb3 = reinterpret_cast<float*>(lds);
     float* const pb1 = pb3 + F4;
     char* const ring = lds + PAR;
@@ -994,6 +989,9 @@ __global__ __launch_bounds__(WAVES * 64, 1024 / (WAVES * 64)) void bneck64_kerne
     constexpr unsigned OOB = 0x80000000u;
     __shared__ __attribute__((aligned(16))) char wl[NCH * FR * 1024];
     __shared__ float pb3[F], pb1[DB];
+    static_assert(ffn_entry_is<sizeof(wl) + sizeof(pb3) + sizeof(pb1), 16, 0>(ffn_entry<FFN_K_B64, D, 1, WAVES, DB>()) &&
+                      ffn_entry<FFN_K_B64, D, 1, WAVES, DB>().wg_per_cu == 1024 / (WAVES * 64),
+                  "ffn_plan.h (the launch bounds' workgroups per CU too)");
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, c16 = lane & 15;
@@ -1129,6 +1127,8 @@ __global__ __launch_bounds__(1024) void bneck64_ds_kernel(const PairDsArgs p, co
     constexpr unsigned OOB = 0x80000000u;
     __shared__ __attribute__((aligned(16))) char wl[NCH * FR * 1024];
     __shared__ float pb3[F], pb1[DB];
+    static_assert(ffn_entry_is<sizeof(wl) + sizeof(pb3) + sizeof(pb1), 16 * RT, 0>(ffn_entry<FFN_K_B64_DS, 64, RT, WAVES, DB>()),
+                  "ffn_plan.h");
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, c16 = lane & 15;
@@ -1271,223 +1271,114 @@ __global__ __launch_bounds__(1024) void bneck64_ds_kernel(const PairDsArgs p, co
     }
 }
 
-template <typename T>
-void launch_pair_ds(const PairDsArgs& a, hipStream_t s) {
-    // one 16-wave workgroup per CU (96 KiB of weights), as bneck64_kernel<T, 128, 16>
-    const int cus = cu_count();
-    if (ffn_debug & 512) {   // A/B knob: two 16-row tiles per wave
-        const int nt = (a.M + 31) / 32, nb = (nt + 15) / 16;
-        hipLaunchKernelGGL((bneck64_ds_kernel<T, 2>), dim3(nb < cus ? nb : cus), dim3(1024), 0, s, a, nt);
-    } else {
-        const int nt = (a.M + 15) / 16, nb = (nt + 15) / 16;
-        hipLaunchKernelGGL((bneck64_ds_kernel<T, 1>), dim3(nb < cus ? nb : cus), dim3(1024), 0, s, a, nt);
-    }
-}
 
-template <typename T, int D, int RT, int WAVES, int WG_PER_CU>
-void launch_pair_cfg(const PairArgs& a, hipStream_t s) {
-    constexpr int ROWS = WAVES * 16 * RT;
-    const int nt = (a.M + ROWS - 1) / ROWS;
-    const int cap = 256 * WG_PER_CU;
-    hipLaunchKernelGGL((bneck_pair_kernel<T, D, RT, WAVES>), dim3(nt < cap ? nt : cap), dim3(WAVES * 64), 0, s, a, nt);
-}
+// The four packed streams (kinet_ffn_pack, kinet_ffn_pack_attn, kinet_bottleneck_pack,
+// kinet_bottleneck_pack_ds) through the one layout function, ffn_pack_src (ffn_plan.h).  F32: the
+// sources are f32 and every row is scaled by its FrozenBN scale (in f32) before the one rounding to T;
+// otherwise they are T already and are copied.
+struct PackSrc {
+    const void* W[kFfnPackMats];
+    const float* scale[kFfnPackMats];
+};
 
-template <typename T>
-int launch_pair(const PairArgs& a, int D, int DB, hipStream_t s) {
-    if (D == 64 && DB == 128) {
-        const int nt = (a.M + 15) / 16, nb = (nt + 15) / 16;
-        hipLaunchKernelGGL((bneck64_kernel<T, 128, 16>), dim3(nb < 256 ? nb : 256), dim3(1024), 0, s, a, nt);
-        return KINET_OK;
-    }
-    if (DB != D) return KINET_ERR_ARG;
-    switch (D) {
-        case 64:
-            if (ffn_debug & 16) {   // A/B knob: the LDS-ring pair kernel at D = 64 too
-                launch_pair_cfg<T, 64, 2, 8, 2>(a, s);
-            } else {
-                const int nt = (a.M + 15) / 16, nb = (nt + 7) / 8;
-                hipLaunchKernelGGL((bneck64_kernel<T, 64, 8>), dim3(nb < 512 ? nb : 512), dim3(512), 0, s, a, nt);
-            }
-            break;
-        case 128:
-        case 256: {
-            // one or two 16-row tiles per wave (128- or 256-row workgroup tiles; the same sums per
-            // element either way): the 2-tile tile reads each weight fragment once for two MFMAs,
-            // but with one batch in flight (kinet_set_solo_launch), when its tiles fill their rounds
-            // of one workgroup per CU 1.5x worse than the 1-tile grid, the 1-tile grid wins --
-            // config 5's stage-3 pairs (M = 32,640: 128 vs 255 tiles on 256 CUs) 84.7 -> 62.9 us
-            // alone (profiles/r06aa_config5_shapes.txt); on 3 streams the other batches fill the
-            // idle CUs (neutral, profiles/r06ab_solo_launch_ab.txt).
-            // ffn_debug 128 / 256 force the 1- / 2-tile grid (tests, A/B)
-            const int cus = cu_count();
-            const long t2 = (a.M + 255) / 256, t1 = (a.M + 127) / 128;
-            const double e2 = (double)t2 / (double)(((t2 + cus - 1) / cus) * cus);
-            const double e1 = (double)t1 / (double)(((t1 + cus - 1) / cus) * cus);
-            const bool one = (ffn_debug & 128) || (!(ffn_debug & 256) && solo_launch() && e1 > 1.5 * e2);
-            if (D == 128) {
-                if (one) launch_pair_cfg<T, 128, 1, 8, 1>(a, s);
-                else launch_pair_cfg<T, 128, 2, 8, 1>(a, s);
-            } else {
-                if (one) launch_pair_cfg<T, 256, 1, 8, 1>(a, s);
-                else launch_pair_cfg<T, 256, 2, 8, 1>(a, s);
-            }
-            break;
-        }
-        default: return KINET_ERR_ARG;
-    }
-    return KINET_OK;
-}
-
-// packed[c][f][lane][j] (see include/kinet_ffn.h): f < 2KS -> W1 fragment (h-tile f / KS,
-// k-step f % KS); else W2 fragment of output tile f - 2KS with the hidden index permuted to
-// the phase-A accumulator order.
-// kinet_bottleneck_pack: ffn_pack_kernel's fragment order from f32 weights, W3 row h scaled by
-// s3[h] and W1 row n by s1[n] (FrozenBN folded) before the one rounding to T
-template <typename T>
-__global__ void bneck_pack_kernel(const float* __restrict__ W3, const float* __restrict__ W1,
-                                  const float* __restrict__ s3, const float* __restrict__ s1, T* __restrict__ out,
-                                  int D, int F, int DB) {
-    const int KS = D / 32, NT = DB / 16, FR = 2 * KS + NT;
-    const long total = (long)(D + DB) * F;
+template <typename T, bool F32>
+__global__ void ffn_pack_kernel(const PackSrc src, T* __restrict__ out, int kind, int D, int F, int DB) {
+    const long total = ffn_pack_total(kind, D, F, DB);
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const long per_chunk = (long)FR * 512;
-        const int c = (int)(idx / per_chunk);
-        const int rem = (int)(idx - (long)c * per_chunk);
-        const int f = rem >> 9, e = rem & 511;
-        const int lane = e >> 3, j = e & 7, g = lane >> 4, c16 = lane & 15;
-        float v;
-        if (f < 2 * KS) {
-            const int ht = f / KS, ks = f - ht * KS;
-            const int h = 32 * c + 16 * ht + c16;
-            v = W3[(long)h * D + 32 * ks + 8 * g + j] * s3[h];
+        const FfnPackSrc e = ffn_pack_src(kind, D, F, DB, idx);
+        const long at = (long)e.row * e.ld + e.col;
+        if constexpr (F32) {
+            float v = static_cast<const float*>(src.W[e.mat])[at] * src.scale[e.mat][e.row];
+            // keeps the parent's instruction pair, v_mul_f32 then v_cvt_f16_f32 / v_cvt_pk_bf16_f32 (the
+            // documented f32 scale + one rounding to T): without it hipcc emits v_fma_mixlo_f16 for the f16
+            // kernel here, and a packed f16 buffer no longer matched the f32-scaled, once-rounded gather
+            // (tests/test_ffn_pack_gpu.py); profiles/ffn_plan_equiv.log section 2
+            asm volatile("" : "+v"(v));
+            out[idx] = Cvt<T>::from(v);
         } else {
-            const int nt = f - 2 * KS;
-            const int h = 32 * c + (j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4));
-            const int n = ffn_sigma(nt, c16);
-            v = W1[(long)n * F + h] * s1[n];
+            out[idx] = static_cast<const T*>(src.W[e.mat])[at];
         }
-        out[idx] = Cvt<T>::from(v);
     }
 }
 
-// kinet_bottleneck_pack_ds (D = DB = 64): per chunk the 2 KS W3 fragments, then the 2 KS W_ds
-// fragments in the same (h-tile, k-step) order, then the NT W1 fragments; every row scaled by
-// its FrozenBN scale before the one rounding to T
-template <typename T>
-__global__ void bneck_pack_ds_kernel(const float* __restrict__ W3, const float* __restrict__ Wd,
-                                     const float* __restrict__ W1, const float* __restrict__ s3,
-                                     const float* __restrict__ sd, const float* __restrict__ s1, T* __restrict__ out,
-                                     int F) {
-    constexpr int D = 64, KS = D / 32, NT = 64 / 16, FR = 4 * KS + NT;
-    const long total = (long)(F / 32) * FR * 512;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const long per_chunk = (long)FR * 512;
-        const int c = (int)(idx / per_chunk);
-        const int rem = (int)(idx - (long)c * per_chunk);
-        const int f = rem >> 9, e = rem & 511;
-        const int lane = e >> 3, j = e & 7, g = lane >> 4, c16 = lane & 15;
-        float v;
-        if (f < 4 * KS) {
-            const bool ds = f >= 2 * KS;
-            const int ff = ds ? f - 2 * KS : f;
-            const int ht = ff / KS, ks = ff - ht * KS;
-            const int h = 32 * c + 16 * ht + c16;
-            v = (ds ? Wd : W3)[(long)h * D + 32 * ks + 8 * g + j] * (ds ? sd : s3)[h];
-        } else {
-            const int nt = f - 4 * KS;
-            const int h = 32 * c + (j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4));
-            const int n = ffn_sigma(nt, c16);
-            v = W1[(long)n * F + h] * s1[n];
-        }
-        out[idx] = Cvt<T>::from(v);
-    }
-}
-
-template <typename T>
-__global__ void ffn_pack_kernel(const T* __restrict__ W1, const T* __restrict__ W2, T* __restrict__ out, int D,
-                                int F) {
-    const int KS = D / 32, NT = D / 16, FR = 2 * KS + NT;
-    const long total = 2L * D * F;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const long per_chunk = (long)FR * 512;
-        const int c = (int)(idx / per_chunk);
-        const int rem = (int)(idx - (long)c * per_chunk);
-        const int f = rem >> 9, e = rem & 511;
-        const int lane = e >> 3, j = e & 7, g = lane >> 4, c16 = lane & 15;
-        T v;
-        if (f < 2 * KS) {
-            const int ht = f / KS, ks = f - ht * KS;
-            v = W1[(long)(32 * c + 16 * ht + c16) * D + 32 * ks + 8 * g + j];
-        } else {
-            const int nt = f - 2 * KS;
-            const int h = 32 * c + (j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4));
-            v = W2[(long)ffn_sigma(nt, c16) * F + h];
-        }
-        out[idx] = v;
-    }
-}
-
-// kinet_ffn_pack_attn's head: Wo (D, D) as D/32 * D/16 1-KiB MFMA A-operand fragments, k-step
-// major: fragment (ks, nt), lane (g, c16), element j = Wo[ffn_sigma(nt, c16)][32 ks + 8 g + j]
-template <typename T>
-__global__ void attn_pack_kernel(const T* __restrict__ Wo, T* __restrict__ out, int D) {
-    const int NT = D / 16;
-    const long total = (long)D * D;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const int f = (int)(idx >> 9), e = (int)(idx & 511);
-        const int ks = f / NT, nt = f - ks * NT;
-        const int lane = e >> 3, j = e & 7, g = lane >> 4, c16 = lane & 15;
-        out[idx] = Wo[(long)ffn_sigma(nt, c16) * D + 32 * ks + 8 * g + j];
-    }
-}
-
-template <typename T, int D>
-int launch_ffn(const FfnArgs& a, hipStream_t s) {
-    // persistent: one workgroup per CU walks row tiles.  Many rows: 4 waves x 32 rows (128
-    // rows share each weight byte; the 2 x D/16 output tiles + 2 x D/32 x-fragments (+ the
-    // next tile's prefetch) need > 256 VGPRs, so one wave per SIMD);  few rows (decoder
-    // queries): 4 waves x 16 rows, so the rows spread over more CUs
-    if (a.M >= 16384) {
-        const int nt = (a.M + 127) / 128;
-        if constexpr (FfnGeo<D>::FR % 8 == 0) {
-            if (a.dbg & 2) {   // A/B knob: 4 waves x 32 rows (one wave per SIMD)
-                const int n2 = (a.M + 127) / 128;
-                hipLaunchKernelGGL((ffn_fused_kernel<T, D, 2, 4>), dim3(n2 < 256 ? n2 : 256), dim3(256), 0, s, a, n2);
-                return KINET_OK;
-            }
-            if (a.dbg & 8) {   // A/B knob: 8 waves x 16 rows (the round-3 default)
-                hipLaunchKernelGGL((ffn_fused_kernel<T, D, 1, 8>), dim3(nt < 256 ? nt : 256), dim3(512), 0, s, a, nt);
-                return KINET_OK;
-            }
-            // 8 waves x 32 rows: each weight fragment feeds two MFMAs and two waves per SIMD hide
-            // each other's latency (config-2 encoder FFN at batch 16: 419 vs 486 us alone, bench
-            // 1267 vs 1219 frames/s, profiles/r04c_ffn_probe.log, r04c_ab_*.json)
-            const int n4 = (a.M + 255) / 256;
-            hipLaunchKernelGGL((ffn_fused_rt2_kernel<T, D>), dim3(n4 < 256 ? n4 : 256), dim3(512), 0, s, a, n4);
-        } else {
-            hipLaunchKernelGGL((ffn_fused_kernel<T, D, 2, 4>), dim3(nt < 256 ? nt : 256), dim3(256), 0, s, a, nt);
-        }
-    } else {
-        const int nt = (a.M + 63) / 64;
-        hipLaunchKernelGGL((ffn_fused_kernel<T, D, 1, 4>), dim3(nt < 256 ? nt : 256), dim3(256), 0, s, a, nt);
-    }
-    return KINET_OK;
-}
-
-template <typename T>
-void launch_attn_out_ffn(const FfnArgs& a, hipStream_t s) {
-    // persistent like launch_ffn's 8-wave x 32-row case, the only tile with the pre-phase
-    const int nt = (a.M + 255) / 256;
-    const dim3 grid(nt < 256 ? nt : 256), block(512);
-    // residual loads: all after the last Wo chunk (715 us per batch-28 encoder layer) or, A/B knob,
-    // staged under the Wo chunks (732 us: no faster, profiles/attn_out_ffn_probe.txt)
-    if (a.dbg & 64)
-        hipLaunchKernelGGL((ffn_fused_rt2_kernel<T, 256, true, 1>), grid, block, 0, s, a, nt);
+template <bool F32>
+int launch_pack(const PackSrc& src, void* packed, int kind, int D, int F, int DB, int dtype, kinet_stream_t stream) {
+    const long total = ffn_pack_total(kind, D, F, DB);
+    const dim3 grid((int)((total + 255) / 256 < kMaxGridStride ? (total + 255) / 256 : kMaxGridStride)), block(256);
+    if (dtype == KINET_BF16)
+        hipLaunchKernelGGL((ffn_pack_kernel<bf16_t, F32>), grid, block, 0, (hipStream_t)stream, src, (bf16_t*)packed, kind, D, F, DB);
     else
-        hipLaunchKernelGGL((ffn_fused_rt2_kernel<T, 256, true, 0>), grid, block, 0, s, a, nt);
+        hipLaunchKernelGGL((ffn_pack_kernel<f16_t, F32>), grid, block, 0, (hipStream_t)stream, src, (f16_t*)packed, kind, D, F, DB);
+    KINET_LAUNCH_CHECK();
+    return KINET_OK;
 }
 
-bool al16(const void* q) { return (((uintptr_t)q) & 15u) == 0; }
+// the argument struct each kernel family takes
+template <typename Args>
+constexpr bool takes(int family) {
+    return std::is_same<Args, FfnArgs>::value    ? family == FFN_K_FUSED || family == FFN_K_RT2
+           : std::is_same<Args, PairArgs>::value ? family == FFN_K_PAIR || family == FFN_K_B64
+                                                 : family == FFN_K_B64_DS;
+}
+
+// Launch entry I of kFfnKernels (ffn_plan.h) for one element type if `kernel` names it.  These are
+// the only launches of the five kernel families, so the table is the list of their instantiations.
+template <typename T, int I, typename Args>
+void launch_entry(int kernel, dim3 grid, hipStream_t s, const Args& a, int tiles) {
+    constexpr FfnKernel k = kFfnKernels[I];
+    if constexpr (takes<Args>(k.family)) {
+        if (kernel != I) return;
+        const dim3 block(k.block());
+        if constexpr (k.family == FFN_K_FUSED) {
+            hipLaunchKernelGGL((ffn_fused_kernel<T, k.d, k.rt, k.waves>), grid, block, 0, s, a, tiles);
+        } else if constexpr (k.family == FFN_K_RT2) {
+            static_assert(k.rt == 2 && k.waves == 8, "ffn_fused_rt2_kernel is 8 waves x 32 rows");
+            hipLaunchKernelGGL((ffn_fused_rt2_kernel<T, k.d, k.pre, k.rv>), grid, block, 0, s, a, tiles);
+        } else if constexpr (k.family == FFN_K_PAIR) {
+            hipLaunchKernelGGL((bneck_pair_kernel<T, k.d, k.rt, k.waves>), grid, block, 0, s, a, tiles);
+        } else if constexpr (k.family == FFN_K_B64) {
+            hipLaunchKernelGGL((bneck64_kernel<T, k.db, k.waves>), grid, block, 0, s, a, tiles);
+        } else {
+            static_assert(k.waves == 16, "bneck64_ds_kernel is 16 waves");
+            hipLaunchKernelGGL((bneck64_ds_kernel<T, k.rt>), grid, block, 0, s, a, tiles);
+        }
+    }
+}
+template <typename T, typename Args, int... I>
+void launch_kernel(const FfnPlan& pl, hipStream_t s, const Args& a, std::integer_sequence<int, I...>) {
+    (launch_entry<T, I>(pl.kernel, dim3(pl.grid), s, a, pl.tiles), ...);
+}
+
+FfnProblem ffn_problem(int kind, int M, int D, int F, int DB, int cus) {
+    return FfnProblem{kind, M, D, F, DB, ffn_debug, solo_launch(), cus};
+}
+
+int refused(const FfnPlan& pl) {
+    set_error(pl.why, pl.why_arg[0], pl.why_arg[1]);
+    return KINET_ERR_ARG;
+}
+
+// Plan the call (ffn_plan.h: every choice, tile count and grid lives there) and run the planned
+// launch: kernel, block, grid and the kinet_ffn_last_kernel record all come from its one table entry.
+template <typename Args>
+int launch_planned(int kind, int M, int D, int F, int DB, int dtype, const Args& a, kinet_stream_t stream) {
+    FfnPlan pl;
+    if (!ffn_plan(ffn_problem(kind, M, D, F, DB, cu_count()), pl)) return refused(pl);
+    ffn_last = pl.kernel;
+    constexpr std::make_integer_sequence<int, kNumFfnKernels> all{};
+    if (dtype == KINET_BF16) launch_kernel<bf16_t>(pl, (hipStream_t)stream, a, all);
+    else launch_kernel<f16_t>(pl, (hipStream_t)stream, a, all);
+    KINET_LAUNCH_CHECK();
+    return KINET_OK;
+}
+
+// checks the entry points share
+bool dt16(int dtype) { return dtype == KINET_BF16 || dtype == KINET_F16; }
+template <typename... Q>
+bool al16(const Q*... q) { return (((uintptr_t)q | ...) & 15u) == 0; }
+// bytes of M rows of stride ld elements, the last one D wide (buffer descriptors: below 2 GiB)
+long long extent(int M, int ld, int D) { return ((long long)(M - 1) * ld + D) * 2; }
+constexpr long long k2GiB = 1LL << 31;
 
 }  // namespace
 }  // namespace kinet
@@ -1500,69 +1391,80 @@ extern "C" int kinet_ffn_set_debug(int flags) {
     return old;
 }
 
+extern "C" int kinet_ffn_last_kernel(void) { return ffn_last; }
+
+extern "C" const char* kinet_ffn_kernel_name(int kernel) {
+    return kernel >= 0 && kernel < kNumFfnKernels ? kFfnKernels[kernel].name : nullptr;
+}
+
+extern "C" int kinet_ffn_launch_plan(const int* problem, int cus, int* plan_out) {
+    KINET_CHECK_ARG(problem != nullptr && plan_out != nullptr && cus > 0, "ffn launch plan: invalid arguments");
+    const int* f = problem;
+    KINET_CHECK_ARG(f[KINET_FFNP_KIND] >= FFN_FFN && f[KINET_FFNP_KIND] <= FFN_PAIR_DS && f[KINET_FFNP_M] >= 0,
+                    "ffn launch plan: invalid problem");
+    FfnPlan pl;
+    if (!ffn_plan(ffn_problem(f[KINET_FFNP_KIND], f[KINET_FFNP_M], f[KINET_FFNP_D], f[KINET_FFNP_F], f[KINET_FFNP_DB], cus), pl))
+        return refused(pl);
+    const FfnKernel& k = kFfnKernels[pl.kernel];
+    const int rec[KINET_FFNPL_FIELDS] = {pl.kernel, pl.tiles, pl.grid, k.block(), k.waves, k.tile_rows,
+                                         k.wg_tiles, k.wg_per_cu, ffn_kernel_lds(k)};
+    for (int i = 0; i < KINET_FFNPL_FIELDS; ++i) plan_out[i] = rec[i];
+    return KINET_OK;
+}
+
+extern "C" int kinet_ffn_pack_map(int kind, int D, int F, int DB, int32_t* out) {
+    KINET_CHECK_ARG(kind >= FFN_PACK_FFN && kind <= FFN_PACK_ATTN && out != nullptr, "ffn_pack_map: invalid arguments");
+    KINET_CHECK_ARG(D > 0 && D % 32 == 0 && F > 0 && F % 32 == 0 && DB > 0 && DB % 32 == 0,
+                    "ffn_pack_map: need D, F, DB multiples of 32 (D=%d F=%d DB=%d)", D, F, DB);
+    KINET_CHECK_ARG(DB == D || kind == FFN_PACK_PAIR, "ffn_pack_map: DB must be D but for the bottleneck pair (D=%d DB=%d)", D, DB);
+    const long long total = ffn_pack_total(kind, D, F, DB);
+    for (long long idx = 0; idx < total; ++idx) {
+        const FfnPackSrc e = ffn_pack_src(kind, D, F, DB, idx);
+        out[3 * idx] = e.mat;
+        out[3 * idx + 1] = e.row;
+        out[3 * idx + 2] = e.col;
+    }
+    return KINET_OK;
+}
+
 extern "C" int kinet_ffn_pack(const void* W1, const void* W2, void* packed, int D, int F, int dtype,
                               kinet_stream_t stream) {
     KINET_CHECK_ARG(D > 0 && D % 32 == 0 && F > 0 && F % 32 == 0, "ffn_pack: need D %% 32 == 0 and F %% 32 == 0 (D=%d F=%d)", D, F);
-    KINET_CHECK_ARG(dtype == KINET_BF16 || dtype == KINET_F16, "ffn_pack: dtype must be bf16 or f16");
-    const long total = 2L * D * F;
-    const int grid = (int)((total + 255) / 256 < kMaxGridStride ? (total + 255) / 256 : kMaxGridStride);
-    if (dtype == KINET_BF16)
-        hipLaunchKernelGGL(ffn_pack_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)W1,
-                           (const bf16_t*)W2, (bf16_t*)packed, D, F);
-    else
-        hipLaunchKernelGGL(ffn_pack_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f16_t*)W1,
-                           (const f16_t*)W2, (f16_t*)packed, D, F);
-    KINET_LAUNCH_CHECK();
-    return KINET_OK;
+    KINET_CHECK_ARG(dt16(dtype), "ffn_pack: dtype must be bf16 or f16");
+    return launch_pack<false>(PackSrc{{W1, W2}, {}}, packed, FFN_PACK_FFN, D, F, D, dtype, stream);
 }
 
 extern "C" int kinet_ffn_fused(const void* X, int ldx, const void* packed, const float* b1, const float* b2,
                                const float* ln_gamma, const float* ln_beta, float ln_eps, void* Y, int ldy, int M,
                                int D, int F, int dtype, kinet_stream_t stream) {
-    KINET_CHECK_ARG(D == 256 || D == 288, "ffn_fused: D must be 256 or 288 (got %d)", D);
+    KINET_CHECK_ARG(D == 256 || D == 288, kFfnWhyD, D);
     KINET_CHECK_ARG(F > 0 && F % 32 == 0 && F <= FFN_MAX_F, "ffn_fused: F must be a multiple of 32 in [32, %d] (got %d)", FFN_MAX_F, F);
     KINET_CHECK_ARG(M >= 0 && ldx >= D && ldy >= D && ldx % 8 == 0 && ldy % 8 == 0, "ffn_fused: bad M / ldx / ldy");
-    KINET_CHECK_ARG(dtype == KINET_BF16 || dtype == KINET_F16, "ffn_fused: dtype must be bf16 or f16");
+    KINET_CHECK_ARG(dt16(dtype), "ffn_fused: dtype must be bf16 or f16");
     KINET_CHECK_ARG(b1 != nullptr && b2 != nullptr, "ffn_fused: b1 and b2 are required");
     KINET_CHECK_ARG((ln_gamma == nullptr) == (ln_beta == nullptr), "ffn_fused: LayerNorm needs both gamma and beta");
-    KINET_CHECK_ARG(al16(X) && al16(Y) && al16(packed) && al16(b1) && al16(b2) &&
-                    (ln_gamma == nullptr || (al16(ln_gamma) && al16(ln_beta))),
+    KINET_CHECK_ARG(al16(X, Y, packed, b1, b2, ln_gamma, ln_beta),
                     "ffn_fused: X, Y, packed weights, biases and LayerNorm params must be 16-byte aligned");
     if (M == 0) return KINET_OK;
-    const long long xb = ((long long)(M - 1) * ldx + D) * 2;
-    KINET_CHECK_ARG(xb < (1LL << 31), "ffn_fused: X larger than 2 GiB (split the call)");
+    const long long xb = extent(M, ldx, D);
+    KINET_CHECK_ARG(xb < k2GiB, "ffn_fused: X larger than 2 GiB (split the call)");
     FfnArgs a{};
     a.X = X; a.W = packed; a.b1 = b1; a.b2 = b2; a.ln_g = ln_gamma; a.ln_b = ln_beta; a.Y = Y; a.eps = ln_eps;
     a.ldx = ldx; a.ldy = ldy; a.M = M; a.F = F;
     a.x_bytes = (int)xb;
-    a.w_bytes = (int)(2LL * D * F * 2);
-    const long long yb = ((long long)(M - 1) * ldy + D) * 2;
-    KINET_CHECK_ARG(yb < (1LL << 31), "ffn_fused: Y larger than 2 GiB (split the call)");
+    a.w_bytes = (int)(ffn_pack_total(FFN_PACK_FFN, D, F, D) * 2);
+    const long long yb = extent(M, ldy, D);
+    KINET_CHECK_ARG(yb < k2GiB, "ffn_fused: Y larger than 2 GiB (split the call)");
     a.y_bytes = (int)yb;
     a.dbg = ffn_debug;
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if (dtype == KINET_BF16) rc = D == 256 ? launch_ffn<bf16_t, 256>(a, s) : launch_ffn<bf16_t, 288>(a, s);
-    else rc = D == 256 ? launch_ffn<f16_t, 256>(a, s) : launch_ffn<f16_t, 288>(a, s);
-    if (rc) return rc;
-    KINET_LAUNCH_CHECK();
-    return KINET_OK;
+    return launch_planned(FFN_FFN, M, D, F, D, dtype, a, stream);
 }
 
 extern "C" int kinet_ffn_pack_attn(const void* Wo, const void* W1, const void* W2, void* packed, int D, int F,
                                    int dtype, kinet_stream_t stream) {
     KINET_CHECK_ARG(D > 0 && D % 32 == 0 && F > 0 && F % 32 == 0, "ffn_pack_attn: need D %% 32 == 0 and F %% 32 == 0 (D=%d F=%d)", D, F);
-    KINET_CHECK_ARG(dtype == KINET_BF16 || dtype == KINET_F16, "ffn_pack_attn: dtype must be bf16 or f16");
-    const long total = (long)D * D;
-    const int grid = (int)((total + 255) / 256 < kMaxGridStride ? (total + 255) / 256 : kMaxGridStride);
-    if (dtype == KINET_BF16)
-        hipLaunchKernelGGL(attn_pack_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)Wo,
-                           (bf16_t*)packed, D);
-    else
-        hipLaunchKernelGGL(attn_pack_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f16_t*)Wo,
-                           (f16_t*)packed, D);
-    KINET_LAUNCH_CHECK();
-    return kinet_ffn_pack(W1, W2, (char*)packed + total * 2, D, F, dtype, stream);
+    KINET_CHECK_ARG(dt16(dtype), "ffn_pack_attn: dtype must be bf16 or f16");
+    return launch_pack<false>(PackSrc{{Wo, W1, W2}, {}}, packed, FFN_PACK_ATTN, D, F, D, dtype, stream);
 }
 
 extern "C" int kinet_attn_out_ffn_fused(const void* A, int lda, const void* R, int ldr, const void* packed,
@@ -1570,23 +1472,20 @@ extern "C" int kinet_attn_out_ffn_fused(const void* A, int lda, const void* R, i
                                         const float* b1, const float* b2, const float* g2, const float* be2,
                                         float eps2, void* Y, int ldy, int M, int D, int F, int dtype,
                                         kinet_stream_t stream) {
-    KINET_CHECK_ARG(D != 288, "attn_out_ffn_fused: D = 288 is not supported (Wo does not fill whole ring chunks); D must be 256");
-    KINET_CHECK_ARG(D == 256, "attn_out_ffn_fused: D must be 256 (got %d)", D);
+    KINET_CHECK_ARG(D != 288, kAttnOutWhyD288);
+    KINET_CHECK_ARG(D == 256, kAttnOutWhyD, D);
     KINET_CHECK_ARG(F > 0 && F % 32 == 0 && F <= FFN_MAX_F, "attn_out_ffn_fused: F must be a multiple of 32 in [32, %d] (got %d)", FFN_MAX_F, F);
     KINET_CHECK_ARG(M >= 0 && lda >= D && ldr >= D && ldy >= D && lda % 8 == 0 && ldr % 8 == 0 && ldy % 8 == 0,
                     "attn_out_ffn_fused: bad M / lda / ldr / ldy");
-    KINET_CHECK_ARG(dtype == KINET_BF16 || dtype == KINET_F16, "attn_out_ffn_fused: dtype must be bf16 or f16");
+    KINET_CHECK_ARG(dt16(dtype), "attn_out_ffn_fused: dtype must be bf16 or f16");
     KINET_CHECK_ARG(bo != nullptr && g1 != nullptr && be1 != nullptr, "attn_out_ffn_fused: bo and the first LayerNorm's gamma and beta are required");
     KINET_CHECK_ARG(b1 != nullptr && b2 != nullptr, "attn_out_ffn_fused: b1 and b2 are required");
     KINET_CHECK_ARG((g2 == nullptr) == (be2 == nullptr), "attn_out_ffn_fused: the second LayerNorm needs both gamma and beta");
-    KINET_CHECK_ARG(al16(A) && al16(R) && al16(Y) && al16(packed) && al16(bo) && al16(g1) && al16(be1) && al16(b1) &&
-                    al16(b2) && (g2 == nullptr || (al16(g2) && al16(be2))),
+    KINET_CHECK_ARG(al16(A, R, Y, packed, bo, g1, be1, b1, b2, g2, be2),
                     "attn_out_ffn_fused: A, R, Y, packed weights, biases and LayerNorm params must be 16-byte aligned");
     if (M == 0) return KINET_OK;
-    const long long ab = ((long long)(M - 1) * lda + D) * 2, rb = ((long long)(M - 1) * ldr + D) * 2;
-    const long long yb = ((long long)(M - 1) * ldy + D) * 2;
-    KINET_CHECK_ARG(ab < (1LL << 31) && rb < (1LL << 31) && yb < (1LL << 31),
-                    "attn_out_ffn_fused: A, R or Y larger than 2 GiB (split the call)");
+    const long long ab = extent(M, lda, D), rb = extent(M, ldr, D), yb = extent(M, ldy, D);
+    KINET_CHECK_ARG(ab < k2GiB && rb < k2GiB && yb < k2GiB, "attn_out_ffn_fused: A, R or Y larger than 2 GiB (split the call)");
     auto overlap = [](const void* u, long long ub, const void* v, long long vb) {
         return (const char*)u < (const char*)v + vb && (const char*)v < (const char*)u + ub;
     };
@@ -1594,62 +1493,45 @@ extern "C" int kinet_attn_out_ffn_fused(const void* A, int lda, const void* R, i
     FfnArgs a{};
     a.W = packed; a.b1 = b1; a.b2 = b2; a.ln_g = g2; a.ln_b = be2; a.Y = Y; a.eps = eps2;
     a.ldy = ldy; a.M = M; a.F = F;
-    a.w_bytes = (int)(((long long)D * D + 2LL * D * F) * 2);
+    a.w_bytes = (int)(ffn_pack_total(FFN_PACK_ATTN, D, F, D) * 2);
     a.y_bytes = (int)yb;
     a.dbg = ffn_debug;
     a.A = A; a.R = R; a.bo = bo; a.g1 = g1; a.be1 = be1; a.eps1 = eps1;
     a.lda = lda; a.ldr = ldr; a.a_bytes = (int)ab; a.r_bytes = (int)rb;
-    if (dtype == KINET_BF16) launch_attn_out_ffn<bf16_t>(a, (hipStream_t)stream);
-    else launch_attn_out_ffn<f16_t>(a, (hipStream_t)stream);
-    KINET_LAUNCH_CHECK();
-    return KINET_OK;
+    return launch_planned(FFN_ATTN_OUT, M, D, F, D, dtype, a, stream);
 }
 
 extern "C" int kinet_bottleneck_pack(const float* W3, const float* W1, const float* s3, const float* s1,
                                      void* packed, int D, int F, int DB, int dtype, kinet_stream_t stream) {
     KINET_CHECK_ARG(D > 0 && D % 32 == 0 && F > 0 && F % 32 == 0 && DB > 0 && DB % 32 == 0,
                     "bottleneck_pack: need D, F, DB multiples of 32 (D=%d F=%d DB=%d)", D, F, DB);
-    KINET_CHECK_ARG(dtype == KINET_BF16 || dtype == KINET_F16, "bottleneck_pack: dtype must be bf16 or f16");
+    KINET_CHECK_ARG(dt16(dtype), "bottleneck_pack: dtype must be bf16 or f16");
     KINET_CHECK_ARG(W3 && W1 && s3 && s1 && packed, "bottleneck_pack: null pointer");
-    const long total = (long)(D + DB) * F;
-    const int grid = (int)((total + 255) / 256 < kMaxGridStride ? (total + 255) / 256 : kMaxGridStride);
-    if (dtype == KINET_BF16)
-        hipLaunchKernelGGL(bneck_pack_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, W3, W1, s3, s1,
-                           (bf16_t*)packed, D, F, DB);
-    else
-        hipLaunchKernelGGL(bneck_pack_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, W3, W1, s3, s1,
-                           (f16_t*)packed, D, F, DB);
-    KINET_LAUNCH_CHECK();
-    return KINET_OK;
+    return launch_pack<true>(PackSrc{{W3, W1}, {s3, s1}}, packed, FFN_PACK_PAIR, D, F, DB, dtype, stream);
 }
 
 extern "C" int kinet_bottleneck_pair(const void* X, int ldx, const void* R, const void* packed, const float* b3,
                                      const float* b1, void* Y, void* T, int M, int D, int F, int DB, int dtype,
                                      kinet_stream_t stream) {
-    KINET_CHECK_ARG(D == 64 || D == 128 || D == 256, "bottleneck_pair: D must be 64, 128 or 256 (got %d)", D);
+    KINET_CHECK_ARG(D == 64 || D == 128 || D == 256, kPairWhyD, D);
     KINET_CHECK_ARG(F == 4 * D, "bottleneck_pair: F must be 4 * D (got D=%d F=%d)", D, F);
-    KINET_CHECK_ARG(DB == D || (D == 64 && DB == 128), "bottleneck_pair: DB must be D, or 128 at D = 64 (got D=%d DB=%d)", D, DB);
+    KINET_CHECK_ARG(DB == D || (D == 64 && DB == 128), kPairWhyDB, D, DB);
     KINET_CHECK_ARG(M >= 0 && ldx >= D && ldx % 8 == 0, "bottleneck_pair: bad M / ldx");
-    KINET_CHECK_ARG(dtype == KINET_BF16 || dtype == KINET_F16, "bottleneck_pair: dtype must be bf16 or f16");
+    KINET_CHECK_ARG(dt16(dtype), "bottleneck_pair: dtype must be bf16 or f16");
     KINET_CHECK_ARG(b3 && b1, "bottleneck_pair: folded BN biases of both convs are required");
-    KINET_CHECK_ARG(al16(X) && al16(R) && al16(packed) && al16(Y) && al16(T) && al16(b3) && al16(b1),
-                    "bottleneck_pair: tensors and BN biases must be 16-byte aligned");
+    KINET_CHECK_ARG(al16(X, R, packed, Y, T, b3, b1), "bottleneck_pair: tensors and BN biases must be 16-byte aligned");
     if (M == 0) return KINET_OK;
-    const long long xb = ((long long)(M - 1) * ldx + D) * 2, fb = (long long)M * F * 2;
-    KINET_CHECK_ARG(xb < (1LL << 31) && fb < (1LL << 31), "bottleneck_pair: tensors larger than 2 GiB (split the call)");
+    const long long xb = extent(M, ldx, D), fb = (long long)M * F * 2;
+    KINET_CHECK_ARG(xb < k2GiB && fb < k2GiB, "bottleneck_pair: tensors larger than 2 GiB (split the call)");
     PairArgs a{};
     a.X = X; a.R = R; a.W = packed; a.b3 = b3; a.b1 = b1; a.Y = Y; a.T = T;
     a.ldx = ldx; a.M = M; a.F = F;
     a.x_bytes = (int)xb;
     a.r_bytes = (int)fb;
     a.y_bytes = (int)fb;
-    a.w_bytes = (int)((long long)(D + DB) * F * 2);
+    a.w_bytes = (int)(ffn_pack_total(FFN_PACK_PAIR, D, F, DB) * 2);
     a.t_bytes = (int)((long long)M * DB * 2);
-    hipStream_t s = (hipStream_t)stream;
-    const int rc = dtype == KINET_BF16 ? launch_pair<bf16_t>(a, D, DB, s) : launch_pair<f16_t>(a, D, DB, s);
-    if (rc) return rc;
-    KINET_LAUNCH_CHECK();
-    return KINET_OK;
+    return launch_planned(FFN_PAIR, M, D, F, DB, dtype, a, stream);
 }
 
 extern "C" int kinet_bottleneck_pack_ds(const float* W3, const float* Wds, const float* W1, const float* s3,
@@ -1657,49 +1539,34 @@ extern "C" int kinet_bottleneck_pack_ds(const float* W3, const float* Wds, const
                                         int dtype, kinet_stream_t stream) {
     KINET_CHECK_ARG(D == 64 && F == 256 && DB == 64,
                     "bottleneck_pack_ds: stage 1 only, D = 64, F = 256, DB = 64 (got D=%d F=%d DB=%d)", D, F, DB);
-    KINET_CHECK_ARG(dtype == KINET_BF16 || dtype == KINET_F16, "bottleneck_pack_ds: dtype must be bf16 or f16");
+    KINET_CHECK_ARG(dt16(dtype), "bottleneck_pack_ds: dtype must be bf16 or f16");
     KINET_CHECK_ARG(W3 && Wds && W1 && s3 && sds && s1 && packed, "bottleneck_pack_ds: null pointer");
-    const long total = (long)(D + 64 + DB) * F;
-    const int grid = (int)((total + 255) / 256 < kMaxGridStride ? (total + 255) / 256 : kMaxGridStride);
-    if (dtype == KINET_BF16)
-        hipLaunchKernelGGL(bneck_pack_ds_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, W3, Wds, W1, s3,
-                           sds, s1, (bf16_t*)packed, F);
-    else
-        hipLaunchKernelGGL(bneck_pack_ds_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, W3, Wds, W1, s3,
-                           sds, s1, (f16_t*)packed, F);
-    KINET_LAUNCH_CHECK();
-    return KINET_OK;
+    return launch_pack<true>(PackSrc{{W3, Wds, W1}, {s3, sds, s1}}, packed, FFN_PACK_DS, D, F, DB, dtype, stream);
 }
 
 extern "C" int kinet_bottleneck_pair_ds(const void* X, int ldx, const void* X0, int ldx0, const void* packed,
                                         const float* b3ds, const float* b1, void* Y, void* T, int M, int D, int F,
                                         int DB, int dtype, kinet_stream_t stream) {
-    KINET_CHECK_ARG(D == 64, "bottleneck_pair_ds: D must be 64 (got %d)", D);
+    KINET_CHECK_ARG(D == 64, kPairDsWhyD, D);
     KINET_CHECK_ARG(F == 256, "bottleneck_pair_ds: F must be 256 (got %d)", F);
-    KINET_CHECK_ARG(DB == 64, "bottleneck_pair_ds: DB must be 64 (got %d)", DB);
+    KINET_CHECK_ARG(DB == 64, kPairDsWhyDB, DB);
     KINET_CHECK_ARG(M >= 0 && ldx >= 64 && ldx % 8 == 0 && ldx0 >= 64 && ldx0 % 8 == 0,
                     "bottleneck_pair_ds: bad M / ldx / ldx0 (row strides >= 64, multiples of 8)");
-    KINET_CHECK_ARG(dtype == KINET_BF16 || dtype == KINET_F16, "bottleneck_pair_ds: dtype must be bf16 or f16");
+    KINET_CHECK_ARG(dt16(dtype), "bottleneck_pair_ds: dtype must be bf16 or f16");
     KINET_CHECK_ARG(b3ds && b1, "bottleneck_pair_ds: the combined bias b3 + b_ds and b1 are required");
     KINET_CHECK_ARG(X && X0 && packed && Y && T, "bottleneck_pair_ds: null pointer");
-    KINET_CHECK_ARG(al16(X) && al16(X0) && al16(packed) && al16(Y) && al16(T) && al16(b3ds) && al16(b1),
-                    "bottleneck_pair_ds: tensors and BN biases must be 16-byte aligned");
+    KINET_CHECK_ARG(al16(X, X0, packed, Y, T, b3ds, b1), "bottleneck_pair_ds: tensors and BN biases must be 16-byte aligned");
     if (M == 0) return KINET_OK;
-    const long long xb = ((long long)(M - 1) * ldx + D) * 2, x0b = ((long long)(M - 1) * ldx0 + 64) * 2;
+    const long long xb = extent(M, ldx, D), x0b = extent(M, ldx0, 64);
     const long long fb = (long long)M * F * 2;
-    KINET_CHECK_ARG(xb < (1LL << 31) && x0b < (1LL << 31) && fb < (1LL << 31),
-                    "bottleneck_pair_ds: tensors larger than 2 GiB (split the call)");
+    KINET_CHECK_ARG(xb < k2GiB && x0b < k2GiB && fb < k2GiB, "bottleneck_pair_ds: tensors larger than 2 GiB (split the call)");
     PairDsArgs a{};
     a.X = X; a.X0 = X0; a.W = packed; a.b3 = b3ds; a.b1 = b1; a.Y = Y; a.T = T;
     a.ldx = ldx; a.ldx0 = ldx0; a.M = M;
     a.x_bytes = (int)xb;
     a.x0_bytes = (int)x0b;
     a.y_bytes = (int)fb;
-    a.w_bytes = (int)((long long)(D + 64 + DB) * F * 2);
+    a.w_bytes = (int)(ffn_pack_total(FFN_PACK_DS, D, F, DB) * 2);
     a.t_bytes = (int)((long long)M * DB * 2);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == KINET_BF16) launch_pair_ds<bf16_t>(a, s);
-    else launch_pair_ds<f16_t>(a, s);
-    KINET_LAUNCH_CHECK();
-    return KINET_OK;
+    return launch_planned(FFN_PAIR_DS, M, D, F, DB, dtype, a, stream);
 }

@@ -318,7 +318,53 @@ def ffn_fused(x, linear1, linear2, norm=None, out=None):
     return out.view(*x.shape[:-1], D)
 
 
-ATTN_OUT_FFN_MIN_ROWS = 16384   # launch_ffn (csrc/ffn.hip) takes the 8-wave x 32-row tile from here
+# kinet_ffn_fused takes the 8-wave x 32-row tile from here: kFfnRt2MinRows of csrc/ffn_plan.h
+# (tests/test_ffn_plan_cpu.py holds the two together: the plan flips to that tile exactly at this M)
+ATTN_OUT_FFN_MIN_ROWS = 16384
+
+# field order of kinet_ffn_launch_plan's plan record (include/kinet_ffn.h, kinet_ffn_plan_field)
+FFN_PLAN_FIELDS = ('kernel', 'tiles', 'grid', 'block', 'waves', 'tile_rows', 'wg_tiles', 'wg_per_cu', 'lds')
+FFN_KINDS = ('ffn', 'attn_out_ffn', 'pair', 'pair_ds')
+FFN_PACK_KINDS = ('ffn', 'pair', 'pair_ds', 'attn_out_ffn')
+
+
+def ffn_kernel_name(index):
+    """Name of entry `index` of the table of instantiations of csrc/ffn_plan.h (no element type), None past its end."""
+    name = N.lib().kinet_ffn_kernel_name(int(index))
+    return None if name is None else name.decode()
+
+
+def ffn_launch_plan(kind, M, D, F_=None, DB=None, cus=256):
+    """The launch kinet_ffn_fused ('ffn'), kinet_attn_out_ffn_fused ('attn_out_ffn'), kinet_bottleneck_pair
+    ('pair') or kinet_bottleneck_pair_ds ('pair_ds') makes for M rows on a device of `cus` compute units
+    (kinet_ffn_launch_plan, csrc/ffn_plan.h; no GPU call), under the calling thread's kinet_ffn_set_debug bits
+    and the kinet_set_solo_launch policy: a dict of FFN_PLAN_FIELDS with 'kernel' the instantiation's name, or
+    None when the entry point refuses D or DB (the message through kinet_last_error)."""
+    prob = (ctypes.c_int * 5)(FFN_KINDS.index(kind), int(M), int(D), int(4 * D if F_ is None else F_), int(D if DB is None else DB))
+    out = (ctypes.c_int * len(FFN_PLAN_FIELDS))()
+    if N.lib().kinet_ffn_launch_plan(ctypes.cast(prob, ctypes.c_void_p), int(cus), ctypes.cast(out, ctypes.c_void_p)) != 0:
+        return None
+    plan = dict(zip(FFN_PLAN_FIELDS, out))
+    plan['kernel'] = ffn_kernel_name(plan['kernel'])
+    return plan
+
+
+def ffn_last_kernel():
+    """Name of the kernel the calling thread's last ffn_fused / attn_out_ffn_fused / bottleneck_pair /
+    bottleneck_pair_ds call launched (kinet_ffn_last_kernel), None before the first."""
+    return ffn_kernel_name(N.lib().kinet_ffn_last_kernel())
+
+
+def ffn_pack_map(kind, D, F_, DB=None):
+    """The layout of a packed weight stream (kinet_ffn_pack_map, ffn_pack_src of csrc/ffn_plan.h): an int32
+    (elements, 3) CPU tensor of (source matrix in the pack call's argument order, row, column) per packed
+    element, for kind 'ffn' (ffn_pack), 'attn_out_ffn' (attn_out_ffn_pack), 'pair' (bottleneck_pack) or
+    'pair_ds' (bottleneck_pack_ds)."""
+    DB = D if DB is None else DB
+    n = {'ffn': 2 * D * F_, 'attn_out_ffn': D * D + 2 * D * F_, 'pair': (D + DB) * F_, 'pair_ds': (2 * D + DB) * F_}[kind]
+    out = torch.empty((n, 3), dtype=torch.int32)
+    N.call('kinet_ffn_pack_map', FFN_PACK_KINDS.index(kind), D, F_, DB, out.data_ptr())
+    return out
 
 
 def attn_out_ffn_supported(x, out_proj, linear1, linear2):

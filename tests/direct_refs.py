@@ -1744,3 +1744,155 @@ MSDA_FWD_CASES = [
                                     lds=MSDA_LEVELINFO + 2 * 8 * 16 * MSDA_TAP4D)),
     ('f32', 32, 0, msda_plan_row('none')),
 ]
+
+
+# ----------------------------------------------------------------------------------------------
+# Fused FFN / bottleneck-pair launch plans (csrc/ffn_plan.h through kinet_ffn_launch_plan), worked by
+# hand from the rules.  256 compute units.
+# ----------------------------------------------------------------------------------------------
+FFN_LDS_LIMIT = 160 * 1024
+# the bits of kinet_ffn_set_debug (FfnDebug, csrc/ffn_plan.h)
+FFN_DBG_NO_DMA, FFN_DBG_4W_RT2, FFN_DBG_8W_RT1, FFN_DBG_PAIR64_RING = 1, 2, 8, 16
+FFN_DBG_ATTN_RV1, FFN_DBG_PAIR_RT1, FFN_DBG_PAIR_RT2, FFN_DBG_DS_RT2 = 64, 128, 256, 512
+
+# the table of instantiations: name -> (waves, rows per row tile, row tiles a workgroup works on, workgroups
+# per CU, LDS bytes).  LDS: parameters + ring slots x (32-unit chunk of 2 D/32 + D/16 KiB [+ 64 B per row of
+# residual]), or 8 chunks of resident fragments + parameters
+FFN_KERNELS = {
+    'ffn_fused_kernel<256, 2, 4>': (4, 128, 1, 1, (2048 + 3 * 256) * 4 + 4 * 32 * 1024),
+    'ffn_fused_kernel<256, 1, 8>': (8, 128, 1, 1, (2048 + 3 * 256) * 4 + 4 * 32 * 1024),
+    'ffn_fused_kernel<256, 1, 4>': (4, 64, 1, 1, (2048 + 3 * 256) * 4 + 4 * 32 * 1024),
+    'ffn_fused_kernel<288, 2, 4>': (4, 128, 1, 1, (2048 + 3 * 288) * 4 + 4 * 36 * 1024),
+    'ffn_fused_kernel<288, 1, 4>': (4, 64, 1, 1, (2048 + 3 * 288) * 4 + 4 * 36 * 1024),
+    'ffn_fused_rt2_kernel<256>': (8, 256, 1, 1, (2048 + 3 * 256) * 4 + 3 * 32 * 1024),
+    'ffn_fused_rt2_kernel<256, true>': (8, 256, 1, 1, (2048 + 6 * 256) * 4 + 3 * 32 * 1024),
+    'ffn_fused_rt2_kernel<256, true, 1>': (8, 256, 1, 1, (2048 + 6 * 256) * 4 + 3 * 32 * 1024),
+    'bneck_pair_kernel<64, 2, 8>': (8, 256, 1, 2, 5 * 64 * 4 + 3 * (8 * 1024 + 256 * 64)),
+    'bneck_pair_kernel<128, 1, 8>': (8, 128, 1, 1, 5 * 128 * 4 + 3 * (16 * 1024 + 128 * 64)),
+    'bneck_pair_kernel<128, 2, 8>': (8, 256, 1, 1, 5 * 128 * 4 + 3 * (16 * 1024 + 256 * 64)),
+    'bneck_pair_kernel<256, 1, 8>': (8, 128, 1, 1, 5 * 256 * 4 + 3 * (32 * 1024 + 128 * 64)),
+    'bneck_pair_kernel<256, 2, 8>': (8, 256, 1, 1, 5 * 256 * 4 + 3 * (32 * 1024 + 256 * 64)),
+    'bneck64_kernel<128, 16>': (16, 16, 16, 1, 8 * 12 * 1024 + (256 + 128) * 4),
+    'bneck64_kernel<64, 8>': (8, 16, 8, 2, 8 * 8 * 1024 + (256 + 64) * 4),
+    'bneck64_ds_kernel<1>': (16, 16, 16, 1, 8 * 12 * 1024 + (256 + 64) * 4),
+    'bneck64_ds_kernel<2>': (16, 32, 16, 1, 8 * 12 * 1024 + (256 + 64) * 4),
+}
+_F24, _F18, _F14 = 'ffn_fused_kernel<%d, 2, 4>', 'ffn_fused_kernel<%d, 1, 8>', 'ffn_fused_kernel<%d, 1, 4>'
+_RT2, _PRE0, _PRE1 = 'ffn_fused_rt2_kernel<256>', 'ffn_fused_rt2_kernel<256, true>', 'ffn_fused_rt2_kernel<256, true, 1>'
+_PAIR = 'bneck_pair_kernel<%d, %d, 8>'
+_B64, _B128, _DS1, _DS2 = 'bneck64_kernel<64, 8>', 'bneck64_kernel<128, 16>', 'bneck64_ds_kernel<1>', 'bneck64_ds_kernel<2>'
+FFN_MSG_D = 'ffn_fused: D must be 256 or 288 (got %d)'
+FFN_MSG_ATTN_288 = 'attn_out_ffn_fused: D = 288 is not supported (Wo does not fill whole ring chunks); D must be 256'
+FFN_MSG_ATTN_D = 'attn_out_ffn_fused: D must be 256 (got %d)'
+FFN_MSG_PAIR_D = 'bottleneck_pair: D must be 64, 128 or 256 (got %d)'
+FFN_MSG_PAIR_DB = 'bottleneck_pair: DB must be D, or 128 at D = 64 (got D=%d DB=%d)'
+FFN_MSG_DS_D = 'bottleneck_pair_ds: D must be 64 (got %d)'
+FFN_MSG_DS_DB = 'bottleneck_pair_ds: DB must be 64 (got %d)'
+
+# (kind, M, D, DB, debug bits, solo) -> (kernel, row tiles, grid), or the refusal's message
+FFN_PLAN_CASES = [
+    # kinet_ffn_fused: 4 waves x 16 rows below 16384 rows, whatever the knobs
+    ('ffn', 1, 256, 256, 0, 0, (_F14 % 256, 1, 1)),
+    ('ffn', 16383, 256, 256, 0, 0, (_F14 % 256, 256, 256)),
+    ('ffn', 16383, 256, 256, 2, 0, (_F14 % 256, 256, 256)),
+    ('ffn', 16383, 256, 256, 8, 0, (_F14 % 256, 256, 256)),
+    ('ffn', 16383, 256, 256, 2 | 8, 0, (_F14 % 256, 256, 256)),
+    ('ffn', 16383, 288, 288, 0, 0, (_F14 % 288, 256, 256)),
+    # from 16384: 8 waves x 32 rows; knob 2 the 4-wave x 32-row tile, knob 8 the 8-wave x 16-row tile, 2 before 8
+    ('ffn', 16384, 256, 256, 0, 0, (_RT2, 64, 64)),
+    ('ffn', 16384, 256, 256, 1, 0, (_RT2, 64, 64)),
+    ('ffn', 16384, 256, 256, 2, 0, (_F24 % 256, 128, 128)),
+    ('ffn', 16384, 256, 256, 8, 0, (_F18 % 256, 128, 128)),
+    ('ffn', 16384, 256, 256, 2 | 8, 0, (_F24 % 256, 128, 128)),
+    ('ffn', 355568, 256, 256, 0, 0, (_RT2, 1389, 256)),
+    ('ffn', 355568, 256, 256, 2, 0, (_F24 % 256, 2778, 256)),
+    # D = 288 (36 fragments per chunk: no whole rounds of 8 waves): the 4-wave x 32-row tile under every knob
+    ('ffn', 16384, 288, 288, 0, 0, (_F24 % 288, 128, 128)),
+    ('ffn', 16384, 288, 288, 2, 0, (_F24 % 288, 128, 128)),
+    ('ffn', 16384, 288, 288, 8, 0, (_F24 % 288, 128, 128)),
+    ('ffn', 16384, 128, 128, 0, 0, FFN_MSG_D % 128),
+    # kinet_attn_out_ffn_fused: the 8-wave x 32-row tile at every M; knob 64 = RV 1
+    ('attn_out_ffn', 5, 256, 256, 0, 0, (_PRE0, 1, 1)),
+    ('attn_out_ffn', 16384, 256, 256, 0, 0, (_PRE0, 64, 64)),
+    ('attn_out_ffn', 16384, 256, 256, 64, 0, (_PRE1, 64, 64)),
+    ('attn_out_ffn', 16384, 256, 256, 2 | 8, 0, (_PRE0, 64, 64)),
+    ('attn_out_ffn', 355568, 256, 256, 0, 0, (_PRE0, 1389, 256)),
+    ('attn_out_ffn', 16384, 288, 288, 0, 0, FFN_MSG_ATTN_288),
+    ('attn_out_ffn', 16384, 128, 128, 0, 0, FFN_MSG_ATTN_D % 128),
+    # kinet_bottleneck_pair at D = 128 / 256.  M = 32640: 128 2-tile tiles fill half a round of 256 CUs, 255 1-tile
+    # tiles 0.996 of one: the 1-tile grid with one batch in flight only
+    ('pair', 32640, 128, 128, 0, 0, (_PAIR % (128, 2), 128, 128)),
+    ('pair', 32640, 128, 128, 0, 1, (_PAIR % (128, 1), 255, 255)),
+    ('pair', 32640, 256, 256, 0, 0, (_PAIR % (256, 2), 128, 128)),
+    ('pair', 32640, 256, 256, 0, 1, (_PAIR % (256, 1), 255, 255)),
+    # e1 <= 1.5 e2 with solo on: both fill whole rounds (65536); 460 / 512 vs 919 / 1024 (117600)
+    ('pair', 65536, 128, 128, 0, 1, (_PAIR % (128, 2), 256, 256)),
+    ('pair', 117600, 256, 256, 0, 1, (_PAIR % (256, 2), 460, 256)),
+    # the rule's edge: 1 vs 1 tile (128 rows), 2 vs 1 (129), 3 vs 2 = exactly 1.5 (300), 4 vs 2 (400)
+    ('pair', 128, 256, 256, 0, 1, (_PAIR % (256, 2), 1, 1)),
+    ('pair', 129, 256, 256, 0, 1, (_PAIR % (256, 1), 2, 2)),
+    ('pair', 300, 256, 256, 0, 1, (_PAIR % (256, 2), 2, 2)),
+    ('pair', 400, 256, 256, 0, 1, (_PAIR % (256, 1), 4, 4)),
+    # knob 128 before knob 256 before the solo rule
+    ('pair', 32640, 128, 128, 128, 0, (_PAIR % (128, 1), 255, 255)),
+    ('pair', 32640, 128, 128, 256, 1, (_PAIR % (128, 2), 128, 128)),
+    ('pair', 32640, 128, 128, 128 | 256, 0, (_PAIR % (128, 1), 255, 255)),
+    ('pair', 65536, 256, 256, 128, 1, (_PAIR % (256, 1), 512, 256)),
+    # D = 64: resident weights, a 16-row tile per wave, 2 x 8 waves per CU; knob 16 the ring kernel (2 per CU);
+    # DB = 128 first: 16 waves, one workgroup per CU, no knob
+    ('pair', 1000, 64, 64, 0, 0, (_B64, 63, 8)),
+    ('pair', 1000, 64, 64, 16, 0, (_PAIR % (64, 2), 4, 4)),
+    ('pair', 1068800, 64, 64, 0, 0, (_B64, 66800, 512)),
+    ('pair', 1068800, 64, 64, 16, 0, (_PAIR % (64, 2), 4175, 512)),
+    ('pair', 1000, 64, 128, 0, 0, (_B128, 63, 4)),
+    ('pair', 1000, 64, 128, 16, 0, (_B128, 63, 4)),
+    ('pair', 1068800, 64, 128, 0, 0, (_B128, 66800, 256)),
+    ('pair', 1000, 128, 64, 0, 0, FFN_MSG_PAIR_DB % (128, 64)),
+    ('pair', 1000, 64, 256, 0, 0, FFN_MSG_PAIR_DB % (64, 256)),
+    ('pair', 1000, 96, 96, 0, 0, FFN_MSG_PAIR_D % 96),
+    # kinet_bottleneck_pair_ds: knob 512 = two 16-row tiles per wave
+    ('pair_ds', 1000, 64, 64, 0, 0, (_DS1, 63, 4)),
+    ('pair_ds', 1000, 64, 64, 512, 0, (_DS2, 32, 2)),
+    ('pair_ds', 1068800, 64, 64, 0, 0, (_DS1, 66800, 256)),
+    ('pair_ds', 1068800, 64, 64, 512, 0, (_DS2, 33400, 256)),
+    ('pair_ds', 1000, 128, 128, 0, 0, FFN_MSG_DS_D % 128),
+    ('pair_ds', 1000, 64, 128, 0, 0, FFN_MSG_DS_DB % 128),
+]
+
+# packed-weight layout (ffn_pack_src): (kind, D, F, DB, packed index) -> (source matrix, row, column).  Index =
+# ((chunk * fragments per chunk + fragment) * 64 + lane) * 8 + j, lane = 16 g + c; the formulas of the comment in
+# csrc/ffn_plan.h, by hand
+FFN_PACK_CASES = [
+    ('ffn', 256, 64, 256, 0, (0, 0, 0)),
+    # chunk 1, fragment 9 = W1 (h-tile 1, k-step 1), lane 37 = (2, 5), j 5: row 32 + 16 + 5, column 32 + 16 + 5
+    ('ffn', 256, 64, 256, (1 * 32 + 9) * 512 + 37 * 8 + 5, (0, 53, 53)),
+    # chunk 0, fragment 16 + 3 = W2 tile 3, lane 22 = (1, 6), j 6: row sigma(3, 6) = 32 + 8 + 4 + 2, hidden 16 + 4 + 2
+    ('ffn', 256, 64, 256, 19 * 512 + 22 * 8 + 6, (1, 46, 22)),
+    # Wo fragment 37 = (k-step 2, tile 5), lane 63 = (3, 15), j 7: row sigma(5, 15) = 64 + 24 + 4 + 3, column 64 + 24 + 7
+    ('attn_out_ffn', 256, 64, 256, 37 * 512 + 63 * 8 + 7, (0, 95, 95)),
+    ('attn_out_ffn', 256, 64, 256, 256 * 256 + 19 * 512 + 22 * 8 + 6, (2, 46, 22)),
+    # D = 64 -> DB = 128: 4 + 8 fragments per chunk.  chunk 3, fragment 2 = W3 (h-tile 1, k-step 0), lane 17 = (1, 1), j 1
+    ('pair', 64, 256, 128, (3 * 12 + 2) * 512 + 17 * 8 + 1, (0, 113, 9)),
+    # chunk 7, fragment 4 + 7 = W1 tile 7, lane 40 = (2, 8), j 3: row sigma(7, 8) = 96 + 16 + 4, hidden 224 + 8 + 3
+    ('pair', 64, 256, 128, (7 * 12 + 11) * 512 + 40 * 8 + 3, (1, 116, 235)),
+    # ds: W3, W_ds, W1 = 4 + 4 + 4 fragments.  chunk 1, fragment 6 = W_ds (h-tile 1, k-step 0), lane 5 = (0, 5), j 2
+    ('pair_ds', 64, 256, 64, (1 * 12 + 6) * 512 + 5 * 8 + 2, (1, 53, 2)),
+    # chunk 0, fragment 9 = W1 tile 1, lane 48 = (3, 0), j 4: row sigma(1, 0) = 4, hidden 16 + 12
+    ('pair_ds', 64, 256, 64, 9 * 512 + 48 * 8 + 4, (2, 4, 28)),
+    # D = 288: 18 + 18 fragments.  chunk 1, fragment 17 = W1 (h-tile 1, k-step 8), lane 31 = (1, 15), j 0
+    ('ffn', 288, 64, 288, (36 + 17) * 512 + 31 * 8, (0, 63, 264)),
+    # chunk 0, fragment 35 = W2 tile 17, lane 15 = (0, 15), j 7: row sigma(17, 15) = 256 + 24 + 4 + 3, hidden 16 + 3
+    ('ffn', 288, 64, 288, 35 * 512 + 15 * 8 + 7, (1, 287, 19)),
+]
+# (kind, D, F, DB) the models pack, plus D = 288 and the shapes of tests/test_ffn_pack_gpu.py
+FFN_PACK_SHAPES = [
+    ('ffn', 256, 1024, 256), ('ffn', 256, 2048, 256), ('ffn', 288, 1024, 288), ('attn_out_ffn', 256, 1024, 256),
+    ('attn_out_ffn', 288, 64, 288), ('pair', 64, 256, 64), ('pair', 64, 256, 128), ('pair', 128, 512, 128),
+    ('pair', 256, 1024, 256), ('pair', 288, 64, 288), ('pair_ds', 64, 256, 64), ('ffn', 64, 256, 64), ('ffn', 256, 64, 256),
+]
+
+
+def ffn_pack_shapes(kind, D, F, DB):
+    """Shapes of a pack kind's source matrices, in the pack call's argument order."""
+    return {'ffn': [(F, D), (D, F)], 'attn_out_ffn': [(D, D), (F, D), (D, F)], 'pair': [(F, D), (DB, F)],
+            'pair_ds': [(F, D), (F, D), (DB, F)]}[kind]

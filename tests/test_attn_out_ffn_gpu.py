@@ -86,6 +86,31 @@ def test_attn_out_ffn_vs_fp64_and_unfused(K, M, dtype):
     assert torch.equal(y, y2)
 
 
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
+def test_attn_out_ffn_residual_staging_bit_identical(K, dtype):
+    """kinet_ffn_set_debug 64 loads the residual under the Wo chunks instead of after the last one (RV = 1): another
+    kernel, the same sums in the same order, so bit-identical outputs; 16391 rows = 65 tiles with a ragged last one.
+    Each call runs the kernel the CPU planner names for it."""
+    from kinet_amd import _native
+    M = 16391
+    mods = [m.cuda() for m in _modules(64)]
+    g = torch.Generator().manual_seed(65)
+    a, r = torch.randn(M, D, generator=g).to(dtype).cuda(), torch.randn(M, D, generator=g).to(dtype).cuda()
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    outs, ran = [], []
+    try:
+        for knob in (0, 64):
+            _native.lib().kinet_ffn_set_debug(knob)
+            outs.append(K.attn_out_ffn_fused(a, mods[0], r, mods[1], mods[2], mods[3], mods[4]))
+            ran.append(K.ffn_last_kernel())
+            assert ran[-1] == K.ffn_launch_plan('attn_out_ffn', M, D, FH, cus=cus)['kernel']
+    finally:
+        _native.lib().kinet_ffn_set_debug(0)
+    torch.cuda.synchronize()
+    assert ran == ['ffn_fused_rt2_kernel<256, true>', 'ffn_fused_rt2_kernel<256, true, 1>']
+    assert torch.isfinite(outs[0].float()).all() and torch.equal(outs[0], outs[1])
+
+
 def test_attn_out_ffn_strides_out_and_no_norm2(K):
     """A and R column slices of wider buffers (lda, ldr > D), out= given, norm2 absent."""
     dtype, M = torch.bfloat16, 700

@@ -62,14 +62,18 @@ def test_bottleneck_pair_ds_tile_variants_bit_identical(M):
     s3, sd, s1 = torch.ones(256).cuda(), torch.ones(256).cuda(), torch.ones(64).cuda()
     b3, bd, b1 = (torch.randn(256, generator=g) * 0.1).cuda(), torch.zeros(256).cuda(), torch.zeros(64).cuda()
     packed, b3ds = K.bottleneck_pack_ds(w3, wd, w1, s3, sd, s1, b3, bd, torch.bfloat16)
-    outs = []
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    outs, ran = [], []
     try:
         for knob in (0, 512):
             _native.lib().kinet_ffn_set_debug(knob)
             outs.append(K.bottleneck_pair_ds(x, x0, packed, b3ds, b1))
+            ran.append(K.ffn_last_kernel())
+            assert ran[-1] == K.ffn_launch_plan('pair_ds', M, 64, cus=cus)['kernel']   # the CPU plan of this call
     finally:
         _native.lib().kinet_ffn_set_debug(0)
     torch.cuda.synchronize()
+    assert ran[0] != ran[1]   # the knob took
     assert torch.isfinite(outs[0][0].float()).all() and outs[0][0].float().abs().sum() > 0
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
 

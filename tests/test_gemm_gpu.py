@@ -894,6 +894,12 @@ def test_direct_conv3x3_c64_vs_fp32(K, B, H, W, dtype):
     assert ((y2.permute(0, 3, 1, 2).float().cpu() - r2).abs() <= 2 * ulp * r2.abs() + 1e-3).all()
 
 
+def _ffn_planned(K, kind, M, D, DB=None):
+    """The kernel the CPU planner names for this call on this device, under the thread's knobs as they stand."""
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    return K.ffn_launch_plan(kind, M, D, DB=DB, cus=cus)['kernel']
+
+
 @pytest.mark.parametrize('M', [16384, 40007, 355568])
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
 def test_ffn_fused_tile_variants_bit_identical(K, M, dtype):
@@ -904,14 +910,17 @@ def test_ffn_fused_tile_variants_bit_identical(K, M, dtype):
     g = torch.Generator().manual_seed(M)
     lin1, lin2, norm = torch.nn.Linear(256, 1024).cuda(), torch.nn.Linear(1024, 256).cuda(), torch.nn.LayerNorm(256).cuda()
     x = torch.randn(M, 256, generator=g).to(dtype).cuda()
-    outs = []
+    outs, ran = [], []
     try:
         for knob in (0, 2, 8):
             _native.lib().kinet_ffn_set_debug(knob)
             outs.append(K.ffn_fused(x, lin1, lin2, norm))
+            ran.append(K.ffn_last_kernel())
+            assert ran[-1] == _ffn_planned(K, 'ffn', M, 256)
     finally:
         _native.lib().kinet_ffn_set_debug(0)
     torch.cuda.synchronize()
+    assert len(set(ran)) == 3   # the knobs took: three different kernels
     assert torch.isfinite(outs[0].float()).all()
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
 
@@ -996,12 +1005,17 @@ def test_bottleneck_pair64_kernels_bit_identical(K, M):
     s3, b3, s1, b1 = (torch.rand(256) + 0.5).cuda(), torch.randn(256).cuda() * 0.1, (torch.rand(64) + 0.5).cuda(), torch.randn(64).cuda() * 0.1
     packed = K.bottleneck_pack(w3, w1, s3, s1, torch.bfloat16)
     y0, t0 = K.bottleneck_pair(x, res, packed, b3, b1)
+    ran0 = K.ffn_last_kernel()
+    assert ran0 == _ffn_planned(K, 'pair', M, 64)
     old = _native.lib().kinet_ffn_set_debug(16)
     try:
         y1, t1 = K.bottleneck_pair(x, res, packed, b3, b1)
+        ran1 = K.ffn_last_kernel()
+        assert ran1 == _ffn_planned(K, 'pair', M, 64)
     finally:
         _native.lib().kinet_ffn_set_debug(old)
     torch.cuda.synchronize()
+    assert ran0 != ran1   # the knob took
     assert torch.equal(y0, y1) and torch.equal(t0, t1)
 
 
@@ -1021,15 +1035,18 @@ def test_bottleneck_pair_row_tiles_bit_identical(K, D, M):
     s3, b3 = (torch.rand(F_, generator=g) + 0.5).cuda(), (torch.randn(F_, generator=g) * 0.1).cuda()
     s1, b1 = (torch.rand(D, generator=g) + 0.5).cuda(), (torch.randn(D, generator=g) * 0.1).cuda()
     packed = K.bottleneck_pack(w3, w1, s3, s1, torch.bfloat16)
-    outs = []
+    outs, ran = [], {}
     for knob, solo in ((0, 0), (0, 1), (128, 0), (256, 0)):
         old, old_solo = _native.lib().kinet_ffn_set_debug(knob), _native.lib().kinet_set_solo_launch(solo)
         try:
             outs.append(K.bottleneck_pair(x, res, packed, b3, b1))
+            ran[knob, solo] = K.ffn_last_kernel()
+            assert ran[knob, solo] == _ffn_planned(K, 'pair', M, D)
         finally:
             _native.lib().kinet_ffn_set_debug(old)
             _native.lib().kinet_set_solo_launch(old_solo)
     torch.cuda.synchronize()
+    assert ran[128, 0] != ran[256, 0]   # the knobs took (the four runs select these two kernels only)
     for y, t in outs[1:]:
         assert torch.equal(outs[0][0], y) and torch.equal(outs[0][1], t)
 

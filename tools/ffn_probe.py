@@ -14,7 +14,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--rows', type=int, default=8 * 22223)
 ap.add_argument('--iters', type=int, default=5)
 ap.add_argument('--d', type=int, default=256)
-ap.add_argument('--knobs', default='0,2,8', help='kinet_ffn_set_debug values (D = 288: 0 = wave pairs, 32 = 4 waves)')
+ap.add_argument('--knobs', default='0,2,8', help='kinet_ffn_set_debug values (the FfnDebug bits of csrc/ffn_plan.h)')
 ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f16'])
 ap.add_argument('--attn-out', action='store_true',
                 help='time the encoder tail instead: K.linear(out_proj, residual, ln) + K.ffn_fused against '
