@@ -85,6 +85,80 @@ int kinet_segm_track_resolve(const float* logits, const int32_t* src, const int1
                              int T, int n, int h, int w, int max_h, int max_w, int img_h, int img_w, int oh, int ow,
                              float threshold, kinet_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mask training (csrc/segm_train.hip): the fused mask losses and the backward of the head's own
+ * ops.  f32 only (the training path is f32).  No float atomics; every sum is taken in an order
+ * fixed by the shapes alone, so reruns are bit-identical.
+ * ------------------------------------------------------------------------------------------- */
+
+/* loss_masks (detr.py:763-791) without the full-resolution intermediate:
+ *   v = bilinear_{align_corners=False}(logits -> (H, W)),  p = sigmoid(v),  t = target != 0
+ *   sums[r] = { sum focal(v, t),  sum p*t,  sum p,  sum t }  over all H*W pixels of row r, with
+ *   focal = alpha_t * BCEWithLogits(v, t) * (1 - p_t)^gamma  (util/misc.py:634-665; alpha < 0: no alpha_t)
+ *   loss[0] = sum_r sums[r][0] / (H*W) / num_boxes
+ *   loss[1] = sum_r (1 - (2*sums[r][1] + 1) / (sums[r][2] + sums[r][3] + 1)) / num_boxes      (dice_loss :616-631)
+ * logits (n, h, w) f32, target (n, H, W) bytes, sums (n, 4) f32, loss 2 f32 on the device.
+ * The bilinear source index is torch's area_pixel_compute_source_index, the rule of
+ * kinet_segm_postprocess.  H >= h and W >= w (ratios >= 1, integer or not); gamma must be 2.
+ * n == 0 writes loss = {0, 0} with a memset and launches nothing.  A thread owns runs of 4
+ * consecutive target bytes (one 32-bit load where the run lies inside the row); the rows' sums are
+ * block partials in ws, added in block order.
+ * ws: kinet_segm_mask_loss_workspace(n, H, W) floats. */
+long kinet_segm_mask_loss_workspace(int n, int H, int W);
+int kinet_segm_mask_loss(const float* logits, const uint8_t* target, float* sums, float* loss, int n, int h, int w,
+                         int H, int W, float alpha, float gamma, float num_boxes, float* ws, kinet_stream_t stream);
+
+/* Backward of kinet_segm_mask_loss: dlogits (n, h, w) = d(dloss[0]*loss[0] + dloss[1]*loss[1]) / dlogits,
+ * from the forward's inputs and its `sums` (the dice quotient's derivative needs the row sums);
+ * dloss 2 f32 on the device.  A gather: one thread per low-resolution pixel walks the
+ * full-resolution pixels whose bilinear taps include it (found with the forward's index
+ * function, so the two agree on every tap), forms the analytic derivative of both losses there
+ * and adds it with the tap's weight, rows then columns ascending.  No workspace. */
+int kinet_segm_mask_loss_backward(const float* logits, const uint8_t* target, const float* sums, const float* dloss,
+                                  float* dlogits, int n, int h, int w, int H, int W, float alpha, float gamma,
+                                  float num_boxes, kinet_stream_t stream);
+
+/* Backward of kinet_segm_attention (f32): with s[r] = sum over (p, n) of att*datt in a fixed order,
+ *   dl[r, p, n] = att[r, p, n] * (datt[r, p, n] - s[r])          (exactly 0 where att is 0: masked pixels)
+ *   dqp[r, n*D + k] = scale * sum_p dl[r, p, n] * kp[b, p, n*D + k]              (p ascending)
+ *   dkp[b, p, n*D + k] = scale * sum_{r in frame b, ascending} dl[r, p, n] * qp[r, n*D + k]
+ * att, datt (B*Q, HW, heads); qp, dqp (B*Q, d); kp, dkp (B, HW, d).  dqp or dkp may be NULL (not
+ * wanted).  Limits of kinet_segm_attention.  ws: kinet_segm_attention_backward_workspace(B, Q) floats. */
+long kinet_segm_attention_backward_workspace(int B, int Q);
+int kinet_segm_attention_backward(const float* datt, const float* att, const float* qp, const float* kp, float* dqp,
+                                  float* dkp, int B, int Q, int HW, int heads, int d, float scale, float* ws,
+                                  kinet_stream_t stream);
+
+/* ReLU + nearest upsample + FPN add of the training head (kinet_segm_gn_relu_up_add without the
+ * GroupNorm, which the training path runs as its own Function), f32:
+ *   y[r][Y, X, c] = (f ? f[(row0 + r) / Q][Y, X, c] : 0) + relu(x[r])[sy(Y), sx(X), c]
+ * with the legacy-nearest rule sy(Y) = min(floorf(Y * ((float)h / H)), h - 1).  x (rows, h, w, C),
+ * y (rows, H, W, C), f (B, H, W, C) or NULL ((H, W) must then equal (h, w)).  C % 4 == 0, H >= h,
+ * W >= w, row0 + rows <= B*Q. */
+int kinet_segm_relu_up_add(const float* x, const float* f, float* y, int rows, int row0, int Q, int B, int h, int w,
+                           int H, int W, int C, kinet_stream_t stream);
+
+/* Its backward:
+ *   dx[r][y, x, c] = [x[r][y, x, c] > 0] * sum of dy[r][Y, X, c] over the (Y, X) with (sy(Y), sx(X)) = (y, x),
+ *                    Y then X ascending (a gather: the children are found with the forward's rule)
+ *   df[b][Y, X, c] = sum of dy[r][Y, X, c] over the call's rows of frame b, ascending; 0 for a frame
+ *                    without a row in [row0, row0 + rows)
+ * dx or df may be NULL (not wanted).  dx depends on its own row only, so it does not depend on
+ * how the rows are split over calls; df is the sum over THIS call's rows. */
+int kinet_segm_relu_up_add_backward(const float* dy, const float* x, float* dx, float* df, int rows, int row0, int Q,
+                                    int B, int h, int w, int H, int W, int C, kinet_stream_t stream);
+
+/* Backward of kinet_segm_out_conv (f32): dy (rows, H, W), x (rows, H, W, C), wt (3, 3, C);
+ *   dx[r][y, x, c] = sum over (ky, kx) of dy[r][y - ky + 1, x - kx + 1] * wt[ky][kx][c]
+ *   dwt[ky][kx][c] = sum over (r, Y, X) of dy[r][Y, X] * x[r][Y + ky - 1, X + kx - 1, c]
+ *   dbias          = sum of dy
+ * dwt and dbias are two-stage: per-block partials in ws (a block owns a contiguous run of
+ * pixels, its threads' sums added in thread order), then the blocks in order.  dx, or dwt with
+ * dbias, may be NULL (not wanted).  C <= 64.  ws: kinet_segm_out_conv_backward_workspace(rows, H, W, C) floats. */
+long kinet_segm_out_conv_backward_workspace(int rows, int H, int W, int C);
+int kinet_segm_out_conv_backward(const float* dy, const float* x, const float* wt, float* dx, float* dwt,
+                                 float* dbias, int rows, int H, int W, int C, float* ws, kinet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

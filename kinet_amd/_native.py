@@ -118,6 +118,15 @@ _SIGS = {
     'kinet_segm_out_conv': [P, P, P, P, I, I, I, I, I, P],
     'kinet_segm_postprocess': [P, P] + [I] * 9 + [F, I, P],
     'kinet_segm_track_resolve': [P, P, P, P] + [I] * 10 + [F, P],
+    'kinet_segm_mask_loss_workspace': [I, I, I],
+    'kinet_segm_mask_loss': [P, P, P, P] + [I] * 5 + [F, F, F, P, P],
+    'kinet_segm_mask_loss_backward': [P] * 5 + [I] * 5 + [F, F, F, P],
+    'kinet_segm_attention_backward_workspace': [I, I],
+    'kinet_segm_attention_backward': [P] * 6 + [I] * 5 + [F, P, P],
+    'kinet_segm_relu_up_add': [P, P, P] + [I] * 9 + [P],
+    'kinet_segm_relu_up_add_backward': [P, P, P, P] + [I] * 9 + [P],
+    'kinet_segm_out_conv_backward_workspace': [I, I, I, I],
+    'kinet_segm_out_conv_backward': [P] * 6 + [I] * 4 + [P, P],
     'kinet_last_error': [],
     'kinet_version': [],
 }
@@ -128,7 +137,9 @@ _RESTYPES = {'kinet_last_error': ctypes.c_char_p, 'kinet_version': ctypes.c_char
              'kinet_layernorm_backward_workspace': ctypes.c_int64,
              'kinet_dropout_add_layernorm_backward_workspace': ctypes.c_int64,
              'kinet_groupnorm_backward_workspace': ctypes.c_int64,
-             'kinet_mha_backward_workspace': ctypes.c_int64}
+             'kinet_mha_backward_workspace': ctypes.c_int64,
+             'kinet_segm_mask_loss_workspace': ctypes.c_long, 'kinet_segm_attention_backward_workspace': ctypes.c_long,
+             'kinet_segm_out_conv_backward_workspace': ctypes.c_long}
 
 DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.float64: 3}
 

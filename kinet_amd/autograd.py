@@ -21,6 +21,10 @@ sigmoid / masked_fill glue of the heads.
     dropout_act(x, drop)                    drop(relu(x)), the FFN hidden
     msda_prep(off, logits, refs, ...)       MSDeformAttn sampling locations + softmaxed weights
     inverse_sigmoid(x)                      util/misc.py:609-613
+    segm_attention(qp, kp, mask, Q, heads)  MHAttentionMap's joint softmax over heads x pixels
+    segm_relu_up_add(x, f, row0, Q, size)   the mask head's ReLU + nearest upsample + FPN add
+    segm_out_conv(x, weight, bias)          the mask head's 3x3 convolution to one channel
+    segm_mask_loss(logits, target, n_boxes) bilinear upsample + sigmoid focal + dice losses, fused
 
 Weight gradients are reductions over the row (pixel / token) dimension (kinet_gemm_tn,
 split-K with a fixed-order finalize), input gradients are GEMMs against the transposed
@@ -400,3 +404,112 @@ class _InverseSigmoid(Function):
 def inverse_sigmoid(x, eps=1e-5):
     """util/misc.py:609-613 on f32 device tensors, one kernel each way."""
     return _InverseSigmoid.apply(x, float(eps))
+
+
+# ------------------------------------------------- mask head and mask losses (csrc/segm_train.hip)
+class _SegmAttention(Function):
+    @staticmethod
+    def forward(ctx, qp, kp, mask, Q, heads):
+        _f32(qp)
+        _f32(kp)
+        qp, kp = qp.contiguous(), kp.contiguous()
+        att = K.segm_attention(qp, kp, mask, Q, heads)
+        ctx.save_for_backward(att, qp, kp)
+        ctx.conf = (Q, heads)
+        return att
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, datt):
+        att, qp, kp = ctx.saved_tensors
+        Q, heads = ctx.conf
+        dqp, dkp = K.segm_attention_backward(datt.contiguous().float(), att, qp, kp, Q, heads,
+                                             need_q=ctx.needs_input_grad[0], need_k=ctx.needs_input_grad[1])
+        return dqp, dkp, None, None, None
+
+
+def segm_attention(qp, kp, mask, Q, heads):
+    """MHAttentionMap's joint softmax over heads x pixels (kernels.segm_attention): qp (B*Q, d), kp
+    (B, HW, d), mask (B, HW) or None -> (B*Q, HW, heads); differentiable w.r.t. qp and kp."""
+    return _SegmAttention.apply(qp, kp, mask, Q, heads)
+
+
+class _SegmReluUpAdd(Function):
+    @staticmethod
+    def forward(ctx, x, f, row0, Q, size):
+        _f32(x)
+        x = x.contiguous()
+        y = K.segm_relu_up_add(x, None if f is None else f.detach(), row0, Q, size)
+        ctx.save_for_backward(x)
+        ctx.conf = (None if f is None else tuple(f.shape), row0, Q)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        f_shape, row0, Q = ctx.conf
+        dx, df = K.segm_relu_up_add_backward(dy.contiguous().float(), x, f_shape, row0, Q,
+                                             need_x=ctx.needs_input_grad[0],
+                                             need_f=f_shape is not None and ctx.needs_input_grad[1])
+        return dx, df, None, None, None
+
+
+def segm_relu_up_add(x, f=None, row0=0, Q=None, size=None):
+    """f[(row0 + r) // Q] + nearest_upsample(relu(x)) on NHWC f32 (the head's :153-156 without the
+    GroupNorm): x (rows, h, w, C), f (B, H, W, C) or None (then `size`, if given, must be x's);
+    differentiable w.r.t. x and f."""
+    if f is None and size is not None and tuple(size) != tuple(x.shape[1:3]):
+        raise RuntimeError('segm_relu_up_add: without an FPN operand the output has the input\'s size')
+    return _SegmReluUpAdd.apply(x, f, int(row0), Q, size)
+
+
+class _SegmOutConv(Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        _f32(x)
+        x = x.contiguous()
+        wt = weight.detach()[0].permute(1, 2, 0).float().contiguous()          # (3, 3, C)
+        y = K.segm_out_conv(x, wt, bias.detach().float().contiguous())
+        ctx.save_for_backward(x, wt)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, wt = ctx.saved_tensors
+        ng = ctx.needs_input_grad
+        dx, dwt, db = K.segm_out_conv_backward(dy.contiguous().float(), x, wt, need_x=ng[0], need_w=ng[1] or ng[2])
+        dw = dwt.permute(2, 0, 1).unsqueeze(0).contiguous() if ng[1] else None  # (1, C, 3, 3)
+        return dx, dw, db if ng[2] else None
+
+
+def segm_out_conv(x, weight, bias):
+    """out_lay: the 3x3 pad-1 convolution to one channel, x (rows, H, W, C) NHWC f32, weight
+    (1, C, 3, 3), bias (1,) -> (rows, H, W); differentiable w.r.t. all three."""
+    return _SegmOutConv.apply(x, weight, bias)
+
+
+class _SegmMaskLoss(Function):
+    @staticmethod
+    def forward(ctx, logits, target, num_boxes):
+        _f32(logits)
+        logits = logits.contiguous()
+        loss, sums = K.segm_mask_loss(logits, target, num_boxes)
+        ctx.save_for_backward(logits, target, sums)
+        ctx.num_boxes = num_boxes
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dloss):
+        logits, target, sums = ctx.saved_tensors
+        return K.segm_mask_loss_backward(logits, target, sums, dloss.contiguous().float(), ctx.num_boxes), None, None
+
+
+def segm_mask_loss(logits, target, num_boxes):
+    """loss_masks' two scalars (detr.py:779-790) fused: sigmoid focal loss (alpha 0.25, gamma 2) and dice
+    loss of bilinear_upsample(logits (n, h, w)) against target (n, H, W) uint8, each summed over the
+    rows and divided by num_boxes -> (loss_mask, loss_dice); differentiable w.r.t. logits."""
+    loss = _SegmMaskLoss.apply(logits, target, float(num_boxes))
+    return loss[0], loss[1]

@@ -10,6 +10,7 @@
 
 #include "../../include/kinet_segm.h"
 #include "common.h"
+#include "segm_resize.h"
 
 namespace kinet {
 namespace {
@@ -354,14 +355,6 @@ __global__ __launch_bounds__(256) void segm_out_conv_kernel(const T* __restrict_
 // ---------------------------------------------------------------------------------
 // PostProcessSegm: one thread per output pixel
 // ---------------------------------------------------------------------------------
-// torch's area_pixel_compute_source_index (align_corners = false) + guard_index_and_lambda
-__device__ __forceinline__ void bilinear_src(int dst, float scale, int in, int& i0, int& i1, float& l1) {
-    const float real = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-    i0 = min((int)floorf(real), in - 1);
-    l1 = fminf(fmaxf(real - (float)i0, 0.f), 1.f);
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-}
-
 // One output pixel's four taps and weights: the legacy-nearest map of (oy, ox) into the cropped
 // (img_h, img_w) probability map, then the bilinear source position in the (h, w) logits.
 struct SegmTap {

@@ -1820,3 +1820,136 @@ def segm_track_resolve(logits, src, prev_labels, max_hw, img_hw, out_hw, thresho
            T, n, h, w, int(max_hw[0]), int(max_hw[1]), int(img_hw[0]), int(img_hw[1]), oh, ow, float(threshold),
            N.stream(logits.device), work={'family': 'segm', 'bytes': out.numel() * 4})
     return out
+
+
+# ------------------------------------------------------------------- mask training
+MASK_LOSS_ALPHA, MASK_LOSS_GAMMA = 0.25, 2.0     # detr.py:788 calls sigmoid_focal_loss with its defaults
+
+
+def _ws(n, device):
+    return torch.empty(max(1, int(n)), dtype=torch.float32, device=device)
+
+
+def _mask_loss_args(logits, target):
+    N.require_gpu(logits, target)
+    if logits.dtype != torch.float32 or logits.dim() != 3 or target.dtype != torch.uint8 or target.dim() != 3 \
+            or target.shape[0] != logits.shape[0]:
+        raise RuntimeError(f'segm_mask_loss: logits must be f32 (n, h, w) and target uint8 (n, H, W): got '
+                           f'{tuple(logits.shape)} {logits.dtype}, {tuple(target.shape)} {target.dtype}')
+    return logits.contiguous(), target.contiguous()
+
+
+def segm_mask_loss(logits, target, num_boxes, alpha=MASK_LOSS_ALPHA, gamma=MASK_LOSS_GAMMA):
+    """The fused mask losses (kinet_segm_mask_loss): logits (n, h, w) f32, target (n, H, W) uint8 0/1 ->
+    (loss (2,) f32 = [focal, dice], sums (n, 4) f32 per-row [focal, p*t, p, t] sums the backward reads)."""
+    logits, target = _mask_loss_args(logits, target)
+    n, h, w = logits.shape
+    H, W = target.shape[1:]
+    loss = torch.empty(2, dtype=torch.float32, device=logits.device)
+    sums = torch.empty((n, 4), dtype=torch.float32, device=logits.device)
+    ws = _ws(N.lib().kinet_segm_mask_loss_workspace(n, H, W), logits.device)
+    N.call('kinet_segm_mask_loss', N.ptr(logits), N.ptr(target), N.ptr(sums), N.ptr(loss), n, h, w, H, W, float(alpha),
+           float(gamma), float(num_boxes), N.ptr(ws), N.stream(logits.device),
+           work={'family': 'segm_loss', 'bytes': target.numel() + 4 * logits.numel()})
+    return loss, sums
+
+
+def segm_mask_loss_backward(logits, target, sums, dloss, num_boxes, alpha=MASK_LOSS_ALPHA, gamma=MASK_LOSS_GAMMA):
+    """d(dloss . loss) / dlogits of segm_mask_loss (kinet_segm_mask_loss_backward): dloss (2,) f32 on the
+    device -> (n, h, w) f32."""
+    logits, target = _mask_loss_args(logits, target)
+    N.require_gpu(sums, dloss)
+    n, h, w = logits.shape
+    H, W = target.shape[1:]
+    if sums.dtype != torch.float32 or tuple(sums.shape) != (n, 4) or dloss.dtype != torch.float32 or dloss.numel() != 2:
+        raise RuntimeError('segm_mask_loss_backward: sums must be f32 (n, 4) and dloss f32 (2,)')
+    dlogits = torch.empty_like(logits)
+    N.call('kinet_segm_mask_loss_backward', N.ptr(logits), N.ptr(target), N.ptr(sums.contiguous()),
+           N.ptr(dloss.contiguous()), N.ptr(dlogits), n, h, w, H, W, float(alpha), float(gamma), float(num_boxes),
+           N.stream(logits.device), work={'family': 'segm_loss', 'bytes': target.numel() + 8 * logits.numel()})
+    return dlogits
+
+
+def segm_attention_backward(datt, att, qp, kp, Q, heads, need_q=True, need_k=True):
+    """Backward of segm_attention in f32 (kinet_segm_attention_backward): datt, att (B*Q, HW, heads),
+    qp (B*Q, d), kp (B, HW, d) -> (dqp, dkp), None where not needed."""
+    N.require_gpu(datt, att, qp, kp)
+    B, HW, d = kp.shape
+    datt, att, qp, kp = datt.contiguous(), att.contiguous(), qp.contiguous(), kp.contiguous()
+    if any(t.dtype != torch.float32 for t in (datt, att, qp, kp)) or qp.shape != (B * Q, d) \
+            or att.shape != (B * Q, HW, heads) or datt.shape != att.shape:
+        raise RuntimeError('segm_attention_backward: f32 datt / att (B*Q, HW, heads), qp (B*Q, d), kp (B, HW, d)')
+    dqp = torch.empty_like(qp) if need_q else None
+    dkp = torch.empty_like(kp) if need_k else None
+    ws = _ws(N.lib().kinet_segm_attention_backward_workspace(B, Q), qp.device)
+    N.call('kinet_segm_attention_backward', N.ptr(datt), N.ptr(att), N.ptr(qp), N.ptr(kp), N.ptr(dqp), N.ptr(dkp), B, Q,
+           HW, heads, d, float(d // heads) ** -0.5, N.ptr(ws), N.stream(qp.device),
+           work={'family': 'segm', 'flops': 8.0 * B * Q * HW * d})
+    return dqp, dkp
+
+
+def _relu_up_add_geometry(x, f, row0, Q, size):
+    rows, h, w, C = x.shape
+    if f is not None:
+        if f.dtype != torch.float32 or f.dim() != 4 or f.shape[3] != C:
+            raise RuntimeError('segm_relu_up_add: f must be f32 (B, H, W, C)')
+        B, H, W = f.shape[:3]
+    else:
+        B, (H, W) = 1, ((h, w) if size is None else size)
+        Q = None
+    return rows, h, w, C, B, int(H), int(W), int(Q) if Q is not None else max(rows + row0, 1)
+
+
+def segm_relu_up_add(x, f=None, row0=0, Q=None, size=None):
+    """y = f[(row0 + r) // Q] + nearest-upsampled relu(x) in f32 (kinet_segm_relu_up_add): x (rows, h, w, C),
+    f (B, H, W, C) or None (the output then has x's size)."""
+    N.require_gpu(x, f)
+    if x.dtype != torch.float32:
+        raise RuntimeError('segm_relu_up_add: f32 only (the training path)')
+    x = x.contiguous()
+    f = None if f is None else f.contiguous()
+    rows, h, w, C, B, H, W, Qn = _relu_up_add_geometry(x, f, row0, Q, size)
+    y = torch.empty((rows, H, W, C), dtype=torch.float32, device=x.device)
+    N.call('kinet_segm_relu_up_add', N.ptr(x), N.ptr(f), N.ptr(y), rows, row0, Qn, B, h, w, H, W, C, N.stream(x.device),
+           work={'family': 'segm', 'bytes': 4 * (x.numel() + 2 * y.numel())})
+    return y
+
+
+def segm_relu_up_add_backward(dy, x, f_shape=None, row0=0, Q=None, need_x=True, need_f=True):
+    """Backward of segm_relu_up_add (kinet_segm_relu_up_add_backward): dy (rows, H, W, C), x (rows, h, w, C),
+    f_shape the FPN operand's (B, H, W, C) or None -> (dx, df), None where not needed.  df sums this
+    call's rows only."""
+    N.require_gpu(dy, x)
+    dy, x = dy.contiguous(), x.contiguous()
+    rows, h, w, C = x.shape
+    H, W = dy.shape[1:3]
+    if dy.dtype != torch.float32 or x.dtype != torch.float32 or dy.shape[0] != rows or dy.shape[3] != C:
+        raise RuntimeError('segm_relu_up_add_backward: f32 dy (rows, H, W, C) and x (rows, h, w, C)')
+    if f_shape is None:
+        B, Qn, need_f = 1, max(rows + row0, 1), False
+    else:
+        if tuple(f_shape[1:]) != (H, W, C):
+            raise RuntimeError('segm_relu_up_add_backward: f_shape must be (B, H, W, C) of dy')
+        B, Qn = int(f_shape[0]), int(Q) if Q is not None else max(rows + row0, 1)
+    dx = torch.empty_like(x) if need_x else None
+    df = torch.empty((B, H, W, C), dtype=torch.float32, device=x.device) if need_f else None
+    N.call('kinet_segm_relu_up_add_backward', N.ptr(dy), N.ptr(x), N.ptr(dx), N.ptr(df), rows, row0, Qn, B, h, w, H, W, C,
+           N.stream(x.device), work={'family': 'segm', 'bytes': 4 * (2 * dy.numel() + 2 * x.numel())})
+    return dx, df
+
+
+def segm_out_conv_backward(dy, x, wt, need_x=True, need_w=True):
+    """Backward of segm_out_conv in f32 (kinet_segm_out_conv_backward): dy (rows, H, W), x (rows, H, W, C),
+    wt (3, 3, C) -> (dx, dwt (3, 3, C), dbias (1,)), None where not needed."""
+    N.require_gpu(dy, x, wt)
+    dy, x, wt = dy.contiguous(), x.contiguous(), wt.contiguous()
+    rows, H, W, C = x.shape
+    if any(t.dtype != torch.float32 for t in (dy, x, wt)) or tuple(dy.shape) != (rows, H, W) or tuple(wt.shape) != (3, 3, C):
+        raise RuntimeError('segm_out_conv_backward: f32 dy (rows, H, W), x (rows, H, W, C), wt (3, 3, C)')
+    dx = torch.empty_like(x) if need_x else None
+    dwt = torch.empty_like(wt) if need_w else None
+    db = torch.empty(1, dtype=torch.float32, device=x.device) if need_w else None
+    ws = _ws(N.lib().kinet_segm_out_conv_backward_workspace(rows, H, W, C), x.device) if need_w else None
+    N.call('kinet_segm_out_conv_backward', N.ptr(dy), N.ptr(x), N.ptr(wt), N.ptr(dx), N.ptr(dwt), N.ptr(db), rows, H, W,
+           C, N.ptr(ws), N.stream(x.device), work={'family': 'segm', 'bytes': 4 * (dy.numel() + 2 * x.numel())})
+    return dx, dwt, db

@@ -12,10 +12,13 @@ reference's default `deformable: false`; kinet_amd/models/detr.py, inference onl
 deformable branch also builds the two-stage variant (`two_stage: true`, inference only; the
 proposal stage runs on csrc/two_stage.hip) and, with `masks: true` (cfgs/train_coco_person_masks.yaml,
 cfgs/train_mots20.yaml), DeformableDETRSegm / DeformableDETRSegmTracking plus the 'segm'
-postprocessor (:63-69, :165-166; kinet_amd/models/segmentation.py on csrc/segm.hip, inference
-only: `out['pred_masks']`).  Still raising NotImplementedError: `masks` without `deformable`
-(vanilla DETRSegm / DETRSegmTracking) or with `two_stage`, the panoptic postprocessor
-(dataset coco_panoptic), and the mask / dice losses (the criterion is built without them).
+postprocessor (:63-69, :165-166; kinet_amd/models/segmentation.py on csrc/segm.hip:
+`out['pred_masks']`).  What build_model returns for masks is the inference model: under autograd
+it raises, and its criterion carries no mask / dice losses.  Training the mask head is opt-in:
+kinet_amd.train.build_mask_training(args) returns the same model with `mask_training` set and the
+criterion rebuilt with build_criterion(..., mask_losses=True) (csrc/segm_train.hip).  Still
+raising NotImplementedError: `masks` without `deformable` (vanilla DETRSegm / DETRSegmTracking) or
+with `two_stage`, and the panoptic postprocessor (dataset coco_panoptic).
 """
 import torch
 
@@ -102,7 +105,7 @@ def build_model(args):
         pass
     postprocessors = {'bbox': DeformablePostProcess()}
     if masks:
-        # the criterion above carries no mask / dice losses (training the heads is not built)
+        # the criterion above carries no mask / dice losses: kinet_amd.train.build_mask_training adds them
         postprocessors['segm'] = PostProcessSegm()
     return model, criterion, postprocessors
 

@@ -8,6 +8,12 @@ output (:858-870).  `num_boxes` is all-reduced over the process group and averag
 the world size (:841-846) -- the one scalar collective of the criterion.  These are small
 ops over (batch, queries, classes) tensors; they run as torch ops on the predictions'
 device (the MFMA-bound and gather-bound work is in the detector forward).
+
+'masks' (:763-791, opt-in: build_criterion(..., mask_losses=True), kinet_amd.train.build_mask_training)
+is the exception: the bilinear upsampling of the matched rows' logits to the targets' size, the
+sigmoid focal loss and the dice loss are ONE kernel each way (autograd.segm_mask_loss on
+csrc/segm_train.hip), the full-resolution map is never materialised.  It is skipped for the
+auxiliary outputs (:859) and, like every kernel call, raises on CPU tensors.
 """
 import torch
 import torch.distributed as dist
@@ -133,9 +139,32 @@ class SetCriterion(nn.Module):
                                                        self.deferred_checks if src_boxes.is_cuda else None))
         return {'loss_bbox': loss_bbox.sum() / num_boxes, 'loss_giou': loss_giou.sum() / num_boxes}
 
+    def loss_masks(self, outputs, targets, indices, num_boxes):
+        """detr.py:763-791 on the fused kernel.  The target stack holds the matched masks only, padded
+        (with zeros, top-left aligned) to the largest mask of the batch as
+        nested_tensor_from_tensor_list pads them (:776); the padded area counts in the loss (the
+        reference's TODO, :775)."""
+        from kinet_amd import autograd as A
+        assert 'pred_masks' in outputs
+        src_masks = outputs['pred_masks']
+        device = src_masks.device
+        logits = src_masks[self._get_src_permutation_idx(indices)]                       # (n, h, w)
+        Ht = max(t['masks'].shape[-2] for t in targets)
+        Wt = max(t['masks'].shape[-1] for t in targets)
+        target = torch.zeros((logits.shape[0], Ht, Wt), dtype=torch.uint8, device=device)
+        o = 0
+        for t, (_, J) in zip(targets, indices):
+            m = t['masks'].to(device)[J.to(device)]
+            target[o:o + m.shape[0], :m.shape[1], :m.shape[2]] = m != 0
+            o += m.shape[0]
+        loss_mask, loss_dice = A.segm_mask_loss(logits, target, num_boxes)
+        return {'loss_mask': loss_mask, 'loss_dice': loss_dice}
+
     def get_loss(self, loss, outputs, targets, indices, num_boxes, **kwargs):
         loss_map = {'labels': self.loss_labels_focal if self.focal_loss else self.loss_labels,
                     'cardinality': self.loss_cardinality, 'boxes': self.loss_boxes}
+        if 'masks' in self.losses:      # (only a criterion built with mask_losses knows the loss)
+            loss_map['masks'] = self.loss_masks
         if loss not in loss_map:
             raise NotImplementedError(f'loss {loss} is outside the detection hot path')
         return loss_map[loss](outputs, targets, indices, num_boxes, **kwargs)
@@ -197,21 +226,29 @@ class SetCriterion(nn.Module):
         for i, aux_outputs in enumerate(aux):
             indices = all_indices[i + 1]
             for loss in self.losses:
+                if loss == 'masks':     # too costly for the intermediate layers (:859-861)
+                    continue
                 kwargs = {'log': False} if loss == 'labels' else {}
                 l_dict = self.get_loss(loss, aux_outputs, targets, indices, num_boxes, **kwargs)
                 losses.update({k + f'_{i}': v for k, v in l_dict.items()})
         return losses
 
 
-def build_criterion(args, num_classes, matcher):
-    """models/__init__.py:125-161 (no masks, no two-stage on this path)."""
+def build_criterion(args, num_classes, matcher, mask_losses=False):
+    """models/__init__.py:125-161 (no two-stage on this path).  mask_losses=True adds the reference's
+    `args.masks` branch (:131-133, :145-146): loss_mask / loss_dice weights (before the aux
+    expansion, so their `_i` keys exist as there) and the 'masks' loss; build_model leaves it False."""
     weight_dict = {'loss_ce': args.cls_loss_coef, 'loss_bbox': args.bbox_loss_coef, 'loss_giou': args.giou_loss_coef}
+    if mask_losses:
+        weight_dict['loss_mask'] = args.mask_loss_coef
+        weight_dict['loss_dice'] = args.dice_loss_coef
     if args.aux_loss:
         aux = {}
         for i in range(args.dec_layers - 1):
             aux.update({k + f'_{i}': v for k, v in weight_dict.items()})
         weight_dict.update(aux)
     return SetCriterion(num_classes, matcher=matcher, weight_dict=weight_dict, eos_coef=args.eos_coef,
-                        losses=['labels', 'boxes', 'cardinality'], focal_loss=args.focal_loss,
+                        losses=['labels', 'boxes', 'cardinality'] + (['masks'] if mask_losses else []),
+                        focal_loss=args.focal_loss,
                         focal_alpha=args.focal_alpha, focal_gamma=args.focal_gamma, tracking=args.tracking,
                         track_query_false_positive_eos_weight=args.track_query_false_positive_eos_weight)

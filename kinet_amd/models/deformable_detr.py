@@ -382,6 +382,10 @@ class DeformableDETR(nn.Module):
         padded = None if any(z is None for z in size_sets) else any(len(set(z)) > 1 for z in size_sets)
         hs, memory, init_reference, inter_references, _, _ = self.transformer(
             src_list, mask_list, pos_list, self.query_embed.weight, targets, padded=padded)
+        if getattr(self, '_segm_want', False):
+            # the mask head's training inputs (kinet_amd/models/segmentation.py): the current frame's
+            # level-1 projection (the last frame's levels end the lists) and its padding mask
+            self._segm_ctx = {'src_nchw': src_list[-3], 'mask': mask_list[-3]}
         outputs_classes, outputs_coords = [], []
         for lvl in range(hs.shape[0]):
             reference = init_reference if lvl == 0 else inter_references[lvl - 1]

@@ -1,4 +1,4 @@
-"""Segmentation heads of Deformable DETR on the kinet_amd kernels (inference only).
+"""Segmentation heads of Deformable DETR on the kinet_amd kernels.
 
 Mirrors src/trackformer/models/detr_segmentation.py: DETRSegmBase :29-71, DeformableDETRSegm
 :81-84, DeformableDETRSegmTracking :94-98, MaskHeadSmallConv :105-178, MHAttentionMap :181-216 and
@@ -22,14 +22,34 @@ kernel choice depends on the chunk (split-K is off), so pred_masks does not depe
 head's operands until the next forward; `mask_logits(rows, frame)` then runs the attention map and
 the head on the chosen query rows only, bit-identical to those rows of the full head.
 
-Not built (NotImplementedError): the training forward and the mask losses, vanilla DETRSegm,
-masks with two_stage, PostProcessPanoptic.  Reference defect: DETRSegmBase.forward(samples,
-targets) drops `prev_features`, so the reference tracker's three-argument call (tracker.py:309) is
-a TypeError with a masks model; here forward(samples, targets=None, prev_features=None) passes it on.
+Mask training (opt-in: `mask_training = True`, set by kinet_amd.train.build_mask_training; a model
+from build_model raises under autograd as before).  Off the fast path the detector runs
+_forward_reference (for the tracking class the two-pass forward; the head reads the last,
+current-frame pass) and `pred_masks` comes from ONE autograd Function over (hs[-1], the memory
+level's rows, the level-1 input projection, the three FPN features, the head's parameters):
+  * forward: the inference head above, in f32, over all B*Q rows in chunks, nothing kept but the inputs;
+  * backward: loss_masks reads the matcher's matched rows only, mask losses are skipped for the aux
+    outputs and rows never mix (GroupNorm statistics are per row), so the gradient of an unmatched
+    row is exactly zero: the rows whose incoming gradient is not all zero are found (ONE host sync
+    per step, next to the matcher's), and per frame the differentiable head -- kinet_amd.autograd
+    Functions only: linear, segm_attention, conv_nhwc (lay1 as its frame part and its 8-channel
+    part through weight slices), group_norm_nhwc, segm_relu_up_add, segm_out_conv -- is recomputed
+    on those rows alone and back-propagated.  Differentiating all B*Q rows would materialise
+    im2col for every row (about 40 GB for lay5 at 600 rows of 200 x 334).
+So the loss VALUE comes from the inference kernels' logits and the GRADIENT from the recomputed
+activations: two f32 evaluations of the same function whose roundings differ (fused GroupNorm vs
+its own Function, the convolutions' epilogues).  tests/test_segm_train_gpu.py holds both to the
+reference's losses and gradients.
+
+Not built (NotImplementedError): vanilla DETRSegm, masks with two_stage, PostProcessPanoptic.
+Reference defect: DETRSegmBase.forward(samples, targets) drops `prev_features`, so the reference
+tracker's three-argument call (tracker.py:309) is a TypeError with a masks model; here
+forward(samples, targets=None, prev_features=None) passes it on.
 """
 import torch
 from torch import nn
 
+from kinet_amd import autograd as A
 from kinet_amd import kernels as K
 from kinet_amd.models.deformable_detr import DeformableDETR
 from kinet_amd.models.deformable_transformer import fast_path
@@ -66,6 +86,13 @@ class MHAttentionMap(nn.Module):
         qp = K.linear(q.reshape(B * Q, d), self.q_linear.weight, self.q_linear.bias)
         kp = K.linear(k.reshape(-1, d), self.k_linear.weight, self.k_linear.bias)
         return K.segm_attention(qp, kp.view(B, -1, self.hidden_dim), mask, Q, self.num_heads)
+
+    def forward_autograd(self, q, k, mask=None):
+        """forward on kinet_amd.autograd Functions (f32, differentiable): q (B, Q, d) ... -> (B*Q, h*w, heads)."""
+        B, Q, d = q.shape
+        qp = A.linear(q.reshape(B * Q, d), self.q_linear.weight, self.q_linear.bias)
+        kp = A.linear(k.reshape(-1, d), self.k_linear.weight, self.k_linear.bias)
+        return A.segm_attention(qp, kp.view(B, -1, self.hidden_dim), mask, Q, self.num_heads)
 
 
 class MaskHeadSmallConv(nn.Module):
@@ -134,6 +161,37 @@ class MaskHeadSmallConv(nn.Module):
         x = self._gn(x, self.gn5)
         return K.segm_out_conv(x, K.segm_out_weights(self.out_lay.weight), K.f32(self.out_lay.bias), out=out)
 
+    def forward_autograd(self, src, att, fpns, Q):
+        """forward on kinet_amd.autograd Functions (f32, differentiable w.r.t. every input and
+        parameter), all rows in one pass: the training head's recompute on the matched rows."""
+        d = self.dim - att.shape[3]
+        n, h, w, _ = att.shape
+
+        def gn(x, mod):
+            r, hh, ww, C = x.shape
+            return A.group_norm_nhwc(x.reshape(r, hh * ww, C), mod).view(r, hh, ww, C)
+
+        def conv(x, mod):
+            return A.conv_nhwc(x, mod.weight, mod.bias, 1, 1)
+        adapted = []
+        for ad, f in zip((self.adapter1, self.adapter2, self.adapter3), fpns):
+            B, fh, fw, C = f.shape
+            adapted.append(A.linear(f.reshape(B * fh * fw, C), ad.weight.view(ad.out_channels, C), ad.bias)
+                           .view(B, fh, fw, -1))
+        frame = A.conv_nhwc(src, self.lay1.weight[:, :d], self.lay1.bias, 1, 1)        # (B, h, w, dim)
+        x = A.conv_nhwc(att, self.lay1.weight[:, d:], None, 1, 1)
+        x = (x.view(-1, Q, h, w, self.dim) + frame.unsqueeze(1)).view(n, h, w, self.dim)
+        x = A.segm_relu_up_add(gn(x, self.gn1))
+        x = conv(x, self.lay2)
+        x = A.segm_relu_up_add(gn(x, self.gn2), adapted[0], 0, Q)
+        x = conv(x, self.lay3)
+        x = A.segm_relu_up_add(gn(x, self.gn3), adapted[1], 0, Q)
+        x = conv(x, self.lay4)
+        x = A.segm_relu_up_add(gn(x, self.gn4), adapted[2], 0, Q)
+        x = conv(x, self.lay5)
+        x = A.segm_relu_up_add(gn(x, self.gn5))
+        return A.segm_out_conv(x, self.out_lay.weight, self.out_lay.bias)
+
     def forward(self, src, att, fpns, Q, chunk=None):
         """src (B, h, w, d) NHWC, att (B*Q, h, w, heads), fpns NHWC backbone features [layer3, layer2,
         layer1] -> (B*Q, H/4, W/4) f32 logits."""
@@ -160,6 +218,77 @@ class MaskHeadSmallConv(nn.Module):
         return out
 
 
+class _MaskHeadTrain(torch.autograd.Function):
+    """pred_masks of the training forward (module docstring): the inference head over all rows
+    forward, the differentiable head recomputed on the rows with a non-zero incoming gradient
+    backward.  Inputs after (model, mask): hs (B, Q, d), k_rows (B, h*w, d), src (B, h, w, d), the
+    three NHWC FPN features, then the head's parameters (so that autograd routes their gradients)."""
+
+    N_IN = 6
+
+    @staticmethod
+    def forward(ctx, model, mask, *tensors):
+        inputs = [t.detach() for t in tensors[:_MaskHeadTrain.N_IN]]
+        hs, k_rows, src = inputs[:3]
+        fpns = [f.contiguous() for f in inputs[3:]]
+        B, Q, d = hs.shape
+        h, w = src.shape[1:3]
+        att_mod, head = model.bbox_attention, model.mask_head
+        qp = K.linear(hs.reshape(B * Q, d), att_mod.q_linear.weight, att_mod.q_linear.bias)
+        kp = K.linear(k_rows.reshape(-1, d), att_mod.k_linear.weight, att_mod.k_linear.bias)
+        att = K.segm_attention(qp, kp.view(B, -1, att_mod.hidden_dim), mask, Q, att_mod.num_heads)
+        seg = head.run(att.view(B * Q, h, w, -1), head.frame_part(src), head.adapters(fpns), Q, model.mask_query_chunk)
+        ctx.save_for_backward(*inputs)
+        ctx.model, ctx.mask = model, mask
+        ctx.params = tensors[_MaskHeadTrain.N_IN:]
+        return seg.view(B, Q, seg.shape[-2], seg.shape[-1])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dseg):
+        model, mask, params = ctx.model, ctx.mask, ctx.params
+        inputs = ctx.saved_tensors
+        n_in = _MaskHeadTrain.N_IN
+        B, Q = dseg.shape[:2]
+        dseg = dseg.contiguous().float()
+        if model.mask_train_all_rows:
+            rows = [list(range(Q))] * B
+        else:
+            # the one host sync of the head's backward: which rows carry a gradient at all
+            live = (dseg.flatten(2) != 0).any(2).tolist()
+            rows = [[q for q in range(Q) if live[b][q]] for b in range(B)]
+        model.last_mask_rows = rows
+        need_in = ctx.needs_input_grad[2:2 + n_in]
+        need_p = ctx.needs_input_grad[2 + n_in:]
+        g_in = [None] * n_in
+        g_p = [None] * len(params)
+        for b, idx in enumerate(rows):
+            if not idx:
+                continue
+            idx_t = torch.tensor(idx, dtype=torch.int64, device=dseg.device)
+            leaves = [inputs[0][b].index_select(0, idx_t).unsqueeze(0)] + [t[b:b + 1] for t in inputs[1:]]
+            leaves = [t.detach().requires_grad_(bool(nd)) for t, nd in zip(leaves, need_in)]
+            with torch.enable_grad():
+                out = model._mask_rows_autograd(leaves[0], leaves[1], mask[b:b + 1], leaves[2], leaves[3:])
+            wanted = [(g_in, i, t) for i, (t, nd) in enumerate(zip(leaves, need_in)) if nd]
+            wanted += [(g_p, i, p) for i, (p, nd) in enumerate(zip(params, need_p)) if nd]
+            grads = torch.autograd.grad(out, [t for _, _, t in wanted], dseg[b].index_select(0, idx_t),
+                                        allow_unused=True)
+            for (store, i, _), g in zip(wanted, grads):
+                if g is None:
+                    continue
+                if store is g_in:
+                    if g_in[i] is None:
+                        g_in[i] = torch.zeros_like(inputs[i])
+                    if i == 0:
+                        g_in[0][b].index_copy_(0, idx_t, g[0])
+                    else:
+                        g_in[i][b:b + 1] = g
+                else:       # the frames in ascending order
+                    g_p[i] = g if g_p[i] is None else g_p[i] + g
+        return (None, None) + tuple(g_in) + tuple(g_p)
+
+
 class DETRSegmBase(nn.Module):
     def __init__(self, freeze_detr=False):
         if freeze_detr:
@@ -179,16 +308,55 @@ class DETRSegmBase(nn.Module):
         self.last_attention = None
         self.defer_masks = False        # True: forward returns no 'pred_masks'; mask_logits(rows) runs the head
         self._mask_ctx = None           # the last deferred forward's operands, valid until the next forward
+        self.mask_training = False      # True (train.build_mask_training): off the fast path, run the training forward
+        self.mask_train_all_rows = False   # diagnostic: back-propagate the head over all B*Q rows, not the live ones
+        self.last_mask_rows = None      # per frame, the query rows the last head backward ran on
 
     @property
     def fpn_channels(self):
         """detr.py:61-64."""
         return self.backbone.num_channels[:3][::-1]
 
+    def _mask_rows_autograd(self, hs_rows, k_rows, mask, src, fpns):
+        """The differentiable head for the rows hs_rows (1, n, d) of ONE frame (k_rows, mask, src and fpns
+        are that frame's, batch 1) -> (n, H/4, W/4) logits."""
+        n = hs_rows.shape[1]
+        h, w = src.shape[1:3]
+        att = self.bbox_attention.forward_autograd(hs_rows, k_rows, mask)
+        return self.mask_head.forward_autograd(src, att.view(n, h, w, -1), fpns, n)
+
+    def _forward_train(self, samples, targets, prev_features):
+        """The training forward (module docstring): detector on _forward_reference, pred_masks from
+        _MaskHeadTrain.  One host sync per step in the head's backward (the rows that carry a gradient)."""
+        self._segm_want = True
+        try:
+            out, targets, features, memory, hs = super().forward(samples, targets, prev_features)
+            ctx = self._segm_ctx
+        finally:
+            self._segm_want = False
+            self._segm_ctx = None
+        # detr_segmentation.py:44-53; src = input_proj[-3](features[-2]) is the tensor the transformer
+        # read (the reference computes it a second time: the same values, the same gradient sum)
+        src = ctx['src_nchw'].permute(0, 2, 3, 1)
+        mask = ctx['mask'].flatten(1)
+        fpns = [features[i].tensors.permute(0, 2, 3, 1) for i in (-2, -3, -4)]
+        memory = memory[-3]
+        if tuple(memory.shape[-2:]) != tuple(src.shape[1:3]) or mask.shape[1] != src.shape[1] * src.shape[2]:
+            raise RuntimeError('segmentation head: memory level and layer-3 feature differ in size')
+        k_rows = memory.flatten(2).permute(0, 2, 1)
+        params = list(self.bbox_attention.parameters()) + list(self.mask_head.parameters())
+        self._mask_ctx = None
+        out['pred_masks'] = _MaskHeadTrain.apply(self, mask, hs[-1].float(), k_rows.float(), src.float(),
+                                                 *[f.float() for f in fpns], *params)
+        return out, targets, features, memory, hs
+
     def forward(self, samples, targets: list = None, prev_features=None):
         if not fast_path(self):
+            if self.mask_training:
+                return self._forward_train(samples, targets, prev_features)
             raise NotImplementedError('DeformableDETRSegm runs the inference path only (eval mode under '
-                                      'torch.no_grad()); its training forward and the mask / dice losses are not built')
+                                      'torch.no_grad()) unless mask_training is set: '
+                                      'kinet_amd.train.build_mask_training builds the model and criterion that train')
         self._segm_want = True
         try:
             out, targets, features, memory, hs = super().forward(samples, targets, prev_features)

@@ -28,7 +28,8 @@ def match_name_keywords(n, name_keywords):
 
 
 def build_optimizer(model, args):
-    """train.py:95-120: base lr, backbone lr, linear-projection lr multiplier; AdamW."""
+    """train.py:95-120: base lr, backbone lr, linear-projection lr multiplier; AdamW.  Frozen
+    parameters (freeze_detr of the masks configs) are left out of every group."""
     m = model.module if hasattr(model, 'module') else model
     lp = list(args.lr_linear_proj_names)
     bb = list(args.lr_backbone_names)
@@ -122,6 +123,39 @@ def synthetic_mot_batch(batch, height, width, device, generator, num_boxes=(10, 
         samples.append(img.to(device))
         targets.append(cur)
     return nested_tensor_from_tensor_list(samples), targets
+
+
+def synthetic_mask_batch(batch, height, width, device=None, generator=None, num_boxes=(10, 30), track_overlap=0.8):
+    """synthetic_mot_batch plus `masks` per target: uint8 (n_i, height, width), one filled ellipse
+    inscribed in each box (pi/4 of the box's area where the box lies inside the image)."""
+    if device is None:
+        device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
+    if generator is None:
+        generator = torch.Generator().manual_seed(0)
+    samples, targets = synthetic_mot_batch(batch, height, width, device, generator, num_boxes, track_overlap)
+    ys = torch.arange(height, dtype=torch.float32, device=device).view(1, -1, 1) + 0.5
+    xs = torch.arange(width, dtype=torch.float32, device=device).view(1, 1, -1) + 0.5
+    for t in targets:
+        cx, cy, bw, bh = (t['boxes'] * t['boxes'].new_tensor([width, height, width, height])).unbind(-1)
+        r = ((xs - cx.view(-1, 1, 1)) / (bw.view(-1, 1, 1) / 2)) ** 2 + ((ys - cy.view(-1, 1, 1)) / (bh.view(-1, 1, 1) / 2)) ** 2
+        t['masks'] = (r <= 1).to(torch.uint8)
+    return samples, targets
+
+
+def build_mask_training(args):
+    """(model, criterion, postprocessors) that TRAIN the mask head -- the entry for both masks configs,
+    cfgs/train_coco_person_masks.yaml (freeze_detr: only the head's parameters require grad) and
+    cfgs/train_mots20.yaml (detector unfrozen): build_model's masks model with `mask_training` set and
+    the criterion rebuilt with the mask / dice losses (models/__init__.py:127-146).  build_model itself
+    stays inference-only for masks."""
+    from kinet_amd.models import NUM_CLASSES, build_model
+    from kinet_amd.models.criterion import build_criterion
+    if not getattr(args, 'masks', False):
+        raise ValueError('build_mask_training needs a masks config (masks: true)')
+    model, criterion, postprocessors = build_model(args)
+    model.mask_training = True
+    criterion = build_criterion(args, NUM_CLASSES[args.dataset], criterion.matcher, mask_losses=True)
+    return model, criterion, postprocessors
 
 
 def setup_ddp(model, device, find_unused_parameters=True):
