@@ -111,6 +111,12 @@ _SIGS = {
     'kinet_two_stage_queries': [P, P, P, P, P, I, I, I, I, P],
     'kinet_two_stage_fill_rows': [P, P, P, I64, I, I, P],
     'kinet_two_stage_boxes': [P, P, P, P, I64, P],
+    'kinet_match_cost_focal': [P, P, P, P, P, P, P, I, I, I, I, F, F, F, F, F, P],
+    'kinet_focal_set_loss_workspace': [I64, I],
+    'kinet_focal_set_loss': [P, P, P, P, I64, I, I, F, F, F, P, P],
+    'kinet_focal_set_loss_backward': [P, P, P, P, P, I64, I, I, F, F, F, P],
+    'kinet_two_stage_mask_rows': [P, P, P, I64, I, P],
+    'kinet_two_stage_boxes_backward': [P, P, P, P, I64, P],
     'kinet_segm_attention': [P, P, P, P, I, I, I, I, I, F, I, P],
     'kinet_segm_lay1': [P, P, P, P] + [I] * 9 + [P],
     'kinet_segm_gn_workspace': [I, I, I],
@@ -138,6 +144,7 @@ _RESTYPES = {'kinet_last_error': ctypes.c_char_p, 'kinet_version': ctypes.c_char
              'kinet_dropout_add_layernorm_backward_workspace': ctypes.c_int64,
              'kinet_groupnorm_backward_workspace': ctypes.c_int64,
              'kinet_mha_backward_workspace': ctypes.c_int64,
+             'kinet_focal_set_loss_workspace': ctypes.c_int64,
              'kinet_segm_mask_loss_workspace': ctypes.c_long, 'kinet_segm_attention_backward_workspace': ctypes.c_long,
              'kinet_segm_out_conv_backward_workspace': ctypes.c_long}
 

@@ -25,6 +25,9 @@ sigmoid / masked_fill glue of the heads.
     segm_relu_up_add(x, f, row0, Q, size)   the mask head's ReLU + nearest upsample + FPN add
     segm_out_conv(x, weight, bias)          the mask head's 3x3 convolution to one channel
     segm_mask_loss(logits, target, n_boxes) bilinear upsample + sigmoid focal + dice losses, fused
+    two_stage_mask_rows(x, keep)            the proposal stage's zeroing of invalid memory rows
+    two_stage_boxes(tmp, proposals)         coord_unact = tmp + proposals and its sigmoid
+    focal_set_loss(logits, rows, cls, n)    sigmoid focal loss of a set with sparse positives, fused
 
 Weight gradients are reductions over the row (pixel / token) dimension (kinet_gemm_tn,
 split-K with a fixed-order finalize), input gradients are GEMMs against the transposed
@@ -404,6 +407,79 @@ class _InverseSigmoid(Function):
 def inverse_sigmoid(x, eps=1e-5):
     """util/misc.py:609-613 on f32 device tensors, one kernel each way."""
     return _InverseSigmoid.apply(x, float(eps))
+
+
+# ------------------------------------- two-stage proposal stage and its loss (csrc/criterion.hip)
+class _TwoStageMaskRows(Function):
+    @staticmethod
+    def forward(ctx, x, keep):
+        _f32(x)
+        ctx.save_for_backward(keep)
+        return K.two_stage_mask_rows(x, keep)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        keep, = ctx.saved_tensors
+        return K.two_stage_mask_rows(dy.float(), keep), None
+
+
+def two_stage_mask_rows(x, keep):
+    """x (..., d) with the rows keep == 0 zeroed (deformable_transformer.py:118-121); the gradient of a
+    zeroed row is zero.  One kernel each way."""
+    return _TwoStageMaskRows.apply(x, keep)
+
+
+class _TwoStageBoxes(Function):
+    @staticmethod
+    def forward(ctx, tmp, proposals):
+        _f32(tmp)
+        unact, boxes = K.two_stage_boxes(tmp, proposals)
+        ctx.set_materialize_grads(False)    # an output nothing differentiates hands None, not zeros
+        ctx.save_for_backward(boxes)
+        return unact, boxes
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_unact, d_boxes):
+        boxes, = ctx.saved_tensors
+        if d_unact is None and d_boxes is None:
+            return None, None
+        return K.two_stage_boxes_backward(d_boxes, d_unact, boxes), None
+
+
+def two_stage_boxes(tmp, proposals):
+    """(coord_unact = tmp + proposals, boxes = sigmoid(coord_unact)) (deformable_transformer.py:185,
+    deformable_detr.py:258), differentiable w.r.t. tmp; the rows of +inf proposals (boxes exactly 1) get a
+    gradient of exactly 0."""
+    return _TwoStageBoxes.apply(tmp, proposals)
+
+
+class _FocalSetLoss(Function):
+    @staticmethod
+    def forward(ctx, logits, pos_rows, pos_cls, num_boxes, alpha, gamma):
+        _f32(logits)
+        shape = logits.shape
+        l2 = logits.reshape(-1, shape[-1]).contiguous()
+        ctx.save_for_backward(l2, pos_rows, pos_cls)
+        ctx.conf = (shape, num_boxes, alpha, gamma)
+        return K.focal_set_loss(l2, pos_rows, pos_cls, num_boxes, alpha, gamma)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dloss):
+        l2, pos_rows, pos_cls = ctx.saved_tensors
+        shape, num_boxes, alpha, gamma = ctx.conf
+        d = K.focal_set_loss_backward(l2, pos_rows, pos_cls, dloss.reshape(1).float().contiguous(), num_boxes, alpha,
+                                      gamma)
+        return d.view(shape), None, None, None, None, None
+
+
+def focal_set_loss(logits, pos_rows, pos_cls, num_boxes, alpha=0.25, gamma=2.0):
+    """The focal classification loss of a prediction set (detr.py:645-703: loss_ce of loss_labels_focal)
+    with the positives given as (flattened row, class) pairs: logits (..., C) f32 -> 0-d loss, one fused
+    kernel each way, no one-hot."""
+    return _FocalSetLoss.apply(logits, pos_rows, pos_cls, float(num_boxes), float(alpha), float(gamma))
 
 
 # ------------------------------------------------- mask head and mask losses (csrc/segm_train.hip)

@@ -994,6 +994,103 @@ def two_stage_boxes(tmp, proposals):
     return unact, boxes
 
 
+def two_stage_boxes_backward(d_boxes, d_coord_unact, boxes):
+    """d_tmp of two_stage_boxes = d_boxes * b (1 - b) + d_coord_unact (either gradient may be None), all
+    (..., 4) f32; exactly 0 from the d_boxes term where b == 1 (the +inf proposals)."""
+    N.require_gpu(d_boxes, d_coord_unact, boxes)
+    if d_boxes is None and d_coord_unact is None:
+        raise RuntimeError('two_stage_boxes_backward: both input gradients are None')
+    b = boxes.contiguous()
+    if b.dtype != torch.float32 or b.shape[-1] != 4:
+        raise RuntimeError('two_stage_boxes_backward: boxes must be f32 (..., 4)')
+    db = None if d_boxes is None else d_boxes.float().contiguous()
+    du = None if d_coord_unact is None else d_coord_unact.float().contiguous()
+    if any(t is not None and t.shape != b.shape for t in (db, du)):
+        raise RuntimeError('two_stage_boxes_backward: the gradients must have the boxes\' shape')
+    out = torch.empty_like(b)
+    N.call('kinet_two_stage_boxes_backward', N.ptr(db), N.ptr(du), N.ptr(b), N.ptr(out), b.numel() // 4,
+           N.stream(b.device))
+    return out
+
+
+def two_stage_mask_rows(x, keep):
+    """y[r] = x[r] where keep[r] else 0 (exactly, whatever the dropped row holds): x (..., d) f32, keep one
+    uint8 per row.  Applied to a gradient it is its own backward."""
+    N.require_gpu(x, keep)
+    d = x.shape[-1]
+    if x.dtype != torch.float32 or keep.dtype != torch.uint8 or keep.numel() * d != x.numel():
+        raise RuntimeError('two_stage_mask_rows: x must be f32 (..., d) and keep uint8 with one byte per row')
+    xc, kc = x.contiguous(), keep.contiguous()
+    y = torch.empty_like(xc)
+    N.call('kinet_two_stage_mask_rows', N.ptr(xc), N.ptr(kc), N.ptr(y), kc.numel(), d, N.stream(x.device),
+           work={'family': 'two_stage', 'bytes': 8 * xc.numel()})
+    return y
+
+
+# --------------------------------------------------- criterion kernels (csrc/criterion.hip)
+def match_cost_focal(logits, boxes, tgt_labels, tgt_boxes, tgt_start, w_class, w_bbox, w_giou, alpha=0.25,
+                     gamma=2.0, want_check=True):
+    """The block-diagonal focal matcher cost (kinet_match_cost_focal): logits (B, Q, C) f32, boxes (B, Q, 4)
+    f32 cxcywh, tgt_labels (T) int64, tgt_boxes (T, 4) f32, tgt_start (B + 1) int32 on the device ->
+    (cost (Q, T) f32: column j against the Q predictions of the image that owns it; ok: a device bool
+    scalar, False when any box is degenerate (util/box_ops.py:44-45), or None)."""
+    N.require_gpu(logits, boxes, tgt_labels, tgt_boxes, tgt_start)
+    if logits.dtype != torch.float32 or boxes.dtype != torch.float32 or logits.dim() != 3 \
+            or tuple(boxes.shape) != tuple(logits.shape[:2]) + (4,):
+        raise RuntimeError(f'match_cost_focal: logits must be f32 (B, Q, C) and boxes f32 (B, Q, 4): got '
+                           f'{tuple(logits.shape)} {logits.dtype}, {tuple(boxes.shape)} {boxes.dtype}')
+    B, Q, C = logits.shape
+    T = tgt_labels.numel()
+    if tgt_labels.dtype != torch.int64 or tgt_boxes.dtype != torch.float32 or tuple(tgt_boxes.shape) != (T, 4) \
+            or tgt_start.dtype != torch.int32 or tgt_start.numel() != B + 1:
+        raise RuntimeError('match_cost_focal: tgt_labels int64 (T), tgt_boxes f32 (T, 4) and tgt_start int32 (B + 1) '
+                           'required')
+    lg, bx, tl, tb, ts = (t.contiguous() for t in (logits, boxes, tgt_labels, tgt_boxes, tgt_start))
+    cost = torch.empty((Q, T), dtype=torch.float32, device=logits.device)
+    ok = torch.ones((), dtype=torch.uint8, device=logits.device) if want_check else None
+    N.call('kinet_match_cost_focal', N.ptr(lg), N.ptr(bx), N.ptr(tl), N.ptr(tb), N.ptr(ts), N.ptr(cost), N.ptr(ok),
+           B, Q, C, T, float(w_class), float(w_bbox), float(w_giou), float(alpha), float(gamma),
+           N.stream(logits.device), work={'family': 'criterion', 'bytes': 4 * Q * T + 20 * B * Q})
+    return cost, (None if ok is None else ok.view(torch.bool))
+
+
+def _focal_set_args(logits, pos_rows, pos_cls):
+    N.require_gpu(logits, pos_rows, pos_cls)
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise RuntimeError(f'focal_set_loss: logits must be f32 (R, C): got {tuple(logits.shape)} {logits.dtype}')
+    if pos_rows.dtype != torch.int64 or pos_cls.dtype != torch.int64 or pos_rows.shape != pos_cls.shape \
+            or pos_rows.dim() != 1:
+        raise RuntimeError('focal_set_loss: pos_rows and pos_cls must be int64 vectors of one length')
+    return logits.contiguous(), pos_rows.contiguous(), pos_cls.contiguous()
+
+
+def focal_set_loss(logits, pos_rows, pos_cls, num_boxes, alpha=0.25, gamma=2.0):
+    """sum over (R, C) of the sigmoid focal loss against the sparse positives (pos_rows[i], pos_cls[i]),
+    divided by num_boxes (kinet_focal_set_loss) -> a 0-d f32 tensor; two runs are bit-identical."""
+    logits, pos_rows, pos_cls = _focal_set_args(logits, pos_rows, pos_cls)
+    R, C = logits.shape
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    ws = _ws(N.lib().kinet_focal_set_loss_workspace(R, C), logits.device)
+    N.call('kinet_focal_set_loss', N.ptr(logits), N.ptr(pos_rows), N.ptr(pos_cls), N.ptr(loss), R, C,
+           pos_rows.numel(), float(alpha), float(gamma), 1.0 / float(num_boxes), N.ptr(ws), N.stream(logits.device),
+           work={'family': 'criterion', 'bytes': 4 * logits.numel()})
+    return loss[0]
+
+
+def focal_set_loss_backward(logits, pos_rows, pos_cls, dloss, num_boxes, alpha=0.25, gamma=2.0):
+    """dloss * d focal_set_loss / d logits (kinet_focal_set_loss_backward): dloss one f32 on the device."""
+    logits, pos_rows, pos_cls = _focal_set_args(logits, pos_rows, pos_cls)
+    N.require_gpu(dloss)
+    if dloss.dtype != torch.float32 or dloss.numel() != 1:
+        raise RuntimeError('focal_set_loss_backward: dloss must be one f32')
+    R, C = logits.shape
+    dlogits = torch.empty_like(logits)
+    N.call('kinet_focal_set_loss_backward', N.ptr(logits), N.ptr(pos_rows), N.ptr(pos_cls), N.ptr(dloss.contiguous()),
+           N.ptr(dlogits), R, C, pos_rows.numel(), float(alpha), float(gamma), 1.0 / float(num_boxes),
+           N.stream(logits.device), work={'family': 'criterion', 'bytes': 8 * logits.numel()})
+    return dlogits
+
+
 # ------------------------------------------------------------------------------ MSDA
 _tile_orders = {}
 

@@ -9,8 +9,10 @@ src/trackformer/models/__init__.py:16-125.
 families are built: the deformable image branch (:51-71, the hot path), the KineT kinematic
 branch (`args.kine`, :72-107, kinet_amd/models/kinet.py) and vanilla DETR (:111-125, the
 reference's default `deformable: false`; kinet_amd/models/detr.py, inference only).  The
-deformable branch also builds the two-stage variant (`two_stage: true`, inference only; the
-proposal stage runs on csrc/two_stage.hip) and, with `masks: true` (cfgs/train_coco_person_masks.yaml,
+deformable branch also builds the two-stage variant (`two_stage: true`; the proposal stage runs on
+csrc/two_stage.hip; what build_model returns is the inference model, and training it is opt-in:
+kinet_amd.train.build_two_stage_training(args) returns the same model with `two_stage_training` set
+and the criterion rebuilt with build_criterion(..., enc_losses=True), csrc/criterion.hip) and, with `masks: true` (cfgs/train_coco_person_masks.yaml,
 cfgs/train_mots20.yaml), DeformableDETRSegm / DeformableDETRSegmTracking plus the 'segm'
 postprocessor (:63-69, :165-166; kinet_amd/models/segmentation.py on csrc/segm.hip:
 `out['pred_masks']`).  What build_model returns for masks is the inference model: under autograd

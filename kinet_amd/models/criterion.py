@@ -14,6 +14,13 @@ is the exception: the bilinear upsampling of the matched rows' logits to the tar
 sigmoid focal loss and the dice loss are ONE kernel each way (autograd.segm_mask_loss on
 csrc/segm_train.hip), the full-resolution map is never materialised.  It is skipped for the
 auxiliary outputs (:859) and, like every kernel call, raises on CPU tensors.
+
+The two-stage `enc_outputs` set (:870-886, opt-in: build_criterion(..., enc_losses=True),
+kinet_amd.train.build_two_stage_training) is the other exception: it is the one set with a row per
+encoder token (22 223 per 800x1333 frame against 300 queries), so on the GPU with the focal loss its
+matcher cost is ONE kernel (HungarianMatcher.cost_block_diagonal) and its loss_ce_enc one kernel each
+way (autograd.focal_set_loss, csrc/criterion.hip) -- no (batch * tokens, targets) intermediates, no
+one-hot.  FUSED_ENC_COST / FUSED_ENC_LOSS switch each back to the torch composition (tests, A/B).
 """
 import torch
 import torch.distributed as dist
@@ -48,6 +55,11 @@ def accuracy(output, target, topk=(1,)):
     return [correct[:k].reshape(-1).float().sum(0).mul_(100.0 / batch_size) for k in topk]
 
 
+# the enc_outputs set on the kernels of csrc/criterion.hip (module doc); False: the torch composition
+FUSED_ENC_COST = True
+FUSED_ENC_LOSS = True
+
+
 def _world_size():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
@@ -56,8 +68,9 @@ class SetCriterion(nn.Module):
     """detr.py:566-870."""
 
     def __init__(self, num_classes, matcher, weight_dict, eos_coef, losses, focal_loss, focal_alpha, focal_gamma,
-                 tracking, track_query_false_positive_eos_weight):
+                 tracking, track_query_false_positive_eos_weight, enc_losses=False):
         super().__init__()
+        self.enc_losses = enc_losses
         self.num_classes = num_classes
         self.matcher = matcher
         self.weight_dict = weight_dict
@@ -120,6 +133,18 @@ class SetCriterion(nn.Module):
             losses['class_error'] = 100 - accuracy(src_logits[idx], target_classes_o)[0]
         return losses
 
+    def loss_labels_focal_set(self, outputs, targets, indices, num_boxes):
+        """loss_labels_focal's loss_ce (no class_error: log=False) on the fused kernel: the positives go in as
+        (flattened row, class) pairs.  loss.mean(1).sum() / num_boxes * Q of :645-703 is the plain sum over
+        every (image, row, class) divided by num_boxes."""
+        from kinet_amd import autograd as A
+        src_logits = outputs['pred_logits']
+        batch_idx, src_idx = self._get_src_permutation_idx(indices)
+        pos_rows = batch_idx.to(src_logits.device) * src_logits.shape[1] + src_idx.to(src_logits.device)
+        pos_cls = torch.cat([t["labels"][J] for t, (_, J) in zip(targets, indices)]).to(src_logits.device)
+        return {'loss_ce': A.focal_set_loss(src_logits, pos_rows, pos_cls, num_boxes, self.focal_alpha,
+                                            self.focal_gamma)}
+
     @torch.no_grad()
     def loss_cardinality(self, outputs, targets, indices, num_boxes):
         """detr.py:705-717."""
@@ -179,19 +204,24 @@ class SetCriterion(nn.Module):
         dist.all_reduce(n)
         return torch.clamp(n / _world_size(), min=1).item()
 
-    def match(self, output_sets, targets):
+    def match(self, output_sets, targets, enc=None):
         """The matcher's indices for every output set, moved to the predictions' device in ONE
         non-blocking copy (the losses index device tensors with them; the reference indexes
-        with host tensors, one implicit copy per sample and loss)."""
+        with host tensors, one implicit copy per sample and loss).  enc: (enc_outputs, its class-0
+        targets) of a two-stage model; its indices come last, from the same host copy."""
         from kinet_amd.models.training import glue_timer, to_device
         with glue_timer():
-            return self._match(output_sets, targets, to_device)
+            return self._match(output_sets, targets, to_device, enc)
 
-    def _match(self, output_sets, targets, to_device):
+    def _enc_fused(self, enc_outputs, flag):
+        return flag and self.focal_loss and enc_outputs['pred_logits'].is_cuda
+
+    def _match(self, output_sets, targets, to_device, enc=None):
         if hasattr(self.matcher, 'match_many'):
-            host = self.matcher.match_many(output_sets, targets)
+            extra = None if enc is None else (enc[0], enc[1], self._enc_fused(enc[0], FUSED_ENC_COST))
+            host = self.matcher.match_many(output_sets, targets, extra=extra)
         else:
-            host = [self.matcher(o, targets) for o in output_sets]
+            host = [self.matcher(o, targets) for o in output_sets] + ([self.matcher(*enc)] if enc else [])
         device = output_sets[0]['pred_logits'].device
         flat = [t for per_set in host for pair in per_set for t in pair]
         if device.type != 'cuda' or not flat:
@@ -216,8 +246,14 @@ class SetCriterion(nn.Module):
     def forward(self, outputs, targets):
         self.deferred_checks = [] if self.defer_box_checks else None
         outputs_without_aux = {k: v for k, v in outputs.items() if k != 'aux_outputs'}
+        outputs_without_aux.pop('enc_outputs', None)
         aux = list(outputs.get('aux_outputs', []))
-        all_indices = self.match([outputs_without_aux] + aux, targets)
+        enc = bin_targets = None
+        if self.enc_losses and 'enc_outputs' in outputs:
+            # detr.py:870-875: the proposals are class-agnostic, matched against class-0 copies of the targets
+            enc = outputs['enc_outputs']
+            bin_targets = [dict(t, labels=torch.zeros_like(t['labels'])) for t in targets]
+        all_indices = self.match([outputs_without_aux] + aux, targets, None if enc is None else (enc, bin_targets))
         indices = all_indices[0]
         num_boxes = self.num_boxes(outputs, targets)
         losses = {}
@@ -231,13 +267,26 @@ class SetCriterion(nn.Module):
                 kwargs = {'log': False} if loss == 'labels' else {}
                 l_dict = self.get_loss(loss, aux_outputs, targets, indices, num_boxes, **kwargs)
                 losses.update({k + f'_{i}': v for k, v in l_dict.items()})
+        if enc is not None:
+            indices = all_indices[-1]
+            for loss in self.losses:
+                if loss == 'masks':
+                    continue
+                if loss == 'labels' and self._enc_fused(enc, FUSED_ENC_LOSS):
+                    l_dict = self.loss_labels_focal_set(enc, bin_targets, indices, num_boxes)
+                else:
+                    kwargs = {'log': False} if loss == 'labels' else {}
+                    l_dict = self.get_loss(loss, enc, bin_targets, indices, num_boxes, **kwargs)
+                losses.update({k + '_enc': v for k, v in l_dict.items()})
         return losses
 
 
-def build_criterion(args, num_classes, matcher, mask_losses=False):
-    """models/__init__.py:125-161 (no two-stage on this path).  mask_losses=True adds the reference's
-    `args.masks` branch (:131-133, :145-146): loss_mask / loss_dice weights (before the aux
-    expansion, so their `_i` keys exist as there) and the 'masks' loss; build_model leaves it False."""
+def build_criterion(args, num_classes, matcher, mask_losses=False, enc_losses=False):
+    """models/__init__.py:125-161.  mask_losses=True adds the reference's `args.masks` branch (:131-133,
+    :145-146): loss_mask / loss_dice weights (before the aux expansion, so their `_i` keys exist as
+    there) and the 'masks' loss.  enc_losses=True adds the `args.two_stage` branch (:140-141): the `_enc`
+    weights (inside the aux expansion, as there) and the criterion's enc_outputs set.  build_model leaves
+    both False."""
     weight_dict = {'loss_ce': args.cls_loss_coef, 'loss_bbox': args.bbox_loss_coef, 'loss_giou': args.giou_loss_coef}
     if mask_losses:
         weight_dict['loss_mask'] = args.mask_loss_coef
@@ -246,9 +295,12 @@ def build_criterion(args, num_classes, matcher, mask_losses=False):
         aux = {}
         for i in range(args.dec_layers - 1):
             aux.update({k + f'_{i}': v for k, v in weight_dict.items()})
+        if enc_losses:
+            aux.update({k + '_enc': v for k, v in weight_dict.items()})
         weight_dict.update(aux)
     return SetCriterion(num_classes, matcher=matcher, weight_dict=weight_dict, eos_coef=args.eos_coef,
                         losses=['labels', 'boxes', 'cardinality'] + (['masks'] if mask_losses else []),
                         focal_loss=args.focal_loss,
                         focal_alpha=args.focal_alpha, focal_gamma=args.focal_gamma, tracking=args.tracking,
-                        track_query_false_positive_eos_weight=args.track_query_false_positive_eos_weight)
+                        track_query_false_positive_eos_weight=args.track_query_false_positive_eos_weight,
+                        enc_losses=enc_losses)

@@ -17,6 +17,13 @@ With box refinement the per-layer boxes are exactly the decoder's refined refere
 (the head recomputes bbox_embed[l](hs[l]) + inverse_sigmoid(ref_l), deformable_detr.py:
 236-244, which IS the decoder's refinement of layer l, deformable_transformer.py:416-424),
 so the head reuses them instead of running the box MLPs twice.
+
+Training path (autograd enabled): `_forward_reference`, the reference's forward op for op in f32 on
+kinet_amd.autograd Functions.  A two-stage model takes it only with `two_stage_training` set
+(kinet_amd.train.build_two_stage_training): no query_embed is read, the proposal stage runs under
+autograd (DeformableTransformer._proposal_queries_train) and `out['enc_outputs']` carries the encoder
+class logits and boxes of every token for the criterion's `_enc` losses; without the flag a two-stage
+model raises in train mode.
 """
 import copy
 import math
@@ -135,6 +142,18 @@ class DeformableDETR(nn.Module):
     def hidden_dim(self):
         return self.transformer.d_model
 
+    @property
+    def two_stage_training(self):
+        """Opt-in of the two-stage training forward (kinet_amd.train.build_two_stage_training sets it);
+        the transformer's proposal stage reads the same flag."""
+        return self.transformer.two_stage_training
+
+    @two_stage_training.setter
+    def two_stage_training(self, on):
+        if on and not (self.two_stage and self.with_box_refine):
+            raise NotImplementedError('two-stage training needs two_stage and with_box_refine')
+        self.transformer.two_stage_training = bool(on)
+
     def set_compute_dtype(self, dtype):
         """torch.bfloat16 (perf) or torch.float32 (parity) for the HIP inference path."""
         if dtype not in (torch.float32, torch.bfloat16, torch.float16):
@@ -226,7 +245,7 @@ class DeformableDETR(nn.Module):
         if not isinstance(samples, NestedTensor):
             samples = nested_tensor_from_tensor_list(samples)
         if not fast_path(self):
-            if self.two_stage:
+            if self.two_stage and not self.two_stage_training:
                 raise NotImplementedError('two-stage Deformable DETR runs the inference path only (eval mode under '
                                           'torch.no_grad()); its training forward and the enc_outputs losses are '
                                           'not built')
@@ -380,8 +399,15 @@ class DeformableDETR(nn.Module):
         if self.multi_frame_attention:
             size_sets.append(getattr(prev_features[0], 'sizes', None))
         padded = None if any(z is None for z in size_sets) else any(len(set(z)) > 1 for z in size_sets)
-        hs, memory, init_reference, inter_references, _, _ = self.transformer(
-            src_list, mask_list, pos_list, self.query_embed.weight, targets, padded=padded)
+        enc_class = None
+        if self.two_stage:
+            # no query_embed is read (deformable_detr.py:223-224); the proposals' box head as in forward()
+            hs, memory, init_reference, inter_references, enc_class, _ = self.transformer(
+                src_list, mask_list, pos_list, None, targets, padded=padded,
+                proposal_bbox_embed=self.bbox_embed[self.transformer.decoder.num_layers])
+        else:
+            hs, memory, init_reference, inter_references, _, _ = self.transformer(
+                src_list, mask_list, pos_list, self.query_embed.weight, targets, padded=padded)
         if getattr(self, '_segm_want', False):
             # the mask head's training inputs (kinet_amd/models/segmentation.py): the current frame's
             # level-1 projection (the last frame's levels end the lists) and its padding mask
@@ -403,6 +429,11 @@ class DeformableDETR(nn.Module):
         out = {'pred_logits': outputs_class[-1], 'pred_boxes': outputs_coord[-1], 'hs_embed': hs[-1]}
         if self.aux_loss:
             out['aux_outputs'] = self._set_aux_loss(outputs_class, outputs_coord)
+        if self.two_stage:
+            # (:256-258; the sigmoid is two_stage_boxes' second output, differentiable through it)
+            out['enc_outputs'] = {'pred_logits': enc_class, 'pred_boxes': self.transformer.enc_outputs_coord}
+            # the module keeps the values only, not this step's graph
+            self.transformer.enc_outputs_coord = self.transformer.enc_outputs_coord.detach()
         B, _, c = memory.shape
         memory_slices, o = [], 0
         for s in src_list:

@@ -17,10 +17,12 @@ Two execution paths with identical arithmetic:
     probability dropout, ...; forward and backward HIP kernels) with MSDeformAttnFunction
     (HIP forward / backward) at the operator boundary; torch supplies only glue (dropout
     masks outside attention, adds, reshapes).
-Two-stage (`two_stage=True`, :52-56, :77-122, :180-194), inference path only: the encoder-output
-proposals, the per-frame top-k of the encoder class logits and the queries built from the selected
-boxes run on the kernels of csrc/two_stage.hip without a host sync (`_proposal_queries`); the
-last forward's selected token indices stay in `topk_proposals`.
+Two-stage (`two_stage=True`, :52-56, :77-122, :180-194): the encoder-output proposals, the per-frame
+top-k of the encoder class logits and the queries built from the selected boxes run on the kernels
+of csrc/two_stage.hip without a host sync (`_proposal_queries`); the last forward's selected token
+indices stay in `topk_proposals`.  Its training forward (`_proposal_queries_train`, the same lines
+op for op on autograd Functions; csrc/criterion.hip holds the row masking and the box sigmoid's
+backward) is opt-in: `two_stage_training`, set by kinet_amd.train.build_two_stage_training.
 Reference quirks kept on purpose: 2-d sampling offsets divided by
 (H, W) applied to (x, y); multi-frame memory concatenated [current, prev] while shapes,
 masks and valid ratios stay [prev, current].
@@ -448,7 +450,7 @@ class DeformableTransformer(nn.Module):
                                tok=slice(0, None), order=K.encoder_tile_order(geo['shapes'], device),
                                ref=DeformableTransformerEncoder.get_reference_points(geo['shapes'], valid_ratios,
                                                                                      device))]
-        if self.two_stage and fast_path(self):
+        if self.two_stage and (fast_path(self) or self.two_stage_training):
             # the encoder-output proposals and the rows they keep depend on shapes and masks only
             geo['proposals'], geo['keep'] = K.two_stage_proposals(geo['shapes'], geo['pad_mask'],
                                                                   valid_ratios.shape[0], device)
@@ -491,6 +493,30 @@ class DeformableTransformer(nn.Module):
         tgt = pos_trans_out[..., c:].contiguous()
         return query_pos, tgt, reference_points, enc_outputs_class, enc_outputs_coord_unact
 
+    two_stage_training = False   # opt-in: kinet_amd.train.build_two_stage_training
+
+    def _proposal_queries_train(self, memory, geo, proposal_bbox_embed=None):
+        """_proposal_queries under autograd, op for op with deformable_transformer.py:118-122 and
+        :180-194 in f32: the invalid rows' memory is zeroed and every row goes through enc_output and
+        enc_output_norm (their output on an invalid row depends on enc_output.bias and the norm's
+        parameters, and the enc_outputs focal loss differentiates it); the selected boxes are detached
+        (:190)."""
+        if proposal_bbox_embed is None:
+            proposal_bbox_embed = self.decoder.bbox_embed[self.decoder.num_layers]
+        c = self.d_model
+        nl = self.decoder.num_layers
+        output_memory = A.two_stage_mask_rows(memory, geo['keep'])
+        output_memory = A.layer_norm(A.linear_module(output_memory, self.enc_output), self.enc_output_norm)
+        enc_outputs_class = A.linear_module(output_memory, self.decoder.class_embed[nl])
+        tmp = proposal_bbox_embed(output_memory)
+        enc_outputs_coord_unact, self.enc_outputs_coord = A.two_stage_boxes(tmp, geo['proposals'])
+        self.topk_proposals = K.topk_rows(enc_outputs_class.detach()[..., 0], self.two_stage_num_proposals)
+        reference_points, pos = K.two_stage_queries(enc_outputs_coord_unact.detach(), self.topk_proposals,
+                                                    torch.float32)
+        pos_trans_out = A.layer_norm(A.linear_module(pos, self.pos_trans), self.pos_trans_norm)
+        query_pos, tgt = torch.split(pos_trans_out, c, dim=2)
+        return query_pos, tgt, reference_points, enc_outputs_class, enc_outputs_coord_unact
+
     def _query_inputs(self, query_embed, bs, dt):
         """(query_pos, tgt, reference_points) for `bs` frames without track queries, cached per
         parameter version (deformable_transformer.py:198-202)."""
@@ -511,7 +537,7 @@ class DeformableTransformer(nn.Module):
                      proposal_bbox_embed=None):
         """deformable_transformer.py:159-257 on flattened inputs."""
         assert self.two_stage or query_embed is not None
-        if self.two_stage and not fast_path(self):
+        if self.two_stage and not fast_path(self) and not self.two_stage_training:
             raise NotImplementedError('two-stage Deformable DETR runs the inference path only (eval mode under '
                                       'torch.no_grad()); its training forward and the enc_outputs losses are not built')
         pad = geo['pad_mask']
@@ -543,8 +569,9 @@ class DeformableTransformer(nn.Module):
         if self.two_stage:
             # the reference's two-stage branch builds the queries from the proposals alone (:180-194)
             tracking = False
+            proposal_queries = self._proposal_queries if fast_path(self) else self._proposal_queries_train
             query_embed_, tgt, reference_points, enc_outputs_class, enc_outputs_coord_unact = \
-                self._proposal_queries(memory, geo, proposal_bbox_embed)
+                proposal_queries(memory, geo, proposal_bbox_embed)
         elif fast_path(self) and not tracking:
             # inference without track queries: the object queries, their positional half and
             # the initial reference points depend only on parameters -> cached per parameter

@@ -3,7 +3,8 @@ build_matcher :685-712).
 
 The cost matrix (focal or softmax class cost, L1 box cost, -GIoU) is built batched on the
 device where the predictions live and crosses to the host in ONE copy (one for all of the
-criterion's final + auxiliary output sets: `match_many`); the linear sum
+criterion's final + auxiliary output sets, and the two-stage enc_outputs set, whose cost is the
+block-diagonal kernel of csrc/criterion.hip: `match_many`); the linear sum
 assignment stays on the host (scipy.optimize.linear_sum_assignment, as in the reference,
 matcher.py:198) -- the north_star keeps the matcher host-side.  Track queries are forced
 onto the targets whose track ids they carry and false-positive track queries are made
@@ -56,15 +57,44 @@ class HungarianMatcher(nn.Module):
         return c.view(batch_size, num_queries, -1)
 
     @torch.no_grad()
+    def cost_block_diagonal(self, outputs, targets, checks=None):
+        """The image-diagonal blocks of cost_matrix as one (num_queries, sum_targets) f32 matrix -- column
+        j holds the cost of the predictions of the image that owns target j -- from ONE kernel
+        (csrc/criterion.hip kinet_match_cost_focal): no (batch * queries, sum_targets) intermediate and
+        none of the off-diagonal blocks cost_matrix computes and match_many discards.  Focal class cost,
+        device tensors.  checks: a list that receives the kernel's degenerate-box flag (a device bool)."""
+        from kinet_amd import kernels as K
+        from kinet_amd.models.misc import host_to_device
+        if not self.focal_loss:
+            raise NotImplementedError('cost_block_diagonal: the fused cost is the focal class cost')
+        logits, boxes = outputs["pred_logits"].detach().float(), outputs["pred_boxes"].detach().float()
+        dev = logits.device
+        sizes = [len(v["boxes"]) for v in targets]
+        start = host_to_device(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32), torch.int32, dev)
+        tgt_ids = torch.cat([v["labels"] for v in targets]).to(dev).long()
+        tgt_bbox = torch.cat([v["boxes"] for v in targets]).to(dev).float()
+        cost, ok = K.match_cost_focal(logits, boxes, tgt_ids, tgt_bbox, start, self.cost_class, self.cost_bbox,
+                                      self.cost_giou, self.focal_alpha, self.focal_gamma,
+                                      want_check=checks is not None)
+        if checks is not None and tgt_ids.numel():
+            checks.append(ok)
+        return cost
+
+    @torch.no_grad()
     def forward(self, outputs, targets):
         return self.match_many([outputs], targets)[0]
 
     @torch.no_grad()
-    def match_many(self, outputs_list, targets):
+    def match_many(self, outputs_list, targets, extra=None):
         """Indices of several output sets against the same targets -- the criterion's final
         and auxiliary decoder outputs (detr.py:819-868 calls the matcher once per set) --
         with ONE device->host synchronisation for all their cost matrices and the track-query
-        masks / match ids (to_host), instead of one per set."""
+        masks / match ids (to_host), instead of one per set.
+
+        extra: (outputs, targets, fused) of one more set with its own row count and targets -- the
+        two-stage enc_outputs against the class-0 targets (detr.py:870-875) -- or None.  Its cost (the
+        block-diagonal kernel's when `fused`, else cost_matrix) and box flags cross to the host in the
+        same copy; its indices come last in the result.  No track queries are forced on it."""
         from kinet_amd.models.training import to_host
         sizes = [len(v["boxes"]) for v in targets]
         offsets = np.cumsum([0] + sizes[:-1])
@@ -81,8 +111,12 @@ class HungarianMatcher(nn.Module):
             costs = self.cost_matrix(both, targets, checks).view(S, bsz, nq, -1)
         else:
             costs = torch.stack([self.cost_matrix(o, targets, checks) for o in outputs_list])
+        e_cost = None
+        if extra is not None:
+            e_out, e_targets, e_fused = extra
+            e_cost = (self.cost_block_diagonal if e_fused else self.cost_matrix)(e_out, e_targets, checks)
         has_chk = bool(checks) and costs.is_cuda
-        extra = [torch.stack(checks)] if has_chk else []
+        extra = ([] if e_cost is None else [e_cost]) + ([torch.stack(checks)] if has_chk else [])
         if tq:
             masks = torch.stack([torch.stack([targets[i]['track_queries_fal_pos_mask'],
                                               targets[i]['track_queries_mask']]).to(costs.device) for i in tq])
@@ -92,6 +126,8 @@ class HungarianMatcher(nn.Module):
                       else torch.zeros(0, dtype=torch.long)]
         host = to_host(costs, *extra)
         costs = host[0]
+        if e_cost is not None:
+            e_cost, host = host[1], host[:1] + host[2:]
         if has_chk:
             assert bool(host[1].all()), 'degenerate boxes (util/box_ops.py:44-45)'
             host = host[:1] + host[2:]
@@ -115,6 +151,12 @@ class HungarianMatcher(nn.Module):
                 cost_matrix[i, :, cols] = np.inf
                 cost_matrix[i, rows, cols] = -1
             indices = [linear_sum_assignment(c[i]) for i, c in enumerate(cost_matrix.split(sizes, -1))]
+            result.append([(torch.as_tensor(i, dtype=torch.int64), torch.as_tensor(j, dtype=torch.int64))
+                           for i, j in indices])
+        if e_cost is not None:
+            blocks = e_cost.split([len(v["boxes"]) for v in e_targets], -1)
+            # fused: (Q, T) holds each image's own block in its columns; else (B, Q, T) as above
+            indices = [linear_sum_assignment(c if e_cost.dim() == 2 else c[i]) for i, c in enumerate(blocks)]
             result.append([(torch.as_tensor(i, dtype=torch.int64), torch.as_tensor(j, dtype=torch.int64))
                            for i, j in indices])
         return result

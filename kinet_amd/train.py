@@ -158,6 +158,28 @@ def build_mask_training(args):
     return model, criterion, postprocessors
 
 
+def build_two_stage_training(args):
+    """(model, criterion, postprocessors) that TRAIN two-stage Deformable DETR (`two_stage: true`):
+    build_model's two-stage model with `two_stage_training` set -- its train-mode forward runs the
+    proposal stage under autograd and returns out['enc_outputs'] -- and the criterion rebuilt with the
+    `_enc` weights and the enc_outputs set (models/__init__.py:140-141, detr.py:870-886; its matcher cost
+    and focal loss on csrc/criterion.hip).  build_model itself stays inference-only for two-stage.
+    Needs `with_box_refine`: without it the reference sets decoder.bbox_embed = None
+    (deformable_detr.py:108) and its own two-stage forward fails at deformable_transformer.py:185."""
+    from kinet_amd.models import NUM_CLASSES, build_model
+    from kinet_amd.models.criterion import build_criterion
+    if not getattr(args, 'two_stage', False):
+        raise ValueError('build_two_stage_training needs a two-stage config (two_stage: true)')
+    if not args.with_box_refine:
+        raise NotImplementedError('two-stage training needs with_box_refine: without box refinement the reference '
+                                  'itself cannot run its two-stage forward (decoder.bbox_embed is None, '
+                                  'deformable_detr.py:108, and deformable_transformer.py:185 indexes it)')
+    model, criterion, postprocessors = build_model(args)
+    model.two_stage_training = True
+    criterion = build_criterion(args, NUM_CLASSES[args.dataset], criterion.matcher, enc_losses=True)
+    return model, criterion, postprocessors
+
+
 def setup_ddp(model, device, find_unused_parameters=True):
     """train.py:84-91: DistributedDataParallel over the RCCL process group (env:// rendezvous).
     find_unused_parameters=True is the reference's setting (train.py:89-91); every parameter of
