@@ -111,11 +111,15 @@ int kinet_bottleneck_pair_ds(const void* X, int ldx, const void* X0, int ldx0, c
 /* Diagnostics and planning (host side, per calling thread; no reference counterpart).
  * kinet_ffn_set_debug: A/B and test knobs, the FfnDebug bits of csrc/ffn_plan.h; returns the
  * previous value.
+ * kinet_ffn_grid_cap: an upper bound on the grid of the four entry points' launches (0 = none,
+ * the default); returns the previous value.  Every kernel walks its row tiles by gridDim.x, so a
+ * bound only moves tiles between workgroups: same outputs bit for bit (tests reach the multi-tile
+ * walk at a few tiles with it).
  * kinet_ffn_launch_plan: the launch kinet_ffn_fused, kinet_attn_out_ffn_fused, kinet_bottleneck_pair
  * or kinet_bottleneck_pair_ds makes for a described problem on a device of `cus` compute units,
- * under the calling thread's debug bits and the kinet_set_solo_launch policy as a real call reads
- * them (csrc/ffn_plan.h; no GPU call).  problem: KINET_FFNP_FIELDS ints, plan_out: KINET_FFNPL_FIELDS
- * ints.  KINET_ERR_ARG with the entry point's message where it refuses D or DB (its other argument
+ * under the calling thread's debug bits, its kinet_ffn_grid_cap and the kinet_set_solo_launch
+ * policy as a real call reads them (csrc/ffn_plan.h; no GPU call).  problem: KINET_FFNP_FIELDS
+ * ints, plan_out: KINET_FFNPL_FIELDS ints.  KINET_ERR_ARG with the entry point's message where it refuses D or DB (its other argument
  * checks are not repeated here).  M = 0: grid 0, nothing would be launched.
  * kinet_ffn_last_kernel: KINET_FFNPL_KERNEL of the calling thread's last launch of these four entry
  * points (-1: none yet); kinet_ffn_kernel_name: the instantiation's name but for the element type
@@ -142,6 +146,7 @@ enum kinet_ffn_plan_field {
 enum kinet_ffn_pack_kind { KINET_FFN_PACK_FFN = 0, KINET_FFN_PACK_PAIR, KINET_FFN_PACK_DS, KINET_FFN_PACK_ATTN };
 
 int kinet_ffn_set_debug(int flags);
+int kinet_ffn_grid_cap(int max_wgs);
 int kinet_ffn_launch_plan(const int* problem, int cus, int* plan_out);
 int kinet_ffn_last_kernel(void);
 const char* kinet_ffn_kernel_name(int kernel);

@@ -57,6 +57,7 @@ _SIGS = {
     'kinet_gemm_splitk': [P, P, P] + [I] * 7 + [P, P, P, I, I, P, P, F, I, P, P, I, P],
     'kinet_ffn_pack': [P, P, P, I, I, I, P],
     'kinet_ffn_set_debug': [I],
+    'kinet_ffn_grid_cap': [I],
     'kinet_ffn_launch_plan': [P, I, P],
     'kinet_ffn_last_kernel': [],
     'kinet_ffn_kernel_name': [I],

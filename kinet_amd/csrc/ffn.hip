@@ -54,6 +54,7 @@ struct FfnArgs {
 };
 
 thread_local int ffn_debug = 0;    // test-only knobs (kinet_ffn_set_debug, FfnDebug), per calling thread
+thread_local int ffn_cap = 0;      // kinet_ffn_grid_cap (0 = no cap), per calling thread
 thread_local int ffn_last = -1;    // kFfnKernels index of the calling thread's last launch (kinet_ffn_last_kernel)
 
 // the table entry of an instantiation (ffn_plan.h): each kernel checks its tile and its LDS against it
@@ -1350,7 +1351,7 @@ void launch_kernel(const FfnPlan& pl, hipStream_t s, const Args& a, std::integer
 }
 
 FfnProblem ffn_problem(int kind, int M, int D, int F, int DB, int cus) {
-    return FfnProblem{kind, M, D, F, DB, ffn_debug, solo_launch(), cus};
+    return FfnProblem{kind, M, D, F, DB, ffn_debug, solo_launch(), cus, ffn_cap};
 }
 
 int refused(const FfnPlan& pl) {
@@ -1388,6 +1389,12 @@ using namespace kinet;
 extern "C" int kinet_ffn_set_debug(int flags) {
     const int old = ffn_debug;
     ffn_debug = flags;
+    return old;
+}
+
+extern "C" int kinet_ffn_grid_cap(int max_wgs) {
+    const int old = ffn_cap;
+    ffn_cap = max_wgs > 0 ? max_wgs : 0;
     return old;
 }
 

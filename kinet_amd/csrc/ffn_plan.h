@@ -169,6 +169,7 @@ struct FfnProblem {
     int dbg;       // FfnDebug bits of the calling thread
     bool solo;     // kinet_set_solo_launch: one batch in flight
     int cus;       // compute units of the device
+    int cap;       // kinet_ffn_grid_cap of the calling thread (0 = none)
 };
 struct FfnPlan {
     int kernel;    // index into kFfnKernels
@@ -286,6 +287,9 @@ inline bool ffn_plan(const FfnProblem& p, FfnPlan& pl) {
     const long long wgs = ffn_ceil_div(tiles, k.wg_tiles), cap = (long long)p.cus * k.wg_per_cu;
     pl.tiles = (int)tiles;
     pl.grid = (int)(wgs < cap ? wgs : cap);
+    // diagnostics: kinet_ffn_grid_cap bounds the grid -- every kernel walks its tiles by gridDim.x, so the
+    // bound only moves tiles between workgroups (tests reach the multi-tile walk at a few tiles)
+    if (p.cap > 0 && pl.grid > p.cap) pl.grid = p.cap;
     return true;
 }
 

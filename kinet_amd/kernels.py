@@ -349,6 +349,12 @@ def ffn_launch_plan(kind, M, D, F_=None, DB=None, cus=256):
     return plan
 
 
+def ffn_grid_cap(max_wgs):
+    """Bound the grid of the fused FFN / bottleneck-pair launches of the calling thread (0 = none;
+    kinet_ffn_grid_cap): same outputs bit for bit.  Returns the previous bound."""
+    return N.lib().kinet_ffn_grid_cap(int(max_wgs))
+
+
 def ffn_last_kernel():
     """Name of the kernel the calling thread's last ffn_fused / attn_out_ffn_fused / bottleneck_pair /
     bottleneck_pair_ds call launched (kinet_ffn_last_kernel), None before the first."""

@@ -1789,7 +1789,8 @@ FFN_MSG_PAIR_DB = 'bottleneck_pair: DB must be D, or 128 at D = 64 (got D=%d DB=
 FFN_MSG_DS_D = 'bottleneck_pair_ds: D must be 64 (got %d)'
 FFN_MSG_DS_DB = 'bottleneck_pair_ds: DB must be 64 (got %d)'
 
-# (kind, M, D, DB, debug bits, solo) -> (kernel, row tiles, grid), or the refusal's message
+# (kind, M, D, DB, debug bits, solo) -> (kernel, row tiles, grid), or the refusal's message; an eighth field is the
+# calling thread's kinet_ffn_grid_cap (none: 0)
 FFN_PLAN_CASES = [
     # kinet_ffn_fused: 4 waves x 16 rows below 16384 rows, whatever the knobs
     ('ffn', 1, 256, 256, 0, 0, (_F14 % 256, 1, 1)),
@@ -1857,6 +1858,24 @@ FFN_PLAN_CASES = [
     ('pair_ds', 1068800, 64, 64, 512, 0, (_DS2, 33400, 256)),
     ('pair_ds', 1000, 128, 128, 0, 0, FFN_MSG_DS_D % 128),
     ('pair_ds', 1000, 64, 128, 0, 0, FFN_MSG_DS_DB % 128),
+    # kinet_ffn_grid_cap: the grid is min(workgroups that cover the tiles, CUs x workgroups per CU, the cap); the
+    # kernel and the tiles do not move.  1389 tiles on 256 CUs under caps 100 and 300; 256 tiles under cap 1
+    ('ffn', 355568, 256, 256, 0, 0, (_RT2, 1389, 100), 100),
+    ('ffn', 355568, 256, 256, 0, 0, (_RT2, 1389, 256), 300),
+    ('ffn', 16383, 256, 256, 0, 0, (_F14 % 256, 256, 1), 1),
+    ('ffn', 16384, 288, 288, 0, 0, (_F24 % 288, 128, 127), 127),
+    ('attn_out_ffn', 5, 256, 256, 0, 0, (_PRE0, 1, 1), 4),
+    ('attn_out_ffn', 355568, 256, 256, 64, 0, (_PRE1, 1389, 255), 255),
+    # the solo rule looks at the CUs, not at the cap: 255 one-tile tiles still win, then the cap bounds them
+    ('pair', 32640, 128, 128, 0, 1, (_PAIR % (128, 1), 255, 16), 16),
+    # resident weights: 63 tiles in 8 workgroups of 8 waves (4 of 16 waves); the cap counts workgroups, not tiles
+    ('pair', 1000, 64, 64, 0, 0, (_B64, 63, 8), 8),
+    ('pair', 1000, 64, 64, 0, 0, (_B64, 63, 7), 7),
+    ('pair', 1068800, 64, 64, 0, 0, (_B64, 66800, 3), 3),
+    ('pair', 1000, 64, 128, 0, 0, (_B128, 63, 2), 2),
+    ('pair_ds', 1000, 64, 64, 512, 0, (_DS2, 32, 1), 1),
+    ('pair_ds', 1068800, 64, 64, 0, 0, (_DS1, 66800, 256), 257),
+    ('ffn', 16384, 128, 128, 0, 0, FFN_MSG_D % 128, 2),
 ]
 
 # packed-weight layout (ffn_pack_src): (kind, D, F, DB, packed index) -> (source matrix, row, column).  Index =
@@ -1896,3 +1915,366 @@ def ffn_pack_shapes(kind, D, F, DB):
     """Shapes of a pack kind's source matrices, in the pack call's argument order."""
     return {'ffn': [(F, D), (D, F)], 'attn_out_ffn': [(D, D), (F, D), (D, F)], 'pair': [(F, D), (DB, F)],
             'pair_ds': [(F, D), (F, D), (DB, F)]}[kind]
+
+
+# ----------------------------------------------------------------------------------------------
+# Direct tests of the fused FFN / bottleneck-pair kernels (csrc/ffn.hip; tests/test_ffn_direct_gpu.py).
+#
+# The table: (entry point, D, F, DB, M, debug bits, solo, kernel, rows per row tile, {grid cap: grid}),
+# written down from the rules of csrc/ffn_plan.h for 256 compute units; test_ffn_plan_cpu.py holds every
+# row, under every cap, against kinet_ffn_launch_plan.
+#   ring kernels the planner serves at any M: five row tiles, the last ragged (M = 5 rows - 5); cap 0 =
+#     one tile per workgroup, 1 = one workgroup walks all five, 2 = 3 / 2 tiles, 4 = one workgroup with
+#     two tiles beside three with one;
+#   the four kernels kinet_ffn_fused takes from 16384 rows: M = 16635 = 65 tiles of 256 rows or 130 of
+#     128, ragged; caps 0, 1, 3, tiles - 1;
+#   resident weights (a 16 rt-row tile per wave): M = rows (2 waves + 3) - 5 -> 2 waves + 3 tiles in 3
+#     workgroups, the last one with idle waves and a ragged tile; under cap 1 every wave walks two or
+#     three tiles (the refill of the residual registers), under cap 2 one or two.
+# F (FFN entry points): 32, 64, 160 = 1, 2, 5 hidden chunks (5: a multiple of neither ring depth), and
+# 2048 = FFN_MAX_F on the kernels that run at few rows; the pairs take F = 4 D only.
+# ----------------------------------------------------------------------------------------------
+FFN_BIG_ROWS = 16635
+_CAPS5 = {0: 5, 1: 1, 2: 2, 4: 4}
+_CAPS65, _CAPS130 = {0: 65, 1: 1, 3: 3, 64: 64}, {0: 130, 1: 1, 3: 3, 129: 129}
+_CAPS_RES = {0: 3, 1: 1, 2: 2}
+FFN_DIRECT_CASES = (
+    [('ffn', 256, F_, 256, 315, 0, 0, _F14 % 256, 64, _CAPS5) for F_ in (32, 64, 160, 2048)]
+    + [('ffn', 288, F_, 288, 315, 0, 0, _F14 % 288, 64, _CAPS5) for F_ in (32, 64, 160, 2048)]
+    + [('attn_out_ffn', 256, F_, 256, 1275, 0, 0, _PRE0, 256, _CAPS5) for F_ in (32, 64, 160, 2048)]
+    + [('attn_out_ffn', 256, F_, 256, 1275, 64, 0, _PRE1, 256, _CAPS5) for F_ in (32, 64, 160, 2048)]
+    + [('ffn', 256, F_, 256, FFN_BIG_ROWS, 0, 0, _RT2, 256, _CAPS65) for F_ in (32, 64, 160)]
+    + [('ffn', 256, F_, 256, FFN_BIG_ROWS, 2, 0, _F24 % 256, 128, _CAPS130) for F_ in (32, 64, 160)]
+    + [('ffn', 256, F_, 256, FFN_BIG_ROWS, 8, 0, _F18 % 256, 128, _CAPS130) for F_ in (32, 64, 160)]
+    + [('ffn', 288, F_, 288, FFN_BIG_ROWS, 0, 0, _F24 % 288, 128, _CAPS130) for F_ in (32, 64, 160)]
+    + [('pair', 64, 256, 64, 1275, 16, 0, _PAIR % (64, 2), 256, _CAPS5),
+       ('pair', 128, 512, 128, 635, 128, 0, _PAIR % (128, 1), 128, _CAPS5),
+       ('pair', 256, 1024, 256, 635, 128, 0, _PAIR % (256, 1), 128, _CAPS5),
+       ('pair', 128, 512, 128, 1275, 256, 0, _PAIR % (128, 2), 256, _CAPS5),
+       ('pair', 256, 1024, 256, 1275, 256, 0, _PAIR % (256, 2), 256, _CAPS5),
+       # 19 tiles over 8 waves, 35 over 16: 3 workgroups
+       ('pair', 64, 256, 64, 16 * 19 - 5, 0, 0, _B64, 16, _CAPS_RES),
+       ('pair', 64, 256, 128, 16 * 35 - 5, 0, 0, _B128, 16, _CAPS_RES),
+       ('pair_ds', 64, 256, 64, 16 * 35 - 5, 0, 0, _DS1, 16, _CAPS_RES),
+       ('pair_ds', 64, 256, 64, 32 * 35 - 5, 512, 0, _DS2, 32, _CAPS_RES)])
+
+
+def ffn_case_id(case):
+    return '-'.join(map(str, case[:7]))
+
+
+def ffn_direct_ld(case):
+    """Row strides of a case's operands: every X (and A) D + 8, the FFN entries' Y D + 16, the attention residual
+    D + 24, the downsample pair's block input 72."""
+    D = case[1]
+    return dict(ldx=D + 8, ldy=D + 16, lda=D + 8, ldr=D + 24, ldx0=72)
+
+
+# --- the references: plain f64, stage by stage; `drop` = (GEMM name, row, output column, k) takes that one
+# product out of that GEMM's sum (the probes of test_direct_refs_cpu.py) ---
+def rnd(v, dtype):
+    """v rounded to dtype, in f64."""
+    return v.to(dtype).double()
+
+
+def _mm(a, b, drop, name):
+    """(a (M, K) @ b (N, K)^T, |a| @ |b|^T)."""
+    acc = a @ b.T
+    if drop is not None and drop[0] == name:
+        _, m, n, k = drop
+        acc[m, n] = acc[m, n] - a[m, k] * b[n, k]
+    return acc, a.abs() @ b.abs().T
+
+
+def ffn_ref(x, W1, b1, W2, b2, ln, dtype, drop=None):
+    """kinet_ffn_fused on x (M, D) holding values of dtype: h = relu(x W1^T + b1) rounded once to dtype, pre = x +
+    h W2^T + b2, y = LayerNorm(pre) for ln = (gamma, beta, eps), else pre (the caller rounds the output).  Also the
+    majorants of ffn_generic_bound: absA = |x| @ |W1|^T, majA = |acc| + |b1|, majB = |x| + |acc| + |b2|."""
+    x, W1, b1, W2, b2 = (t.double() for t in (x, W1, b1, W2, b2))
+    accA, absA = _mm(x, W1, drop, 'W1')
+    h = rnd((accA + b1).clamp(min=0), dtype)
+    accB, _ = _mm(h, W2, drop, 'W2')
+    pre = x + accB + b2
+    out = dict(x=x, h=h, pre=pre, absA=absA, majA=accA.abs() + b1.abs(), majB=x.abs() + accB.abs() + b2.abs())
+    out['y'] = ln_epilogue_ref(pre, ln[0], ln[1], ln[2])['y'] if ln is not None else pre
+    return out
+
+
+def attn_out_ffn_ref(A, R, Wo, bo, ln1, W1, b1, W2, b2, ln2, dtype, drop=None):
+    """kinet_attn_out_ffn_fused: x = LN1(R + A Wo^T + bo) rounded once to dtype (ln1 = (gamma, beta, eps)), then
+    ffn_ref on that x.  pre1 / x64: the first LayerNorm's input / unrounded output; absO, majO its GEMM's majorants."""
+    A, R, Wo, bo = (t.double() for t in (A, R, Wo, bo))
+    accO, absO = _mm(A, Wo, drop, 'Wo')
+    pre1 = R + accO + bo
+    l1 = ln_epilogue_ref(pre1, ln1[0], ln1[1], ln1[2])
+    out = ffn_ref(rnd(l1['y'], dtype), W1, b1, W2, b2, ln2, dtype, drop)
+    out.update(pre1=pre1, x64=l1['y'], ln1=l1, absO=absO, majO=R.abs() + accO.abs() + bo.abs())
+    return out
+
+
+def scaled_rows(W, s, dtype):
+    """A bottleneck pack's weight rows: the f32 weight times its f32 scale (one f32 rounding), rounded once to dtype."""
+    return (W.float() * s.float().reshape(-1, 1)).to(dtype).double()
+
+
+def pair_ref(X, R, W3, s3, b3, W1, s1, b1, dtype, drop=None):
+    """kinet_bottleneck_pair: Y = relu(X (s3 W3)^T + b3 + R) rounded once (preY: before the rounding), T = relu(Y
+    (s1 W1)^T + b1) from that rounded Y (preT likewise); each weight row scaled, then rounded once, as the pack does."""
+    X, R, b3, b1 = (t.double() for t in (X, R, b3, b1))
+    W3s, W1s = scaled_rows(W3, s3, dtype), scaled_rows(W1, s1, dtype)
+    accA, absA = _mm(X, W3s, drop, 'W3')
+    preY = (accA + b3 + R).clamp(min=0)
+    return _pair_tail(preY, absA, accA.abs() + b3.abs() + R.abs(), W1s, b1, dtype, drop)
+
+
+def pair_ds_ref(X, X0, W3, Wds, s3, sds, b3ds, W1, s1, b1, dtype, drop=None):
+    """kinet_bottleneck_pair_ds: as pair_ref with Y = relu(X (s3 W3)^T + X0 (s_ds W_ds)^T + b3ds)."""
+    X, X0, b3ds, b1 = (t.double() for t in (X, X0, b3ds, b1))
+    W3s, Wdss, W1s = scaled_rows(W3, s3, dtype), scaled_rows(Wds, sds, dtype), scaled_rows(W1, s1, dtype)
+    acc3, abs3 = _mm(X, W3s, drop, 'W3')
+    accd, absd = _mm(X0, Wdss, drop, 'Wds')
+    preY = (acc3 + accd + b3ds).clamp(min=0)
+    return _pair_tail(preY, abs3 + absd, acc3.abs() + accd.abs() + b3ds.abs(), W1s, b1, dtype, drop)
+
+
+def _pair_tail(preY, absA, majA, W1s, b1, dtype, drop):
+    Y = rnd(preY, dtype)
+    accB, _ = _mm(Y, W1s, drop, 'W1')
+    return dict(preY=preY, Y=Y, preT=(accB + b1).clamp(min=0), absA=absA, majA=majA, majB=accB.abs() + b1.abs(), W1s=W1s)
+
+
+# --- the generic class's bound ---
+# u = U32, r = OUT_ROUND[dtype]; every product of two 16-bit values is exact in f32.
+#   phase A, as gemm_generic_bound: K1 exact products summed in f32 in any order, then the bias (and the
+#     residual) added:  errA = 1.01 (K1 + 64) u absA + 4 u majA  [+ dx @ |W1|^T where the operand itself is off
+#     by dx: the attention entry's x];
+#   the hidden: the kernel rounds its own f32 value, the reference its f64 one; |rd(p) - rd(q)| <= |p - q| +
+#     r |p| + r |q| and relu does not widen |p - q|:  dh = (1 + r) errA + 2 r h, h the reference's rounded hidden;
+#   phase B: that difference through |W2|, plus the accumulation of the kernel's own hidden (at most h + dh):
+#     errB = dh @ |W2|^T + 1.01 (K2 + 64) u ((h + dh) @ |W2|^T);
+#   the epilogue's additions (residual, bias; relu is exact): 4 u majB  [+ dx on the residual];
+#   the output: rd(p) against the unrounded reference q: (1 + r) E + r |q| -- or, with the LayerNorm on,
+#     ln_propagate(E) + the LayerNorm epilogue's own bound (ffn_ln_tol).
+def ffn_generic_bound(absA, majA, h, W2abs, majB, K1, K2, dtype, dxA=None, dxres=None):
+    """The bound E on |kernel's f32 value before the output rounding - the reference's| per element, and dh."""
+    r = OUT_ROUND[dtype]
+    errA = 1.01 * (K1 + 64) * U32 * absA + 4 * U32 * majA
+    if dxA is not None:
+        errA = errA + (1 + 1.01 * (K1 + 64) * U32) * dxA     # the kernel sums |x| + dx
+    dh = (1 + r) * errA + 2 * r * h.abs()
+    E = dh @ W2abs.T + 1.01 * (K2 + 64) * U32 * ((h.abs() + dh) @ W2abs.T) + 4 * U32 * majB
+    if dxres is not None:
+        E = E + dxres
+    return E, dh
+
+
+def out_round_bound(E, ref, dtype):
+    return (1 + OUT_ROUND[dtype]) * E + OUT_ROUND[dtype] * ref.abs() + 1e-30
+
+
+def ln_propagate(E, v, gamma, eps):
+    """|LN(v') - LN(v)| for |v' - v| <= E elementwise, rigorously: the centred value moves by dc = E + mean E;
+    the variance by at most dvar = mean(2 |c| dc + dc^2); rstd is decreasing and convex in the variance, so it moves
+    by at most drs = (var + eps - dvar)^-1/2 - (var + eps)^-1/2; then |gamma| (dc (rstd + drs) + |c| drs)."""
+    v = v.double()
+    c = v - v.mean(-1, keepdim=True)
+    dc = E + E.mean(-1, keepdim=True)
+    var = (c * c).mean(-1, keepdim=True) + eps32(eps)
+    dvar = (2 * c.abs() * dc + dc * dc).mean(-1, keepdim=True)
+    assert (dvar < var).all()
+    drs = (var - dvar).rsqrt() - var.rsqrt()
+    return gamma.double().abs() * (dc * (var.rsqrt() + drs) + c.abs() * drs)
+
+
+def ffn_ln_tol(pre, ln, dtype):
+    """test_ln_epilogue_direct_gpu.py's bound on a fused LayerNorm epilogue's output (rw_ln_check): one rounding of
+    the 16-bit output + 4x the error of torch's CPU f32 layer_norm of the same pre-activation.  (y64, tol)."""
+    y, t = ln_epilogue_yardstick(pre.cpu(), ln[0].cpu(), ln[1].cpu(), ln[2])
+    return y, OUT_ROUND[dtype] * y.abs() + 4 * t
+
+
+# --- operands ---
+def sparse_w(shape, q, g, unit=0.5):
+    """+-unit with probability q each, +-2 unit with q / 4 each (exact_w's shape: var = 4 q unit^2); then one +-unit
+    into every aligned 4-row x 32-column block and every column that came out empty.  Every 1-KiB fragment of the
+    packed streams is four such blocks (16 rows of 4 aligned groups, 32 aligned columns: ffn_pack_src)."""
+    u = torch.rand(shape, generator=g)
+    w = torch.zeros(shape)
+    for lo, hi, v in ((0, q, 1), (q, 2 * q, -1), (2 * q, 2.25 * q, 2), (2.25 * q, 2.5 * q, -2)):
+        w[(u >= lo) & (u < hi)] = v
+    R_, C_ = shape
+    blocks = (w != 0).view(R_ // 4, 4, C_ // 32, 32).sum((1, 3)) == 0
+    bi, bj = blocks.nonzero(as_tuple=True)
+    if bi.numel():
+        rr = 4 * bi + torch.randint(0, 4, bi.shape, generator=g)
+        cc = 32 * bj + torch.randint(0, 32, bi.shape, generator=g)
+        w[rr, cc] = torch.randint(0, 2, bi.shape, generator=g).float() * 2 - 1
+    cols = ((w != 0).sum(0) == 0).nonzero().flatten()
+    if cols.numel():
+        w[torch.randint(0, R_, cols.shape, generator=g), cols] = 1.0
+    return w * unit
+
+
+def _quarters(lo, hi, n, g):
+    """n multiples of 1/4 in [lo / 4, hi / 4]."""
+    return torch.randint(lo, hi + 1, (n,), generator=g).float() / 4
+
+
+def _ffn_exact_tail(D, F_, g, xvar, q2F):
+    """W1, b1, W2, b2 of the exact class for an x of variance xvar: accumulator std 1.25, b1 = -1 + multiples of 1/4
+    in [-1/2, 1/2] (about a fifth of the hidden units live), W2 with q2 = q2F / F (at most 0.19)."""
+    W1 = sparse_w((F_, D), _EXACT_ACC_STD ** 2 / (D * xvar), g)
+    b1 = -1 + _quarters(-2, 2, F_, g)
+    W2 = sparse_w((D, F_), min(0.19, q2F / F_), g)
+    return W1, b1, W2, _quarters(-4, 4, D, g)
+
+
+FFN_KINDS_ = ('ffn', 'attn_out_ffn', 'pair', 'pair_ds')      # the entry points, in the planner's order
+
+
+def _seed(case, cls):
+    kind, D, F_, DB, M, debug = case[:6]
+    return (FFN_KINDS_.index(kind) * 7 + debug) * 1000003 + D * 7919 + F_ * 131 + DB * 17 + M + (0 if cls == 'exact' else 5)
+
+
+FFN_LN1_EPS_EXACT = 3.0
+
+
+def ffn_direct_inputs(case, cls, dtype=None):
+    return _ffn_direct_inputs(tuple(case[:7]), cls, dtype)
+
+
+@functools.lru_cache(maxsize=3)
+def _ffn_direct_inputs(case, cls, dtype):
+    """The operands of a row of FFN_DIRECT_CASES as CPU f32 tensors.  cls 'exact' (dtype-independent: pass None) or
+    'generic' (randn rounded to dtype, weights scaled by K^-1/2: generic_operands).
+
+    Exact class, FFN: x multiples of 1/2 in [-1, 1]; W1, W2 in {0, +-1/2, +-1}, sparse; h comes out as multiples of
+    1/4 and the output as multiples of 1/8 below 32: exact in bf16.
+    Exact class, attention entry: A, Wo, bo dyadic, S = +-1 with D/2 of each sign per row, R = S - (A Wo^T + bo), so
+    LayerNorm1's input is S whatever the summation order: mean 0, variance 1, and with eps1 = 3 rstd = 1/2; gamma1 in
+    {1, 2}, beta1 in {+-1/4, +-3/4}: x = +-gamma1/2 + beta1 is a non-zero multiple of 1/4, far from any rounding tie
+    (an inexact rsqrtf moves nothing: test_direct_refs_cpu.py).  h multiples of 1/8, the output of 1/16 below 16.
+    Exact class, pairs: X, X0 multiples of 1/2, R of 1/4 in [-1, 1]; raw weights in {0, +-1/2, +-1} and scales in
+    {1, 2}; b3 multiples of 1/4 in [0, 1]; Y multiples of 1/4, T of 1/8 below 32."""
+    kind, D, F_, DB, M = case[:5]
+    g = torch.Generator().manual_seed(_seed(case, cls))
+    ex = cls == 'exact'
+    d = {}
+    if kind == 'ffn':
+        if ex:
+            d['x'] = exact_x((M, D), g)
+            d['W1'], d['b1'], d['W2'], d['b2'] = _ffn_exact_tail(D, F_, g, 0.5, 30)
+        else:
+            d['x'], d['W1'] = generic_operands((M, D), (F_, D), D, dtype, g)
+    elif kind == 'attn_out_ffn':
+        if ex:
+            d['A'] = exact_x((M, D), g)
+            d['Wo'] = sparse_w((D, D), _EXACT_ACC_STD ** 2 / (D * 0.5), g)
+            d['bo'] = _quarters(-4, 4, D, g)
+            d['S'] = (torch.rand(M, D, generator=g).argsort(1) < D // 2).float() * 2 - 1
+            d['R'] = (d['S'].double() - (d['A'].double() @ d['Wo'].double().T + d['bo'].double())).float()
+            d['g1'] = torch.randint(1, 3, (D,), generator=g).float()
+            d['be1'] = torch.tensor([-0.75, -0.25, 0.25, 0.75])[torch.randint(0, 4, (D,), generator=g)]
+            d['eps1'] = FFN_LN1_EPS_EXACT
+            # var(x) = E[gamma1^2] / 4 + E[beta1^2] = 5/8 + 5/16
+            d['W1'], d['b1'], d['W2'], d['b2'] = _ffn_exact_tail(D, F_, g, 0.9375, 6)
+        else:
+            d['A'], d['Wo'] = generic_operands((M, D), (D, D), D, dtype, g)
+            d['bo'] = torch.randn(D, generator=g)
+            d['R'] = torch.randn(M, D, generator=g).to(dtype).float()
+            d['g1'], d['be1'] = torch.rand(D, generator=g) + 0.5, torch.randn(D, generator=g)
+            d['eps1'] = 1e-5
+            d['W1'] = (torch.randn(F_, D, generator=g) / D ** 0.5).to(dtype).float()
+    if kind in ('ffn', 'attn_out_ffn'):
+        if not ex:
+            d['b1'] = torch.randn(F_, generator=g)
+            d['W2'] = (torch.randn(D, F_, generator=g) / F_ ** 0.5).to(dtype).float()
+            d['b2'] = torch.randn(D, generator=g)
+        d['ln'] = (torch.rand(D, generator=g) + 0.5, torch.randn(D, generator=g), 1e-5)
+        return d
+    ds = kind == 'pair_ds'
+    if ex:
+        d['X'] = exact_x((M, D), g)
+        qa = _EXACT_ACC_STD ** 2 / (D * 0.5 * 2.5) / (2 if ds else 1)     # E[s^2] = 5/2
+        d['W3'], d['s3'] = sparse_w((F_, D), qa, g), torch.randint(1, 3, (F_,), generator=g).float()
+        d['b3'] = _quarters(0, 4, F_, g)
+        if ds:
+            d['X0'] = exact_x((M, D), g)
+            d['Wds'], d['sds'] = sparse_w((F_, D), qa, g), torch.randint(1, 3, (F_,), generator=g).float()
+        else:
+            d['R'] = torch.randint(-4, 5, (M, F_), generator=g).float() / 4
+        d['W1'], d['s1'] = sparse_w((DB, F_), 2.0 / F_, g), torch.randint(1, 3, (DB,), generator=g).float()
+        d['b1'] = _quarters(-4, 4, DB, g)
+    else:
+        d['X'] = torch.randn(M, D, generator=g).to(dtype).float()
+        d['W3'], d['s3'] = torch.randn(F_, D, generator=g) / D ** 0.5, torch.rand(F_, generator=g) + 0.5
+        d['b3'] = torch.randn(F_, generator=g)
+        if ds:
+            d['X0'] = torch.randn(M, D, generator=g).to(dtype).float()
+            d['Wds'], d['sds'] = torch.randn(F_, D, generator=g) / D ** 0.5, torch.rand(F_, generator=g) + 0.5
+        else:
+            d['R'] = torch.randn(M, F_, generator=g).to(dtype).float()
+        d['W1'], d['s1'] = torch.randn(DB, F_, generator=g) / F_ ** 0.5, torch.rand(DB, generator=g) + 0.5
+        d['b1'] = torch.randn(DB, generator=g)
+    return d
+
+
+def ffn_direct_ref(case, d, dtype, ln=False, offset=0.0, drop=None, rows=None, dev='cpu'):
+    """The reference of a row of FFN_DIRECT_CASES on its operands d (all rows, or the slice `rows`), on device `dev`.
+    ln: the final LayerNorm on (FFN entries), with `offset` added to b2."""
+    kind = case[0]
+
+    def t(name, per_row=False):
+        v = d[name][rows] if per_row and rows is not None else d[name]
+        return v.to(dev)
+    if kind in ('ffn', 'attn_out_ffn'):
+        lnp = (d['ln'][0].to(dev), d['ln'][1].to(dev), d['ln'][2]) if ln else None
+        b2 = t('b2') + offset
+        if kind == 'ffn':
+            return ffn_ref(t('x', True), t('W1'), t('b1'), t('W2'), b2, lnp, dtype, drop)
+        return attn_out_ffn_ref(t('A', True), t('R', True), t('Wo'), t('bo'), (t('g1'), t('be1'), d['eps1']),
+                                t('W1'), t('b1'), t('W2'), b2, lnp, dtype, drop)
+    if kind == 'pair':
+        return pair_ref(t('X', True), t('R', True), t('W3'), t('s3'), t('b3'), t('W1'), t('s1'), t('b1'), dtype, drop)
+    return pair_ds_ref(t('X', True), t('X0', True), t('W3'), t('Wds'), t('s3'), t('sds'), t('b3'), t('W1'), t('s1'),
+                       t('b1'), dtype, drop)
+
+
+def ffn_direct_outputs(case, ref):
+    """{name: f64 value before the output rounding} of what the entry point writes."""
+    return {'y': ref['y']} if case[0] in ('ffn', 'attn_out_ffn') else {'Y': ref['preY'], 'T': ref['preT']}
+
+
+def ffn_direct_gemms(case):
+    """The weight matrices of a case's GEMMs, by their key in its operands (= the `drop` name of the references)."""
+    return {'ffn': ('W1', 'W2'), 'attn_out_ffn': ('Wo', 'W1', 'W2'), 'pair': ('W3', 'W1'), 'pair_ds': ('W3', 'Wds', 'W1')}[case[0]]
+
+
+def ffn_direct_generic_tol(case, d, ref, dtype, ln):
+    """Per-element tolerance of each output of a generic-class row (derivation above ffn_generic_bound)."""
+    kind, D, F_, DB = case[:4]
+    r = OUT_ROUND[dtype]
+    dev = ref['absA'].device
+    if kind in ('pair', 'pair_ds'):
+        K1 = 2 * D if kind == 'pair_ds' else D
+        errA = 1.01 * (K1 + 64) * U32 * ref['absA'] + 4 * U32 * ref['majA']
+        dY = (1 + r) * errA + 2 * r * ref['Y'].abs()
+        W1a = ref['W1s'].abs()
+        ET = dY @ W1a.T + 1.01 * (F_ + 64) * U32 * ((ref['Y'].abs() + dY) @ W1a.T) + 4 * U32 * ref['majB']
+        return {'Y': out_round_bound(errA, ref['preY'], dtype), 'T': out_round_bound(ET, ref['preT'], dtype)}
+    W1a, W2a = d['W1'].double().abs().to(dev), d['W2'].double().abs().to(dev)
+    dxA = dx = None
+    if kind == 'attn_out_ffn':
+        # x: the out-projection's sums (as phase A, the residual among the additions) through LayerNorm1, the f32
+        # LayerNorm's own error (ln_epilogue_ref: y_c u yA), then the two roundings of x as for the hidden
+        E1 = 1.01 * (D + 64) * U32 * ref['absO'] + 4 * U32 * ref['majO']
+        l1 = ref['ln1']
+        ex = ln_propagate(E1, ref['pre1'], d['g1'].to(dev), d['eps1']) + l1['y_c'] * U32 * l1['yA']
+        dx = (1 + r) * ex + 2 * r * ref['x'].abs()
+        dxA = dx @ W1a.T
+    E, _ = ffn_generic_bound(ref['absA'], ref['majA'], ref['h'], W2a, ref['majB'], D, F_, dtype, dxA, dx)
+    if not ln:
+        return {'y': out_round_bound(E, ref['pre'], dtype)}
+    _, tol = ffn_ln_tol(ref['pre'], d['ln'], dtype)
+    return {'y': ln_propagate(E, ref['pre'], d['ln'][0].to(dev), d['ln'][2]) + tol.to(dev)}

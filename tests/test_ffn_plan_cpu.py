@@ -23,27 +23,28 @@ def last_error():
 
 
 @contextlib.contextmanager
-def knobs(debug, solo):
+def knobs(debug, solo, cap=0):
     from kinet_amd import _native
     L = _native.lib()
-    old, old_solo = L.kinet_ffn_set_debug(debug), L.kinet_set_solo_launch(solo)
+    old, old_solo, old_cap = L.kinet_ffn_set_debug(debug), L.kinet_set_solo_launch(solo), L.kinet_ffn_grid_cap(cap)
     try:
         yield
     finally:
         L.kinet_ffn_set_debug(old)
         L.kinet_set_solo_launch(old_solo)
+        L.kinet_ffn_grid_cap(old_cap)
 
 
-def plan(K, kind, M, D, DB, debug=0, solo=0, cus=256):
-    with knobs(debug, solo):
-        return K.ffn_launch_plan(kind, M, D, 4 * D, DB, cus)
+def plan(K, kind, M, D, DB, debug=0, solo=0, cus=256, cap=0, F_=None):
+    with knobs(debug, solo, cap):
+        return K.ffn_launch_plan(kind, M, D, 4 * D if F_ is None else F_, DB, cus)
 
 
 # --------------------------------------------------------------------------- the literal tables
-@pytest.mark.parametrize('case', R.FFN_PLAN_CASES, ids=lambda c: '-'.join(map(str, c[:6])))
+@pytest.mark.parametrize('case', R.FFN_PLAN_CASES, ids=lambda c: '-'.join(map(str, c[:6] + c[7:])))
 def test_table_plan(K, case):
-    kind, M, D, DB, debug, solo, want = case
-    got = plan(K, kind, M, D, DB, debug, solo)
+    kind, M, D, DB, debug, solo, want = case[:7]
+    got = plan(K, kind, M, D, DB, debug, solo, cap=case[7] if len(case) > 7 else 0)
     if isinstance(want, str):
         assert got is None and last_error() == want
         return
@@ -63,6 +64,38 @@ def test_table_of_kernels(K):
     assert {c[6][0] for c in R.FFN_PLAN_CASES if not isinstance(c[6], str)} == set(names)
     for waves, rows, wg_tiles, wg_per_cu, lds in R.FFN_KERNELS.values():
         assert lds * wg_per_cu <= R.FFN_LDS_LIMIT and 64 * waves * wg_per_cu <= 1024
+
+
+@pytest.mark.parametrize('case', R.FFN_DIRECT_CASES, ids=R.ffn_case_id)
+def test_direct_table_plan(K, case):
+    """Every row of the direct tests' table (tests/test_ffn_direct_gpu.py), under every grid cap it lists: the kernel it
+    names, its row tiles and the grid; M is five ragged tiles, the 16384-row floor's 65 / 130, or 2 waves + 3 tiles."""
+    kind, D, F_, DB, M, debug, solo, kernel, rows, caps = case
+    waves, tile_rows, wg_tiles, wg_per_cu, lds = R.FFN_KERNELS[kernel]
+    assert rows == tile_rows and M % rows == rows - 5 and 0 in caps
+    tiles = -(-M // rows)
+    assert tiles in (5, 65, 130, 2 * waves + 3) and (tiles == 2 * waves + 3) == (wg_tiles > 1)
+    assert caps[0] == -(-tiles // wg_tiles) and all(grid == min(cap, caps[0]) for cap, grid in caps.items() if cap)
+    for cap, grid in caps.items():
+        got = plan(K, kind, M, D, DB, debug, solo, cap=cap, F_=F_)
+        assert got == dict(kernel=kernel, tiles=tiles, grid=grid, block=64 * waves, waves=waves, tile_rows=rows,
+                           wg_tiles=wg_tiles, wg_per_cu=wg_per_cu, lds=lds), (cap, got)
+
+
+def test_direct_table_reaches_every_kernel():
+    assert {c[7] for c in R.FFN_DIRECT_CASES} == set(R.FFN_KERNELS)
+    # the hidden-chunk counts of the FFN entries: 1, 2, 5 on every kernel, FFN_MAX_F on those that run at few rows
+    for kernel in {c[7] for c in R.FFN_DIRECT_CASES if c[0] in ('ffn', 'attn_out_ffn')}:
+        fs = {c[2] for c in R.FFN_DIRECT_CASES if c[7] == kernel}
+        small = {c[4] for c in R.FFN_DIRECT_CASES if c[7] == kernel} != {R.FFN_BIG_ROWS}
+        assert fs == ({32, 64, 160, 2048} if small else {32, 64, 160}), kernel
+
+
+def test_grid_cap_is_per_thread_state_with_the_previous_value_returned(K):
+    assert K.ffn_grid_cap(5) == 0 and K.ffn_grid_cap(-1) == 5 and K.ffn_grid_cap(0) == 0
+    with knobs(0, 0, 3):
+        assert K.ffn_launch_plan('ffn', 1000, 256)['grid'] == 3
+    assert K.ffn_launch_plan('ffn', 1000, 256)['grid'] == 16
 
 
 def test_row_threshold(K):
@@ -107,15 +140,15 @@ def test_structure(K, cus):
                 ('pair', 256, 256, (0, 128, 256)), ('pair_ds', 64, 64, (0, 512))]
     for kind, D, DB, debugs in problems:
         for debug in debugs:
-            for solo in (0, 1):
-                with knobs(debug, solo):
+            for solo, cap in ((0, 0), (1, 0), (0, 1), (1, 7), (0, cus), (0, 1 << 30)):
+                with knobs(debug, solo, cap):
                     for M in _sweep_rows():
                         p = K.ffn_launch_plan(kind, M, D, 4 * D, DB, cus)
-                        assert 1 <= p['grid'] <= cus * p['wg_per_cu'], (kind, D, DB, debug, solo, M, p)
+                        assert 1 <= p['grid'] <= cus * p['wg_per_cu'], (kind, D, DB, debug, solo, cap, M, p)
                         assert p['tiles'] * p['tile_rows'] >= M > (p['tiles'] - 1) * p['tile_rows']
                         assert p['block'] == 64 * p['waves'] <= 1024
-                        # a grid below its cap covers every tile at once
-                        assert p['grid'] == min(-(-p['tiles'] // p['wg_tiles']), cus * p['wg_per_cu'])
+                        # a grid below its caps covers every tile at once; kinet_ffn_grid_cap is one more cap
+                        assert p['grid'] == min(-(-p['tiles'] // p['wg_tiles']), cus * p['wg_per_cu'], cap or 1 << 30)
                         assert p['lds'] * p['wg_per_cu'] <= R.FFN_LDS_LIMIT
                         assert (p['waves'], p['tile_rows'], p['wg_tiles'], p['wg_per_cu'], p['lds']) == R.FFN_KERNELS[p['kernel']]
 
