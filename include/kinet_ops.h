@@ -72,16 +72,42 @@ int kinet_mha_core_dropout(const void* Q, int ldq, const void* Kt, int ldk, cons
 int kinet_dropout_mask(const int64_t* dropout_seed, int64_t n, float dropout_p, uint8_t* keep,
                        kinet_stream_t stream);
 
-/* Diagnostic knob (no reference counterpart) for kinet_mha_core on bf16 / f16, head_dim 32
- * (row strides % 8, 16-byte pointers) or 36 (row strides % 4, 8-byte pointers), no dropout:
- *   1 (default) = the MFMA kernels of attn.hip: keys resident in LDS up to Lk 384 (head_dim 32)
- *                 / 640 (head_dim 36), the key-streaming kernel for longer key sets;
+/* Diagnostic knob (no reference counterpart) for the kinet_mha_core calls the MFMA kernels of
+ * attn.hip can take; which calls those are, and where the resident kernel hands over to the
+ * key-streaming one, is attn_plan() of csrc/attn_plan.h (kinet_mha_launch_plan answers from it):
+ *   1 (default) = the plan's choice: keys resident in LDS up to the head dim's cap, streamed above;
  *   0           = always the FMA kernel;
  *   2           = the key-streaming kernel for every such call whatever Lk (tests reach its
  *                 tile edges at small sizes).
- * Every other call (fp32, dropout, other head dims, unaligned operands) runs the FMA kernel at
- * any setting.  Per calling thread.  Returns the previous setting. */
+ * Every other call runs the FMA kernel at any setting.  Per calling thread.  Returns the
+ * previous setting. */
 int kinet_mha_set_mfma(int enable);
+
+/* Planning and diagnostics (host side, no GPU call; no reference counterpart).
+ * kinet_mha_launch_plan: the launch kinet_mha_core / kinet_mha_core_dropout makes for a described
+ * problem: KINET_MHAP_FIELDS ints in, KINET_MHAPL_FIELDS ints out.  KINET_ERR_ARG with the entry
+ * point's message for sizes or a head dim it refuses.  An empty batch or Lq: a zero grid, nothing
+ * would be launched.
+ * kinet_mha_last_kernel: KINET_MHAPL_KERNEL of the calling thread's last launch (-1: none yet). */
+enum kinet_mha_problem_field {
+    KINET_MHAP_DTYPE = 0,     /* kinet_dtype */
+    KINET_MHAP_HEAD_DIM, KINET_MHAP_BATCH, KINET_MHAP_HEADS, KINET_MHAP_LQ, KINET_MHAP_LK,
+    KINET_MHAP_LDQ, KINET_MHAP_LDK, KINET_MHAP_LDV, KINET_MHAP_LDO,   /* row strides in elements */
+    KINET_MHAP_ALIGN,         /* bytes every one of the Q / K / V / O pointers is a multiple of */
+    KINET_MHAP_DROPOUT,       /* 1: kinet_mha_core_dropout with p > 0 */
+    KINET_MHAP_KNOB,          /* a kinet_mha_set_mfma value; < 0: the calling thread's */
+    KINET_MHAP_FIELDS
+};
+enum kinet_mha_plan_field {
+    KINET_MHAPL_KERNEL = 0,   /* 0 the FMA kernel, 1 mha_resident_kernel, 2 mha_stream_kernel */
+    KINET_MHAPL_GRID_X, KINET_MHAPL_GRID_Y, KINET_MHAPL_GRID_Z, KINET_MHAPL_BLOCK,
+    KINET_MHAPL_LDS,          /* dynamic LDS bytes */
+    KINET_MHAPL_RESIDENT_MAXK,/* the head dim's resident cap (0: it has no MFMA kernel) */
+    KINET_MHAPL_STREAM_KT,    /* keys per tile of the streaming kernel */
+    KINET_MHAPL_FIELDS
+};
+int kinet_mha_launch_plan(const int* problem, int* plan_out);
+int kinet_mha_last_kernel(void);
 
 /* Iterative box refinement (deformable_transformer.py:414-425) fused with the next
  * layer's reference input (:406-411):

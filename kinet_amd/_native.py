@@ -78,6 +78,8 @@ _SIGS = {
     'kinet_pack_image_nhwc': [P, P] + [I] * 5 + [P],
     'kinet_pack_image_kwfold': [P, P] + [I] * 8 + [P],
     'kinet_mha_set_mfma': [I],
+    'kinet_mha_launch_plan': [P, P],
+    'kinet_mha_last_kernel': [],
     'kinet_mha_core': [P, I, P, I, P, I, P, I] + [I] * 5 + [F, I, P, P],
     'kinet_add': [P, P, P, I64, I, P],
     'kinet_box_refine': [P, P, I, P, P, P, I, I, I, P],

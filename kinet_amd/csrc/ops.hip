@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "../../include/kinet_ops.h"
+#include "attn_plan.h"
 #include "common.h"
 
 namespace kinet {
@@ -792,12 +793,12 @@ extern "C" int kinet_add(const void* a, const void* b, void* y, int64_t n, int d
 }
 
 namespace kinet {
-// attn.hip: the MFMA kernels for 16-bit head_dim 32 / 36 (false = not covered): resident keys up
-// to 384 / 640, the key-streaming kernel above that (mode 2: the streaming kernel at any Lk)
-bool launch_mha_mfma(const void* Q, int ldq, const void* Kt, int ldk, const void* V, int ldv, void* O, int ldo,
-                     int batch, int Lq, int Lk, int heads, int head_dim, float scale, int dtype,
-                     const uint8_t* key_mask, int mode, hipStream_t stream);
+// attn.hip: run the MFMA kernel the plan names with the plan's grid and LDS
+void launch_mha_mfma(const AttnPlan& pl, const void* Q, int ldq, const void* Kt, int ldk, const void* V, int ldv, void* O,
+                     int ldo, int Lq, int Lk, int head_dim, float scale, int dtype, const uint8_t* key_mask,
+                     hipStream_t stream);
 thread_local int mha_use_mfma = 1;   // test-only knob (kinet_mha_set_mfma), per calling thread
+thread_local int mha_last = -1;      // AttnKernel of the calling thread's last launch (kinet_mha_last_kernel)
 }  // namespace kinet
 
 extern "C" int kinet_mha_set_mfma(int enable) {
@@ -806,28 +807,58 @@ extern "C" int kinet_mha_set_mfma(int enable) {
     return old;
 }
 
-static int mha_core_impl(const void* Q, int ldq, const void* Kt, int ldk, const void* V, int ldv, void* O, int ldo,
-                         int batch, int Lq, int Lk, int heads, int head_dim, float scale, int dtype,
-                         const uint8_t* key_mask, float dropout_p, const int64_t* dropout_seed, kinet_stream_t stream) {
+extern "C" int kinet_mha_last_kernel(void) { return kinet::mha_last; }
+
+// the size checks kinet_mha_core and kinet_mha_launch_plan share
+static int mha_check_sizes(int batch, int Lq, int Lk, int heads, int head_dim) {
     KINET_CHECK_ARG(batch >= 0 && Lq >= 0 && Lk >= 0 && heads > 0, "mha: bad sizes");
     KINET_CHECK_ARG(head_dim == 32 || head_dim == 36 || head_dim == 16 || head_dim == 64,
                     "mha: head_dim %d not instantiated (16/32/36/64)", head_dim);
+    return KINET_OK;
+}
+
+extern "C" int kinet_mha_launch_plan(const int* problem, int* plan_out) {
+    KINET_CHECK_ARG(problem != nullptr && plan_out != nullptr, "mha launch plan: invalid arguments");
+    const int* f = problem;
+    if (const int rc = mha_check_sizes(f[KINET_MHAP_BATCH], f[KINET_MHAP_LQ], f[KINET_MHAP_LK], f[KINET_MHAP_HEADS],
+                                       f[KINET_MHAP_HEAD_DIM]))
+        return rc;
+    const int knob = f[KINET_MHAP_KNOB] < 0 ? kinet::mha_use_mfma : f[KINET_MHAP_KNOB];
+    const kinet::AttnPlan pl = kinet::attn_plan(kinet::AttnProblem{
+        f[KINET_MHAP_DTYPE], f[KINET_MHAP_HEAD_DIM], f[KINET_MHAP_BATCH], f[KINET_MHAP_HEADS], f[KINET_MHAP_LQ],
+        f[KINET_MHAP_LK], f[KINET_MHAP_LDQ], f[KINET_MHAP_LDK], f[KINET_MHAP_LDV], f[KINET_MHAP_LDO], f[KINET_MHAP_ALIGN],
+        f[KINET_MHAP_DROPOUT] != 0, knob});
+    const int rec[KINET_MHAPL_FIELDS] = {pl.kernel, pl.grid[0], pl.grid[1], pl.grid[2], pl.block, pl.lds,
+                                         kinet::attn_geo(f[KINET_MHAP_HEAD_DIM]).maxk, kinet::kAttnStreamKT};
+    for (int i = 0; i < KINET_MHAPL_FIELDS; ++i) plan_out[i] = rec[i];
+    return KINET_OK;
+}
+
+static int mha_core_impl(const void* Q, int ldq, const void* Kt, int ldk, const void* V, int ldv, void* O, int ldo,
+                         int batch, int Lq, int Lk, int heads, int head_dim, float scale, int dtype,
+                         const uint8_t* key_mask, float dropout_p, const int64_t* dropout_seed, kinet_stream_t stream) {
+    if (const int rc = mha_check_sizes(batch, Lq, Lk, heads, head_dim)) return rc;
     KINET_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || dropout_seed),
                     "mha: dropout p %g must be in [0, 1) with a seed", (double)dropout_p);
     if (batch == 0 || Lq == 0) return KINET_OK;
     hipStream_t s = (hipStream_t)stream;
     const bool drop = dropout_p > 0.f;
-    if (!drop && kinet::mha_use_mfma &&
-        kinet::launch_mha_mfma(Q, ldq, Kt, ldk, V, ldv, O, ldo, batch, Lq, Lk, heads, head_dim, scale, dtype, key_mask,
-                               kinet::mha_use_mfma == 2 ? 2 : 1, s)) {
+    // every choice, the grid and the LDS size live in attn_plan.h
+    const uintptr_t ptrs = (uintptr_t)Q | (uintptr_t)Kt | (uintptr_t)V | (uintptr_t)O;
+    const kinet::AttnPlan pl = kinet::attn_plan(kinet::AttnProblem{
+        dtype, head_dim, batch, heads, Lq, Lk, ldq, ldk, ldv, ldo, (int)(ptrs % 16 ? ptrs & (~ptrs + 1) : 16), drop,
+        kinet::mha_use_mfma});
+    kinet::mha_last = pl.kernel;
+    if (pl.kernel != kinet::ATTN_K_FMA) {
+        kinet::launch_mha_mfma(pl, Q, ldq, Kt, ldk, V, ldv, O, ldo, Lq, Lk, head_dim, scale, dtype, key_mask, s);
         KINET_LAUNCH_CHECK();
         return KINET_OK;
     }
     const int64_t* dseed = drop ? dropout_seed : nullptr;
     const uint32_t dthresh = kinet::dropout_thresh(dropout_p);
     const float dscale = drop ? 1.f / (1.f - dropout_p) : 1.f;
-    dim3 grid((Lq + 15) / 16, heads, batch);
-#define MH(DD) DISPATCH_T(dtype, hipLaunchKernelGGL((mha_kernel<T, DD>), grid, dim3(256), 0, s, (const T*)Q, ldq, \
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+#define MH(DD) DISPATCH_T(dtype, hipLaunchKernelGGL((mha_kernel<T, DD>), grid, dim3(pl.block), 0, s, (const T*)Q, ldq, \
                                                    (const T*)Kt, ldk, (const T*)V, ldv, (T*)O, ldo, Lq, Lk, heads, \
                                                    scale, key_mask, dseed, dthresh, dscale))
     switch (head_dim) {

@@ -860,10 +860,44 @@ def dropout_mask(seed, n, p):
     return keep
 
 
-# csrc/attn.hip: the 16-bit head_dim 32 / 36 MFMA kernels keep a head's keys resident in LDS up
-# to these Lk; longer key sets run the key-streaming kernel in tiles of MHA_STREAM_KT keys
-MHA_RESIDENT_MAXK = {32: 384, 36: 640}
-MHA_STREAM_KT = 128
+# field order of kinet_mha_launch_plan's records (include/kinet_ops.h) and its kernel codes
+MHA_PROBLEM_FIELDS = ('dtype', 'head_dim', 'batch', 'heads', 'Lq', 'Lk', 'ldq', 'ldk', 'ldv', 'ldo', 'align', 'dropout',
+                      'knob')
+MHA_PLAN_FIELDS = ('kernel', 'grid_x', 'grid_y', 'grid_z', 'block', 'lds', 'resident_maxk', 'stream_kt')
+MHA_KERNELS = ('fma', 'resident', 'stream')
+
+
+def mha_launch_plan(dtype, head_dim, batch, heads, Lq, Lk, ld=None, align=16, dropout=False, knob=None):
+    """The launch mha_core makes for this problem (kinet_mha_launch_plan, csrc/attn_plan.h; no GPU call): a dict
+    of MHA_PLAN_FIELDS with 'kernel' one of MHA_KERNELS.  ld: the row stride of q / k / v / out in elements, one
+    value or four (default heads * head_dim); align: bytes every pointer is a multiple of; knob: a
+    kinet_mha_set_mfma value (default: the calling thread's)."""
+    ld = heads * head_dim if ld is None else ld
+    lds = tuple(ld) if isinstance(ld, (tuple, list)) else (ld,) * 4
+    prob = (ctypes.c_int * len(MHA_PROBLEM_FIELDS))(N.dtype_code(dtype), head_dim, batch, heads, Lq, Lk, *lds, align,
+                                                    int(bool(dropout)), -1 if knob is None else knob)
+    out = (ctypes.c_int * len(MHA_PLAN_FIELDS))()
+    N.call('kinet_mha_launch_plan', ctypes.cast(prob, ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p))
+    plan = dict(zip(MHA_PLAN_FIELDS, out))
+    plan['kernel'] = MHA_KERNELS[plan['kernel']]
+    return plan
+
+
+def mha_last_kernel():
+    """Which of MHA_KERNELS the calling thread's last mha_core call launched (kinet_mha_last_kernel), None
+    before the first."""
+    code = N.lib().kinet_mha_last_kernel()
+    return None if code < 0 else MHA_KERNELS[code]
+
+
+def __getattr__(name):
+    # csrc/attn_plan.h through the library: the 16-bit head_dim 32 / 36 MFMA kernels keep a head's keys resident
+    # in LDS up to MHA_RESIDENT_MAXK[head_dim]; longer key sets stream in tiles of MHA_STREAM_KT keys
+    if name == 'MHA_RESIDENT_MAXK':
+        return {D: mha_launch_plan(torch.bfloat16, D, 1, 1, 1, 1)['resident_maxk'] for D in (32, 36)}
+    if name == 'MHA_STREAM_KT':
+        return mha_launch_plan(torch.bfloat16, 32, 1, 1, 1, 1)['stream_kt']
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
 
 
 def mha_core(q, k, v, heads, scale, key_mask=None, out=None, dropout_p=0.0, seed=None):

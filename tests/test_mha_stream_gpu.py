@@ -1,12 +1,14 @@
-"""The key-streaming MFMA attention kernel (csrc/attn.hip mha_stream_kernel: head_dim 32 / 36,
-bf16 / f16, any Lk in double-buffered tiles of KT keys) vs fp32 SDPA with a key padding mask and
-vs the FMA kernel on the same 16-bit inputs.
+"""The MFMA attention kernels (csrc/attn.hip: mha_stream_kernel, any Lk in double-buffered tiles of
+KT keys, and mha_resident_kernel, the head's keys staged once; head_dim 32 / 36, bf16 / f16) vs
+fp32 SDPA with a key padding mask and vs the FMA kernel on the same 16-bit inputs.
 
 kinet_mha_set_mfma(2) sends every eligible call to the streaming kernel, so its tile edges are
-reached at small sizes; with the knob at its default the kernel serves Lk above the resident
-kernels' caps (384 at head_dim 32, 640 at head_dim 36), which ran the FMA kernel before.
-Tolerances are test_mha_core_mfma's (tests/test_gemm_gpu.py): the per-32-key block arithmetic is
-the resident kernels', so the same bound relative to max |ref| applies -- 2e-2 bf16, 4e-3 f16.
+reached at small sizes; with the knob at its default (1) the same small shapes run the resident
+kernel and the streaming kernel serves Lk above the resident caps (kernels.MHA_RESIDENT_MAXK).
+Which kernel ran is asserted by name (kernels.mha_last_kernel).  Both kernels run one block step
+(attn_block) over the same 32-key blocks in the same order, so their outputs are equal bit for bit.
+Tolerances are test_mha_core_mfma's (tests/test_gemm_gpu.py): the same bound relative to
+max |ref| -- 2e-2 bf16, 4e-3 f16.
 """
 import pytest
 import torch
@@ -34,11 +36,16 @@ def _knob(value):
     return _native.lib().kinet_mha_set_mfma(value)
 
 
-def _run(K, knob, q, k, v, D, mask):
+KNOB = {'fma': 0, 'resident': 1, 'stream': 2}   # below the resident caps
+
+
+def _run(K, knob, q, k, v, D, mask, kernel=None):
+    """mha_core under `knob`; kernel: the kernel the call must have launched."""
     old = _knob(knob)
     try:
         y = K.mha_core(q, k, v, HEADS, D ** -0.5, key_mask=mask)
         torch.cuda.synchronize()
+        assert kernel is None or K.mha_last_kernel() == kernel
         return y
     finally:
         _knob(old)
@@ -68,11 +75,11 @@ def _sdpa(q, k, v, D, mask):
     return ref
 
 
-def _check(K, D, dtype, q, k, v, mask, knob=2):
+def _check(K, D, dtype, q, k, v, mask, knob=2, kernel='stream'):
     ref = _sdpa(q, k, v, D, mask)
     qc, kc, vc, mc = q.cuda(), k.cuda(), v.cuda(), mask.cuda()
-    y = _run(K, knob, qc, kc, vc, D, mc)
-    y_fma = _run(K, 0, qc, kc, vc, D, mc)
+    y = _run(K, knob, qc, kc, vc, D, mc, kernel)
+    y_fma = _run(K, 0, qc, kc, vc, D, mc, 'fma')
     e_ref, e_fma = _rel(y, ref), _rel(y, y_fma)
     print(f'[mha_stream] D={D} {dtype} Lq={q.shape[1]} Lk={k.shape[1]} knob={knob}: vs sdpa {e_ref:.3g} '
           f'vs fma {e_fma:.3g}')
@@ -89,17 +96,28 @@ def _shapes():
     return [(1, 1), (65, 37), (16, KT), (16, KT + 1), (70, 2 * KT + 5)]
 
 
+# Each case below runs on the streaming kernel (test_stream_*: knob 2) and, every shape here being
+# below the resident caps, on the resident kernel (test_resident_*: knob 1).
+
+def _forced(K, D, Lq, Lk, dtype, kernel):
+    _check(K, D, dtype, *_inputs(D, Lq, Lk, dtype), knob=KNOB[kernel], kernel=kernel)
+
+
 @pytest.mark.parametrize('Lq,Lk', _shapes())
 @pytest.mark.parametrize('D', [32, 36])
 @pytest.mark.parametrize('dtype', DTYPES)
 def test_stream_forced(K, D, Lq, Lk, dtype):
-    _check(K, D, dtype, *_inputs(D, Lq, Lk, dtype))
+    _forced(K, D, Lq, Lk, dtype, 'stream')
 
 
-@pytest.mark.parametrize('case', ['first_tile', 'last_tile', 'dead_row'])
+@pytest.mark.parametrize('Lq,Lk', _shapes())
 @pytest.mark.parametrize('D', [32, 36])
 @pytest.mark.parametrize('dtype', DTYPES)
-def test_stream_mask_edges(K, D, dtype, case):
+def test_resident_forced(K, D, Lq, Lk, dtype):
+    _forced(K, D, Lq, Lk, dtype, 'resident')
+
+
+def _mask_edges(K, D, dtype, case, kernel):
     """Whole tiles masked (the running max stays -inf through the first tile / is untouched by
     the last) and a batch row with no live key: exactly 0, as the FMA kernel."""
     KT = K.MHA_STREAM_KT
@@ -112,10 +130,24 @@ def test_stream_mask_edges(K, D, dtype, case):
         mask[:, 2 * KT:] = True
     else:
         mask[1] = True
-    y, y_fma = _check(K, D, dtype, q, k, v, mask)
+    y, y_fma = _check(K, D, dtype, q, k, v, mask, knob=KNOB[kernel], kernel=kernel)
     if case == 'dead_row':
         assert (y[1] == 0).all() and (y_fma[1] == 0).all()
         assert y[0].abs().max() > 0 and y[2].abs().max() > 0
+
+
+@pytest.mark.parametrize('case', ['first_tile', 'last_tile', 'dead_row'])
+@pytest.mark.parametrize('D', [32, 36])
+@pytest.mark.parametrize('dtype', DTYPES)
+def test_stream_mask_edges(K, D, dtype, case):
+    _mask_edges(K, D, dtype, case, 'stream')
+
+
+@pytest.mark.parametrize('case', ['first_tile', 'last_tile', 'dead_row'])
+@pytest.mark.parametrize('D', [32, 36])
+@pytest.mark.parametrize('dtype', DTYPES)
+def test_resident_mask_edges(K, D, dtype, case):
+    _mask_edges(K, D, dtype, case, 'resident')
 
 
 @pytest.mark.parametrize('D,Lq,Lk', [(32, 300, 385), (36, 500, 641), (32, 651, 651), (36, 651, 651)])
@@ -125,27 +157,35 @@ def test_stream_natural_dispatch(K, D, Lq, Lk, dtype):
     run), no longer the FMA kernel."""
     assert Lk > K.MHA_RESIDENT_MAXK[D]
     q, k, v, mask = _inputs(D, Lq, Lk, dtype, seed=2)
-    y, y_fma = _check(K, D, dtype, q, k, v, mask, knob=1)
-    y2 = _run(K, 2, q.cuda(), k.cuda(), v.cuda(), D, mask.cuda())
+    y, y_fma = _check(K, D, dtype, q, k, v, mask, knob=1, kernel='stream')
+    y2 = _run(K, 2, q.cuda(), k.cuda(), v.cuda(), D, mask.cuda(), 'stream')
     assert torch.equal(y, y2)
     assert not torch.equal(y, y_fma)
+
+
+def _resident_equals_stream(K, D, dtype, Lk):
+    q, k, v, mask = _inputs(D, 40, Lk, dtype, seed=3)
+    y, _ = _check(K, D, dtype, q, k, v, mask, knob=1, kernel='resident')
+    y2 = _run(K, 2, q.cuda(), k.cuda(), v.cuda(), D, mask.cuda(), 'stream')
+    assert torch.equal(y2, y)
 
 
 @pytest.mark.parametrize('D', [32, 36])
 @pytest.mark.parametrize('dtype', DTYPES)
 def test_stream_resident_sizes_keep_resident_kernel(K, D, dtype):
-    """At the caps the default dispatch still runs the resident kernel: same block arithmetic in
-    the same order, so the forced streaming run agrees to the kernels' common bound."""
-    Lk = K.MHA_RESIDENT_MAXK[D]
-    q, k, v, mask = _inputs(D, 40, Lk, dtype, seed=3)
-    y, _ = _check(K, D, dtype, q, k, v, mask, knob=1)
-    y2 = _run(K, 2, q.cuda(), k.cuda(), v.cuda(), D, mask.cuda())
-    assert _rel(y2, y) < TOL[dtype]
+    """At the caps the default dispatch still runs the resident kernel: the same block step over
+    the same blocks in the same order, so the forced streaming run gives the same bits."""
+    _resident_equals_stream(K, D, dtype, K.MHA_RESIDENT_MAXK[D])
 
 
 @pytest.mark.parametrize('D', [32, 36])
 @pytest.mark.parametrize('dtype', DTYPES)
-def test_stream_strided_qk(K, D, dtype):
+def test_resident_small_equals_stream(K, D, dtype):
+    """The same at 37 keys: a ragged second block, a partial first tile."""
+    _resident_equals_stream(K, D, dtype, 37)
+
+
+def _strided_qk(K, D, dtype, kernel):
     """q and k as the two halves of one (B, L, 2E) projection (row stride 2E), as the models'
     fused q|k GEMM produces them."""
     E, L = HEADS * D, K.MHA_STREAM_KT + 1
@@ -156,10 +196,22 @@ def test_stream_strided_qk(K, D, dtype):
     mask[:, 0] = False
     ref = _sdpa(qk[..., :E], qk[..., E:], v, D, mask)
     qkc = qk.cuda()
-    y = _run(K, 2, qkc[..., :E], qkc[..., E:], v.cuda(), D, mask.cuda())
-    y_fma = _run(K, 0, qkc[..., :E], qkc[..., E:], v.cuda(), D, mask.cuda())
+    y = _run(K, KNOB[kernel], qkc[..., :E], qkc[..., E:], v.cuda(), D, mask.cuda(), kernel)
+    y_fma = _run(K, 0, qkc[..., :E], qkc[..., E:], v.cuda(), D, mask.cuda(), 'fma')
     assert _rel(y, ref) < TOL[dtype]
     assert _rel(y, y_fma) < TOL[dtype]
+
+
+@pytest.mark.parametrize('D', [32, 36])
+@pytest.mark.parametrize('dtype', DTYPES)
+def test_stream_strided_qk(K, D, dtype):
+    _strided_qk(K, D, dtype, 'stream')
+
+
+@pytest.mark.parametrize('D', [32, 36])
+@pytest.mark.parametrize('dtype', DTYPES)
+def test_resident_strided_qk(K, D, dtype):
+    _strided_qk(K, D, dtype, 'resident')
 
 
 @pytest.mark.parametrize('D', [32, 36])
@@ -167,15 +219,25 @@ def test_stream_knob_leaves_fp32_on_fma(K, D):
     """fp32 is not the streaming kernel's: under knob 2 it still runs the FMA kernel."""
     q, k, v, mask = _inputs(D, 70, 2 * K.MHA_STREAM_KT + 5, torch.float32, seed=4)
     ref = _sdpa(q, k, v, D, mask)
-    y = _run(K, 2, q.cuda(), k.cuda(), v.cuda(), D, mask.cuda())
+    y = _run(K, 2, q.cuda(), k.cuda(), v.cuda(), D, mask.cuda(), 'fma')
     assert _rel(y, ref) < 1e-5
-    assert torch.equal(y, _run(K, 0, q.cuda(), k.cuda(), v.cuda(), D, mask.cuda()))
+    assert torch.equal(y, _run(K, 0, q.cuda(), k.cuda(), v.cuda(), D, mask.cuda(), 'fma'))
+
+
+def _deterministic(K, D, kernel):
+    q, k, v, mask = (t.cuda() for t in _inputs(D, 70, 2 * K.MHA_STREAM_KT + 5, torch.bfloat16, seed=5))
+    knob = KNOB[kernel]
+    assert torch.equal(_run(K, knob, q, k, v, D, mask, kernel), _run(K, knob, q, k, v, D, mask, kernel))
 
 
 @pytest.mark.parametrize('D', [32, 36])
 def test_stream_deterministic(K, D):
-    q, k, v, mask = (t.cuda() for t in _inputs(D, 70, 2 * K.MHA_STREAM_KT + 5, torch.bfloat16, seed=5))
-    assert torch.equal(_run(K, 2, q, k, v, D, mask), _run(K, 2, q, k, v, D, mask))
+    _deterministic(K, D, 'stream')
+
+
+@pytest.mark.parametrize('D', [32, 36])
+def test_resident_deterministic(K, D):
+    _deterministic(K, D, 'resident')
 
 
 def test_knob_returns_previous_setting():

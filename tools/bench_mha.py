@@ -1,11 +1,12 @@
-"""Microbenchmark of the dense attention core (`kernels.mha_core`) at vanilla DETR's shapes: one
-800x1333 frame is a 25x42 stride-32 map = 1050 keys, batch 16, 8 heads, for the encoder
-self-attention (Lq = Lk = 1050) and the decoder cross-attention (Lq = 100 at d 256, 500 at d 288).
+"""Microbenchmark of the attention core (`kernels.mha_core`), batch 16, 8 heads, at vanilla DETR's
+shapes -- one 800x1333 frame is a 25x42 stride-32 map = 1050 keys, for the encoder self-attention
+(Lq = Lk = 1050) and the decoder cross-attention (Lq = 100 at d 256, 500 at d 288) -- and at the
+decoder query self-attention shapes of the Deformable DETR models (300 queries at d 256; 500 + 20
+and 500 x 640 at d 288), whose keys stay resident in LDS.
 
-Each shape is timed on the default dispatch (above the resident kernels' caps: the key-streaming
-MFMA kernel of csrc/attn.hip) and with kinet_mha_set_mfma(0) (the FMA kernel, which served these
-shapes before the streaming kernel existed), alternating the two in one process: per variant a
-warm-up, then `--repeats` windows of `--iters` calls between HIP events, median and spread of the
+Each shape is timed on the default dispatch (the MFMA kernels of csrc/attn.hip: `kernel` names
+which one ran) and with kinet_mha_set_mfma(0) (the FMA kernel), alternating the two in one
+process: per variant a warm-up, then `--repeats` windows of `--iters` calls between HIP events, median and spread of the
 windows.  The outputs of the two are compared on the timed inputs first.  One JSON line per shape;
 `mfma_peak_frac` is the useful attention FLOPs (4 * B * heads * Lq * Lk * head_dim, padding
 excluded) per second over the 2.5 PFLOP/s dense 16-bit MFMA peak.
@@ -31,6 +32,9 @@ SHAPES = [  # (tag, head_dim, Lq, Lk)
     ('enc_self_d36', 36, 1050, 1050),
     ('dec_cross_d32', 32, 100, 1050),
     ('dec_cross_d36', 36, 500, 1050),
+    ('dec_self_d32', 32, 300, 300),
+    ('dec_self_d36', 36, 520, 520),
+    ('dec_self_d36_640', 36, 500, 640),
 ]
 BATCH, HEADS = 16, 8
 
@@ -63,6 +67,8 @@ def bench_shape(tag, D, Lq, Lk, dtype, iters, repeats):
             lib.kinet_mha_set_mfma(old)
 
     run(1)
+    # (a library from before kinet_mha_last_kernel, under KINET_AMD_LIB: no name)
+    kernel = K.mha_last_kernel() if _native.exported('kinet_mha_last_kernel') else None
     y = out.float().clone()
     run(0)
     y_fma = out.float().clone()
@@ -78,8 +84,8 @@ def bench_shape(tag, D, Lq, Lk, dtype, iters, repeats):
     flops = 4.0 * BATCH * HEADS * Lq * Lk * D
     us, us_fma = statistics.median(times[1]), statistics.median(times[0])
     return {'shape': tag, 'dtype': str(dtype).replace('torch.', ''), 'B': BATCH, 'heads': HEADS, 'head_dim': D,
-            'Lq': Lq, 'Lk': Lk, 'default_us': round(us, 2), 'default_us_min_max': [round(min(times[1]), 2),
-                                                                                    round(max(times[1]), 2)],
+            'Lq': Lq, 'Lk': Lk, 'kernel': kernel, 'default_us': round(us, 2),
+            'default_us_min_max': [round(min(times[1]), 2), round(max(times[1]), 2)],
             'fma_us': round(us_fma, 2), 'fma_us_min_max': [round(min(times[0]), 2), round(max(times[0]), 2)],
             'speedup': round(us_fma / us, 2), 'default_tflops': round(flops / us / 1e6, 1),
             'mfma_peak_frac': round(flops / (us * 1e-6) / PEAK_16BIT_FLOPS, 4),
