@@ -1,7 +1,7 @@
 """High-precision restatements of the small kernels' operations, shared by
 test_ops_direct_gpu.py / test_grad_prims_gpu.py / test_grad_norm_attn_gpu.py /
-test_train_ops_direct_gpu.py / test_gemm_tiles_direct_gpu.py / test_msda_direct_gpu.py and checked on the CPU by
-test_direct_refs_cpu.py.
+test_train_ops_direct_gpu.py / test_gemm_tiles_direct_gpu.py / test_msda_direct_gpu.py / test_attn_direct_gpu.py
+and checked on the CPU by test_direct_refs_cpu.py.
 Plain torch on the CPU; nothing here touches the GPU or the native library."""
 import functools
 import math
@@ -2278,3 +2278,553 @@ def ffn_direct_generic_tol(case, d, ref, dtype, ln):
         return {'y': out_round_bound(E, ref['pre'], dtype)}
     _, tol = ffn_ln_tol(ref['pre'], d['ln'], dtype)
     return {'y': ln_propagate(E, ref['pre'], d['ln'][0].to(dev), d['ln'][2]) + tol.to(dev)}
+
+
+# ------------------------------------------------------- attention forward, kernel by kernel
+# Cases, expected values and the bound of tests/test_attn_direct_gpu.py (csrc/attn.hip: mha_resident_kernel,
+# mha_stream_kernel; csrc/ops.hip: mha_kernel).  Every case has ATTN_B batches with different masks and ATTN_HEADS
+# heads (odd head offsets: at head_dim 36 an odd head starts 8-byte, not 16-byte aligned); codes, values and the
+# query -> key assignment differ per batch, head and query.
+ATTN_KT = 128                       # keys per tile of the streaming kernel (kernels.MHA_STREAM_KT)
+ATTN_RESIDENT_MAXK = {32: 384, 36: 640}
+ATTN_B, ATTN_HEADS = 2, 3
+ATTN_U = {torch.float32: 2.0 ** -24, torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}   # unit roundoffs
+ATTN_INST = ([(kern, dt, D) for kern in ('resident', 'stream') for dt in (torch.bfloat16, torch.float16) for D in (32, 36)]
+             + [('fma', dt, D) for dt in (torch.float32, torch.bfloat16, torch.float16) for D in (16, 32, 36, 64)])
+# (Lq, Lk): every Lk of {1, 31, 32, 33, 37, KT - 1, KT, KT + 1, 2 KT + 5, 3 KT} and every Lq of {1, 15, 16, 17, 63, 64,
+# 65, 129}; the two three-tile cases have enough queries to select every slot of a block in each tile
+ATTN_SHAPES = [(1, 1), (15, 31), (16, 32), (17, 33), (63, 37), (64, ATTN_KT - 1), (65, ATTN_KT), (129, ATTN_KT + 1),
+               (129, 2 * ATTN_KT + 5), (129, 3 * ATTN_KT)]
+ATTN_FMA_SHAPES = [(17, 63), (64, 64), (65, 65), (129, 129)]        # the FMA kernel's 64-key tile
+ATTN_MAIN = (129, 2 * ATTN_KT + 5)
+
+
+def attn_shapes(kernel, D):
+    """The (Lq, Lk) of one instantiation: the common list, the FMA kernel's tile edges, the resident caps (cap - 31,
+    cap) and, as 'stream', cap + 1 -- which the default knob sends there."""
+    s = list(ATTN_SHAPES)
+    if kernel == 'fma':
+        s += ATTN_FMA_SHAPES
+    if kernel == 'resident':
+        s += [(16, ATTN_RESIDENT_MAXK[D] - 31), (65, ATTN_RESIDENT_MAXK[D])]
+    if kernel == 'stream':
+        s += [(65, ATTN_RESIDENT_MAXK[D] + 1)]
+    return s
+
+
+def _attn_split(t, heads):
+    B, L, E = t.shape
+    return t.view(B, L, heads, E // heads).transpose(1, 2)
+
+
+def _attn_merge(t):
+    B, H, L, D = t.shape
+    return t.transpose(1, 2).reshape(B, L, H * D)
+
+
+def attn_bits(t):
+    """The bit patterns of t as integers (exact comparisons: NaN-free, +0 != -0)."""
+    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+
+
+_ATTN_FMT = {torch.float32: (torch.int32, 8, 23, 227), torch.bfloat16: (torch.int16, 8, 7, 227),
+             torch.float16: (torch.int16, 5, 10, 30)}
+
+
+def attn_random_values(shape, dtype, g):
+    """Arbitrary finite bit patterns of dtype, subnormals included: sign, exponent field 0 .. emax, mantissa, each
+    uniform.  bf16 / f32 stay below 2^101, so that no f32 partial sum of the kernels can overflow (a partial O^T
+    holds p v of keys that a later rescale by exactly 0 removes: inf * 0 would be NaN in any online softmax); -0 is
+    left out (x + -0 = +0 in the accumulator)."""
+    it, eb, mb, emax = _ATTN_FMT[dtype]
+    sign = torch.randint(0, 2, shape, generator=g)
+    ex = torch.randint(0, emax + 1, shape, generator=g)
+    mant = torch.randint(0, 2 ** mb, shape, generator=g)
+    bits = (sign << (eb + mb)) | (ex << mb) | mant
+    bits = torch.where((ex == 0) & (mant == 0), torch.zeros_like(bits), bits)
+    width = 32 if it == torch.int32 else 16
+    bits = torch.where(bits >= 2 ** (width - 1), bits - 2 ** width, bits)
+    return bits.to(it).view(dtype)
+
+
+def attn_special_rows(D, dtype):
+    """(4, D): zeros; negatives; the largest finite value with alternating sign; subnormals (the smallest and the
+    largest, alternating sign)."""
+    fi = torch.finfo(dtype)
+    alt = torch.tensor([1.0, -1.0]).repeat(D)[:D].double()
+    neg = -(torch.arange(D).double() % 7 + 1) * 0.375
+    big = alt * fi.max
+    tiny = fi.smallest_normal * 2.0 ** -{torch.float32: 23, torch.bfloat16: 7, torch.float16: 10}[dtype]
+    sub = torch.where(torch.arange(D) % 4 < 2, torch.tensor(tiny, dtype=torch.float64),
+                      torch.tensor(fi.smallest_normal - tiny, dtype=torch.float64)) * alt
+    rows = torch.stack([torch.zeros(D, dtype=torch.float64), neg, big, sub]).to(dtype)
+    assert torch.equal(rows.double(), torch.stack([torch.zeros(D, dtype=torch.float64), neg, big, sub]))
+    return rows
+
+
+def _attn_codes(n, D, g):
+    """n distinct +-1 codewords of length D, (n, D) int64."""
+    low = torch.randperm(2 ** 16, generator=g)[:n]
+    bits = [(low >> d) & 1 for d in range(min(D, 16))] + [torch.randint(0, 2, (n,), generator=g) for _ in range(D - 16)]
+    return torch.stack(bits, 1) * 2 - 1
+
+
+def attn_pair_keys(D, Lk, kt=ATTN_KT):
+    """Key indices (lo[d], hi[d]) of the pair that differs in head dim d only, d < min(D, Lk // 2): lo in the first
+    blocks, hi from the last block of the second tile where that fits (so one of the pair sits blocks, and a tile,
+    before the other), and the 'middle' block index (None below three blocks)."""
+    npair = min(D, Lk // 2)
+    nblk = (Lk + 31) // 32
+    mid = min(2 * kt // 32 - 1, nblk - 2) if nblk >= 3 else None
+    lo = list(range(npair))
+    if mid is not None and mid * 32 >= npair and mid * 32 + npair <= Lk:
+        hi = list(range(mid * 32, mid * 32 + npair))
+    else:
+        hi = list(range(npair, 2 * npair))
+    return lo, hi, mid
+
+
+def _attn_priority(D, Lk, kt):
+    lo, hi, mid = attn_pair_keys(D, Lk, kt)
+    nblk = (Lk + 31) // 32
+    order = lo + hi + list(range(min(32, Lk)))
+    if mid is not None:
+        order += list(range(mid * 32, mid * 32 + 32))
+    order += list(range((nblk - 1) * 32, Lk)) + list(range(Lk))
+    return list(dict.fromkeys(order))
+
+
+def _attn_select_mask(D, Lk, mode, kt):
+    """The key masks of a selection case (B, Lk).  'pairs': in batch b the pair member a_d (lo[d] for even d, hi[d]
+    for odd d) of every d = b mod 3 -- its query then selects the other member, the nearest live key -- and every
+    7th key outside the pairs.  'edges': batch 0 masks the first block, a middle block and the last (ragged) block,
+    batch 1 the whole first tile (the first block below two tiles).  'last': batch 0 keeps key Lk - 1 only, batch 1
+    nothing."""
+    mask = torch.zeros(ATTN_B, Lk, dtype=torch.bool)
+    lo, hi, _ = attn_pair_keys(D, Lk, kt)
+    nblk = (Lk + 31) // 32
+    if mode == 'pairs':
+        paired = set(lo + hi)
+        for b in range(ATTN_B):
+            for d in range(len(lo)):
+                if d % 3 == b:
+                    mask[b, lo[d] if d % 2 == 0 else hi[d]] = True
+            for j in range(3 + b, Lk, 7):
+                if j not in paired:
+                    mask[b, j] = True
+    elif mode == 'edges':
+        mask[0, :32] = True
+        mask[0, (nblk // 2) * 32:(nblk // 2) * 32 + 32] = True
+        mask[0, (nblk - 1) * 32:] = True
+        mask[1, :kt if Lk > kt else 32] = True
+    elif mode == 'last':
+        mask[0, :Lk - 1] = True
+        mask[1] = True
+    return mask
+
+
+def _attn_select_try(D, Lq, Lk, dtype, mode, kt, seed):
+    B, H = ATTN_B, ATTN_HEADS
+    g = torch.Generator().manual_seed(77003 * seed + 131 * D + 17 * Lq + Lk + {'pairs': 0, 'edges': 1, 'last': 2}[mode] * 7919)
+    lo, hi, mid = attn_pair_keys(D, Lk, kt)
+    codes = torch.stack([torch.stack([_attn_codes(Lk, D, g) for _ in range(H)]) for _ in range(B)])   # (B, H, Lk, D)
+    for d in range(len(lo)):
+        codes[:, :, hi[d]] = codes[:, :, lo[d]]
+        codes[:, :, hi[d], d] *= -1
+    mask = _attn_select_mask(D, Lk, mode, kt)
+    prio = _attn_priority(D, Lk, kt)
+    target = torch.zeros(B, H, Lq, dtype=torch.long)
+    for b in range(B):
+        # a masked pair member stays a target: its query selects the other member
+        live = [j for j in prio if not mask[b, j] or (mode == 'pairs' and j in set(lo + hi))]
+        tl = live if live else prio
+        for h in range(H):
+            perm = torch.randperm(Lq, generator=g)
+            target[b, h] = torch.tensor([tl[int(i) % len(tl)] for i in perm])
+    qcode = torch.gather(codes, 2, target[..., None].expand(B, H, Lq, D))
+    S = 64 * (qcode @ codes.transpose(-1, -2))                                         # exact integers
+    Sm = S.masked_fill(mask[:, None, None, :], -2 ** 40)
+    top = Sm.topk(min(2, Lk), -1).values
+    alive = ~mask.all(1)
+    if Lk > 1 and (top[alive][..., 0] - top[alive][..., 1]).min() < 128:
+        return None
+    sel = Sm.argmax(-1)                                                                 # (B, H, Lq)
+    v = attn_random_values((B, H, Lk, D), dtype, g)
+    special = attn_special_rows(D, dtype)
+    for i in range(min(4, Lk)):
+        v[:, :, prio[i]] = special[i]
+    huge = special[2]
+    v = torch.where(mask[:, None, :, None], huge.expand(B, H, Lk, D), v)
+    expected = torch.gather(v, 2, sel[..., None].expand(B, H, Lq, D))
+    expected = torch.where(alive[:, None, None, None], expected, torch.zeros_like(expected))
+    return {'q': _attn_merge(64 * qcode).to(dtype), 'k': _attn_merge(codes).to(dtype), 'v': _attn_merge(v), 'mask': mask,
+            'scale': 1.0, 'sel': sel, 'target': target, 'expected': _attn_merge(expected), 'codes': codes, 'scores': S,
+            'heads': H, 'mode': mode}
+
+
+@functools.lru_cache(maxsize=None)
+def attn_select_case(D, Lq, Lk, dtype, mode='pairs', kt=ATTN_KT):
+    """Class 1.  Keys are distinct +-1 codewords, query i is 64 code(target(i)), scale = 1: every score is an integer
+    multiple of 128 apart from every other (64 (D - 2 hamming)), exact in f32, so the softmax is exactly one-hot
+    on the best live key `sel` and the output row is v[sel] bit for bit.  The builder re-seeds until the best live
+    key of every query leads by >= 128 (the masked-best-match queries need a unique nearest live key)."""
+    for seed in range(32):
+        case = _attn_select_try(D, Lq, Lk, dtype, mode, kt, seed)
+        if case is not None:
+            return case
+    raise AssertionError('attn_select_case: no seed gives a score gap of 128')
+
+
+def attn_tie_groups(kt=ATTN_KT):
+    """Class 2's tied key sets at Lk = 2 kt + 5, name -> key indices (disjoint)."""
+    b3, b7 = kt - 32, 2 * kt - 32           # the last blocks of tiles 0 and 1
+    groups = {
+        'lane8': [4, 5, 6, 7, 20, 21, 22, 23],                  # the eight keys of lane group 1 of block 0
+        'lane4': [8, 9, 10, 11],
+        'lane2': [12, 28],
+        'groups4': [b3, b3 + 4, b3 + 8, b3 + 12],                # one key of each lane group: the two cross-lane sums
+        'groups16': list(range(b7, b7 + 16)),
+        'block32': list(range(kt + 64, kt + 96)),
+        'consec64': list(range(32, 96)),                         # two whole consecutive blocks: alpha = 1 between them
+        'consec2': [kt + 5, kt + 37],
+        'edge4': [kt - 2, kt - 1, kt, kt + 1],                   # across the edge of tiles 0 and 1
+        'tiles02_2': [3, 2 * kt + 3],                            # tiles 0 and 2: the same buffer, reused
+        'tiles02_8': [1, 2, 13, 14, 2 * kt, 2 * kt + 1, 2 * kt + 2, 2 * kt + 4],
+    }
+    flat = [j for ks in groups.values() for j in ks]
+    assert len(flat) == len(set(flat)) and max(flat) < 2 * kt + 5
+    return groups
+
+
+ATTN_TIE_DECOY = (15, 'lane2')              # a masked key that carries a group's codeword and huge values
+
+
+@functools.lru_cache(maxsize=None)
+def attn_tie_case(D, Lq, dtype, kt=ATTN_KT):
+    """Class 2.  As class 1, but the n in {2, .., 64} keys of a group share the selected codeword: p is 1 on n keys, l
+    is n, the output is the mean of their values -- nonzero multiples of 1/4 up to 3/4, so the f32 sums are exact,
+    the mean (an integer of at most 8 bits over 4 n) is representable in bf16 / f16 and survives the final rounding."""
+    B, H, Lk = ATTN_B, ATTN_HEADS, 2 * kt + 5
+    groups = attn_tie_groups(kt)
+    names = sorted(groups)
+    for seed in range(32):
+        g = torch.Generator().manual_seed(90001 * seed + 131 * D + Lq)
+        codes = torch.stack([torch.stack([_attn_codes(Lk, D, g) for _ in range(H)]) for _ in range(B)])
+        for ks in groups.values():
+            codes[:, :, ks] = codes[:, :, ks[:1]]
+        mask = torch.zeros(B, Lk, dtype=torch.bool)
+        codes[:, :, ATTN_TIE_DECOY[0]] = codes[:, :, groups[ATTN_TIE_DECOY[1]][0]]
+        mask[:, ATTN_TIE_DECOY[0]] = True
+        grouped = {j for ks in groups.values() for j in ks}
+        for b in range(B):
+            for j in range(30 + b, Lk, 9):
+                if j not in grouped:
+                    mask[b, j] = True
+        gi = torch.stack([torch.stack([torch.randperm(Lq, generator=g) % len(names) for _ in range(H)]) for _ in range(B)])
+        first = torch.tensor([groups[n][0] for n in names])[gi]
+        qcode = torch.gather(codes, 2, first[..., None].expand(B, H, Lq, D))
+        S = 64 * (qcode @ codes.transpose(-1, -2))
+        Sm = S.masked_fill(mask[:, None, None, :], -2 ** 40)
+        best = Sm.amax(-1, keepdim=True)
+        tied = Sm == best
+        size = torch.tensor([len(groups[n]) for n in names])[gi]
+        rest = Sm.masked_fill(tied, -2 ** 40).amax(-1, keepdim=True)
+        if not torch.equal(tied.sum(-1), size) or (best - rest).min() < 128:
+            continue
+        v = attn_random_values((B, H, Lk, D), dtype, g)
+        m4 = (torch.randint(1, 4, (B, H, Lk, D), generator=g) * (torch.randint(0, 2, (B, H, Lk, D), generator=g) * 2 - 1)) / 4.0
+        gmask = torch.zeros(Lk, dtype=torch.bool)
+        gmask[sorted(grouped)] = True
+        v = torch.where(gmask[None, None, :, None], m4.to(dtype), v)
+        v = torch.where(mask[:, None, :, None], attn_special_rows(D, dtype)[2].expand(B, H, Lk, D), v)
+        mean = (tied.double() @ v.double()) / size[..., None].double()
+        expected = mean.to(dtype)
+        assert torch.equal(expected.double(), mean), 'attn_tie_case: a mean is not representable'
+        return {'q': _attn_merge(64 * qcode).to(dtype), 'k': _attn_merge(codes).to(dtype), 'v': _attn_merge(v),
+                'mask': mask, 'scale': 1.0, 'group': gi, 'names': names, 'tied': tied, 'expected': _attn_merge(expected),
+                'mean64': _attn_merge(mean), 'scores': S, 'heads': H}
+    raise AssertionError('attn_tie_case: no seed gives a score gap of 128')
+
+
+ATTN_VARIANTS = ('plain', 'wide', 'offset')
+ATTN_MASKS = ('random', 'none', 'allfalse', 'first_block', 'first_tile', 'middle_block', 'last_block', 'last_only',
+              'dead_batch')
+
+
+def attn_generic_mask(Lk, mode, g, kt=ATTN_KT):
+    if mode == 'none':
+        return None
+    mask = torch.zeros(ATTN_B, Lk, dtype=torch.bool)
+    nblk = (Lk + 31) // 32
+    if mode == 'random':
+        mask = torch.rand(ATTN_B, Lk, generator=g) < 0.2
+        mask[0, 0] = False
+        mask[1, Lk - 1] = False
+    elif mode == 'first_block':                  # m stays -inf through the first block (batch 1: the first two)
+        mask[0, :32] = True
+        mask[1, :64] = True
+    elif mode == 'first_tile':
+        mask[:, :kt] = True
+        mask[1, kt:kt + 7] = True
+    elif mode == 'middle_block':
+        mask[0, (nblk // 2) * 32:(nblk // 2) * 32 + 32] = True
+        mask[1, 32:64] = True
+    elif mode == 'last_block':
+        mask[0, (nblk - 1) * 32:] = True
+        mask[1, (nblk - 2) * 32:] = True
+    elif mode == 'last_only':
+        mask[:, :Lk - 1] = True
+    elif mode == 'dead_batch':
+        mask[1] = True
+        mask[0, 5] = True
+    return mask
+
+
+@functools.lru_cache(maxsize=None)
+def attn_generic_case(D, Lq, Lk, dtype, variant='plain', maskmode='random'):
+    """Class 3: N(0, 1) operands rounded to dtype, scale D^-0.5.  'wide': q times 15, so scores reach +-60; 'offset':
+    dim 0 of every key is 4 and dim 0 of every query 50 sqrt(D), a common score offset of 200 that the softmax
+    cancels and the f32 score arithmetic does not.  With the f64 reference of the rounded operands, the bound's
+    ingredients and torch's CPU f32 SDPA."""
+    H = ATTN_HEADS
+    q, k, v, _ = attn_case(ATTN_B, H, D, Lq, Lk, seed=5 + ATTN_VARIANTS.index(variant), qscale=15.0 if variant == 'wide' else 1.0)
+    q, k, v = q.clone(), k.clone(), v.clone()
+    if variant == 'offset':
+        k[..., ::D] = 4.0
+        q[..., ::D] = 50.0 * math.sqrt(D)
+    q, k, v = q.to(dtype), k.to(dtype), v.to(dtype)
+    g = torch.Generator().manual_seed(D * 31 + Lk + ATTN_MASKS.index(maskmode) * 1009)
+    mask = attn_generic_mask(Lk, maskmode, g)
+    scale = D ** -0.5
+    ref = attn_ref(q, k, v, torch.zeros_like(q), H, scale, key_mask=mask)
+    case = {'q': q, 'k': k, 'v': v, 'mask': mask, 'scale': scale, 'heads': H, 'o': ref['o'], 'oA': ref['oA']}
+    case['sdpa'] = attn_sdpa_f32(q, k, v, H, scale, mask)
+    return case
+
+
+def attn_sdpa_f32(q, k, v, heads, scale, mask):
+    """torch's CPU f32 scaled_dot_product_attention on the same (rounded) operands, 0 on a batch without a live key:
+    the yardstick."""
+    m = None
+    dead = torch.zeros(q.shape[0], dtype=torch.bool)
+    if mask is not None:
+        dead = mask.all(1)
+        m = mask.clone()
+        m[dead] = False
+        m = ~m[:, None, None, :]
+    o = F.scaled_dot_product_attention(_attn_split(q.float(), heads), _attn_split(k.float(), heads),
+                                       _attn_split(v.float(), heads), attn_mask=m, scale=scale)
+    o = _attn_merge(o).double()
+    o[dead] = 0
+    return o
+
+
+def attn_fwd_bound(case, kernel, dtype):
+    """Per-element bound on |kernel output - f64 attention| of a class-3 case, from the kernels' arithmetic; u = 2^-24
+    (f32), u16 the unit roundoff of the 16-bit type (2^-8 bf16, 2^-11 f16).  The kernels compute, key block by key
+    block (32 keys: attn_block; one key: the FMA kernel), s = scale q.k (+ 0 / -inf key bias), the running max m,
+    p = __expf(s - m), l = l alpha + sum p, O = O alpha + p v with alpha = __expf(m_old - m_new), and at the end
+    O / l rounded to the output type.  With P the exact softmax, o = P V, oA = P |V| (attn_ref):
+
+    (a) output rounding: u_out |o|, plus half the subnormal spacing of the output type (2^-25 in f16).
+    (b) MFMA kernels only: p is rounded to the 16-bit type as the B operand of O^T += V^T P^T while l sums the
+        unrounded p: relative u16 on every normal p -- u16 oA -- and an absolute part for p below the smallest
+        normal.  Facts this rests on: Cvt<f16_t>::from is a plain float -> _Float16 cast (v_cvt_f16_f32, round to
+        nearest even; the kernels are built with hipcc's default mode, which keeps f16 and f32 subnormals), and
+        the MFMA never flushes its C / D and is modelled as taking the f16 subnormal operand as it is: the
+        absolute error is half the subnormal spacing, 2^-25 per live key, scaled by 1 / l (l >= 1 in units of the
+        largest p).  f32_to_bf16 is a plain __bf16 cast (v_cvt_pk_bf16_f32: round to nearest even, NaN kept);
+        bf16 shares f32's exponent range, so a p below 2^-126 is already an f32 subnormal: 2^-126 per live key
+        covers either treatment.  The 257-key case of attn_subnormal_case tells 'kept' from 'flushed' in f16:
+        flushed, the output misses by 2^-8.
+    (c) score error.  The products of two 16-bit values are exact in f32; S^T accumulates n = 32 KSTEPS of them
+        (64 at head_dim 36: the padded length), each addition committing at most one ulp (2 u, which covers
+        truncation as well as round to nearest), then one rounding of the scale multiply; the key bias adds 0 or
+        -inf exactly.  The FMA kernel rounds q scale once, then runs D / 4 fma and two shuffle additions: n = D / 4
+        + 2.  ds = (2 n + 2) u scale sum_d |q_d k_d| per (query, key); an error of the running max itself is common
+        to numerator and denominator and cancels.
+    (d) __expf(x) = exp2(x log2 e): the rounding of s - m and of the argument, 2 |x| u, and 4 u for the result's
+        ulps.  Over a key's own exp and the later rescales, the arguments add up to exactly m_final - s, so
+        a key's weight has the relative error e = ds + 2 (m - s) u + 4 u (steps + 1), steps = ceil(Lk / 32) (FMA:
+        ceil(Lk / 4) keys per wave + the merge).
+        (c) and (d) enter numerator and denominator: sum_j P_j (|v_j| + |o|) e_j, which is at most 2 max(e) oA.
+    (e) f32 accumulation of l and O^T: a multiply and an add per step, and the 32-term sum of an MFMA:
+        2 (2 steps + 32) u oA, and 3 u |o| for 1 / l and the final product.
+    Elements with oA = 0 (no live key, or only zero values) must be exactly 0."""
+    q, k, v, mask, scale, H = (case[n] for n in ('q', 'k', 'v', 'mask', 'scale', 'heads'))
+    D = q.shape[-1] // H
+    Lk = k.shape[1]
+    u = U32
+    Q, K_, V = _attn_split(q.double(), H), _attn_split(k.double(), H), _attn_split(v.double(), H)
+    S = Q @ K_.transpose(-1, -2) * scale
+    SA = Q.abs() @ K_.abs().transpose(-1, -2) * scale
+    live = torch.ones(q.shape[0], Lk, dtype=torch.bool) if mask is None else ~mask
+    S = S.masked_fill(~live[:, None, None, :], float('-inf'))
+    mx = S.amax(-1, keepdim=True)
+    mx = torch.where(torch.isinf(mx), torch.zeros_like(mx), mx)
+    e = (S - mx).exp()
+    den = e.sum(-1, keepdim=True)
+    P = e / torch.where(den > 0, den, torch.ones_like(den))
+    mfma = kernel != 'fma'
+    n = 32 * (2 if D == 36 else 1) if mfma else D // 4 + 2
+    steps = (Lk + 31) // 32 if mfma else (Lk + 3) // 4 + 1
+    X = torch.where(P > 0, mx - S, torch.zeros_like(S))
+    ej = (2 * n + 2) * u * SA + 2 * X * u + 4 * u * (steps + 1)
+    Pe = P * ej
+    o, oA = _attn_split(case['o'], H), _attn_split(case['oA'], H)
+    bound = Pe @ V.abs() + o.abs() * Pe.sum(-1, keepdim=True)
+    bound = bound + 2 * (2 * steps + 32) * u * oA + 3 * u * o.abs()
+    tiny = {torch.float32: 2.0 ** -150, torch.bfloat16: 2.0 ** -134, torch.float16: 2.0 ** -25}[dtype]
+    bound = bound + ATTN_U[dtype] * o.abs() + tiny
+    if mfma:
+        sub = {torch.bfloat16: 2.0 ** -126, torch.float16: 2.0 ** -25}[dtype]
+        absV = (live[:, None, :, None].double() * V.abs()).sum(2, keepdim=True)
+        bound = bound + ATTN_U[dtype] * oA + sub * absV / torch.where(den > 0, den, torch.ones_like(den))
+    return _attn_merge(torch.where(oA > 0, bound, torch.zeros_like(bound)))
+
+
+def attn_ratio(got64, case, bound):
+    """(worst |got - o| / bound over the elements with oA > 0, their share of all elements, whether every other
+    element is exactly 0)."""
+    cmp = case['oA'] > 0
+    err = (got64 - case['o']).abs()
+    worst = (err[cmp] / bound[cmp]).max().item() if cmp.any() else 0.0
+    return worst, cmp.double().mean().item(), bool((got64[~cmp] == 0).all())
+
+
+@functools.lru_cache(maxsize=None)
+def attn_subnormal_case(D, dtype):
+    """One key at p = 1 and 256 keys near p = 2^-16 (scale 1, q = e_0, the keys' dim 0 is 0 and -11.09), every value 1:
+    the exact output is 1.  In f16 those p are subnormal operands of P V: kept (spacing 2^-24), the kernel's sum
+    misses 1 by at most 256 2^-25; flushed, it gives 1 / (1 + 2^-8)."""
+    B, H, Lq, Lk = ATTN_B, ATTN_HEADS, 17, 257
+    E = H * D
+    q, k = torch.zeros(B, Lq, E), torch.zeros(B, Lk, E)
+    q[..., ::D] = 1.0
+    k[:, 1:, ::D] = -16 * math.log(2.0)
+    v = torch.ones(B, Lk, E)
+    return _attn_make(q.to(dtype), k.to(dtype), v.to(dtype), H, 1.0)
+
+
+def _attn_bias_parts(D, dtype, nAs, Lq=1, Lk=257):
+    """One batch of the bias case: head h has key 0 at score 0 (p = 1, value 0), nAs[h] keys of value 1 whose p sits
+    just below a rounding midpoint of the 16-bit type at 1/2 (rounded down by almost u16 relative) and value-0 keys
+    whose p sits just above it (rounded up).  scale 1; q = e_0 + 2^-10 e_1, so a key's score is k_0 + 2^-10 k_1: a
+    16-bit k_0 and its 16-bit residual place the score within 2^-18 of its target, the midpoint being 2^-13 (bf16) /
+    2^-16 (f16) away in relative terms."""
+    t = {torch.bfloat16: 8, torch.float16: 11}[dtype]
+    H = len(nAs)
+    xs = {'A': math.log((1 + 2.0 ** -t - 2.0 ** -(t + 5)) / 2), 'B': math.log((1 + 2.0 ** -t + 2.0 ** -(t + 5)) / 2)}
+    q, k, v = torch.zeros(1, Lq, H, D), torch.zeros(1, Lk, H, D), torch.zeros(1, Lk, H, D)
+    q[..., 0], q[..., 1] = 1.0, 2.0 ** -10
+    for h, nA in enumerate(nAs):
+        for j in range(1, Lk):
+            x = xs['A' if j <= nA else 'B']
+            k0 = torch.tensor(x).to(dtype).double().item()
+            k[0, j, h, 0], k[0, j, h, 1] = k0, (x - k0) * 2.0 ** 10
+        v[0, 1:nA + 1, h] = 1.0
+    return q.reshape(1, Lq, H * D).to(dtype), k.reshape(1, Lk, H * D).to(dtype), v.reshape(1, Lk, H * D).to(dtype)
+
+
+def _attn_make(q, k, v, H, scale, mask=None):
+    ref = attn_ref(q, k, v, torch.zeros_like(q), H, scale, key_mask=mask)
+    return {'q': q, 'k': k, 'v': v, 'mask': mask, 'scale': scale, 'heads': H, 'o': ref['o'], 'oA': ref['oA'],
+            'sdpa': attn_sdpa_f32(q, k, v, H, scale, mask)}
+
+
+@functools.lru_cache(maxsize=None)
+def attn_bias_case(D, dtype):
+    """The class-3 case built for the one systematic term of the bound, (b): with l summed from the unrounded p, the
+    kernels' output is low by almost u16 oA -- inside the bound.  A kernel that summed l from the rounded p would
+    be low by almost 2 u16 oA here (the value-0 keys inflate its l), and over the bound wherever the output rounding
+    goes the same way: the counts of value-1 keys per head are the first six, from 1 up, at which the f64 model of
+    that kernel is over the bound (test_direct_refs_cpu.py runs the mutation on this case)."""
+    good = []
+    for nA in range(1, 200):
+        c = _attn_make(*_attn_bias_parts(D, dtype, [nA]), 1, 1.0)
+        bound = attn_fwd_bound(c, 'resident', dtype)
+        r = [attn_ratio(attn_blockwise(c, m, True, pround=dtype).to(dtype).double(), c, bound)[0] for m in (None, 'l_rounded')]
+        if r[0] < 1.0 < r[1]:
+            good.append(nA)
+        if len(good) == ATTN_B * ATTN_HEADS:
+            break
+    assert len(good) == ATTN_B * ATTN_HEADS, good
+    parts = [_attn_bias_parts(D, dtype, good[b * ATTN_HEADS:(b + 1) * ATTN_HEADS], Lq=17) for b in range(ATTN_B)]
+    return _attn_make(*(torch.cat(t) for t in zip(*parts)), ATTN_HEADS, 1.0)
+
+
+ATTN_MUTATIONS = ('swap', 'drop_dim35', 'drop_dim0', 'mask_shift', 'skip_rescale', 'drop_block', 'l_rounded')
+
+
+def attn_blockwise(case, mut=None, arg=None, pround=None, kt=ATTN_KT):
+    """The kernels' block step restated in f64: 32-key blocks in order, running max m, l = l alpha + sum p,
+    O = O alpha + p V, O / l at the end (0 without a live key); exp(x) is 0 below -104, as in f32.  pround: a 16-bit
+    type p is rounded to for P V (l keeps the unrounded p) -- the model of the MFMA kernels.  mut, one of
+    ATTN_MUTATIONS, breaks it the way a kernel could be broken:
+      'swap' (j1, j2): two keys of one block swapped against their values;
+      'drop_dim35' / 'drop_dim0': that head dim lost from q.k;
+      'mask_shift' (b, j): the mask byte of key j of batch b applied to key j + 1;
+      'skip_rescale' i: block i does not rescale O (l is rescaled);
+      'drop_block' i: block i contributes nothing (a tile's last block, lost at the buffer swap);
+      'l_rounded': l sums the rounded p."""
+    q, k, v, mask, scale, H = (case[n] for n in ('q', 'k', 'v', 'mask', 'scale', 'heads'))
+    B, Lk = k.shape[0], k.shape[1]
+    Q, K_, V = _attn_split(q.double(), H).clone(), _attn_split(k.double(), H), _attn_split(v.double(), H).clone()
+    km = torch.zeros(B, Lk, dtype=torch.bool) if mask is None else mask.clone()
+    if mut == 'swap':
+        V[:, :, list(arg)] = V[:, :, list(arg)[::-1]]
+    elif mut in ('drop_dim35', 'drop_dim0'):
+        Q[..., int(mut[8:])] = 0
+    elif mut == 'mask_shift':
+        km[arg[0], arg[1]], km[arg[0], arg[1] + 1] = False, True
+    S = (Q @ K_.transpose(-1, -2) * scale).masked_fill(km[:, None, None, :], float('-inf'))
+    ninf = float('-inf')
+
+    def ex(x):
+        return torch.where(x < -104.0, torch.zeros_like(x), x.exp())
+    m = torch.full(S.shape[:-1] + (1,), ninf, dtype=torch.float64)
+    l = torch.zeros_like(m)
+    o = torch.zeros_like(Q)
+    for i, k0 in enumerate(range(0, Lk, 32)):
+        if mut == 'drop_block' and i == arg:
+            continue
+        s = S[..., k0:k0 + 32]
+        mn = torch.maximum(m, s.amax(-1, keepdim=True))
+        dead = mn == ninf
+        safe = torch.where(dead, torch.zeros_like(mn), mn)
+        alpha = torch.where(dead | (m == ninf), torch.where(dead, torch.ones_like(m), torch.zeros_like(m)), ex(m - safe))
+        p = torch.where(dead, torch.zeros_like(s), ex(s - safe))
+        pr = p if pround is None else p.to(pround).double()
+        l = l * alpha + (pr if mut == 'l_rounded' else p).sum(-1, keepdim=True)
+        o = o * (torch.ones_like(alpha) if mut == 'skip_rescale' and i == arg else alpha) + pr @ V[:, :, k0:k0 + 32]
+        m = mn
+    return _attn_merge(torch.where(l > 0, o / torch.where(l > 0, l, torch.ones_like(l)), torch.zeros_like(o)))
+
+
+def attn_mutation_arg(mut, case, kt=ATTN_KT):
+    """Where a mutation strikes in a case (None: it cannot strike there): the swap and the shifted mask byte in the
+    last block of the second tile, the skipped rescale there too, the dropped block the last block of the first tile."""
+    Lk = case['k'].shape[1]
+    D = case['q'].shape[-1] // case['heads']
+    j = 2 * kt - 32
+    if mut == 'swap':           # (in a tie case: the last key of 'groups16' and its neighbour outside the group)
+        return (j + 15, j + 16) if j + 16 < Lk else ((0, 1) if Lk > 1 else None)
+    if mut == 'drop_dim35':
+        return True if D > 35 else None
+    if mut == 'drop_dim0':
+        return True
+    if mut == 'mask_shift':
+        if case['mask'] is None:
+            return None
+        if 'tied' in case:      # the decoy's byte moves on: the decoy joins its group's tie
+            return (0, ATTN_TIE_DECOY[0])
+        for b in range(case['mask'].shape[0]):
+            for jj in list(range(min(j, Lk - 1), Lk - 1)) + list(range(0, min(j, Lk - 1))):
+                if case['mask'][b, jj] and not case['mask'][b, jj + 1]:
+                    return (b, jj)
+        return None
+    if mut == 'skip_rescale':
+        return j // 32 if j < Lk else None
+    if mut == 'drop_block':
+        return kt // 32 - 1 if kt < Lk else None
+    return True

@@ -1302,3 +1302,209 @@ def test_ffn_refs_against_an_f32_torch_composition(case, dtype):
     got = _ffn_f32_composition(case, d, dtype, False, rows)
     for name, want in R.ffn_direct_outputs(case, ref).items():
         assert torch.equal(got[name].double(), want), name
+
+
+# ------------------------------------------------------- attention forward, kernel by kernel
+_ATTN_DT = [torch.bfloat16, torch.float16, torch.float32]
+_KT = R.ATTN_KT
+
+
+def _attn_exact_model(case, dtype):
+    """The f64 block model of the kernels on an exact-class case, as the output type's bits."""
+    return R.attn_bits(R.attn_blockwise(case).to(dtype))
+
+
+def _attn_scores(case):
+    """(scores of the case's actual q and k in f64, the same in f32 arithmetic) -- scale 1."""
+    H = case['heads']
+    q, k = R._attn_split(case['q'], H), R._attn_split(case['k'], H)
+    return q.double() @ k.double().transpose(-1, -2), q.float() @ k.float().transpose(-1, -2)
+
+
+@pytest.mark.parametrize('dtype', _ATTN_DT, ids=str)
+@pytest.mark.parametrize('D', [16, 32, 36, 64])
+def test_attn_select_cases_gap_and_expected(D, dtype):
+    """Every selection case the GPU test runs: q and k hold exactly 64 code and code, every score is an f32-exact
+    integer, the selected key leads every other live key by >= 128, the expected row is v[sel], and the block
+    model of the kernels reproduces it bit for bit."""
+    shapes = R.attn_shapes('fma', D)
+    if D in R.ATTN_RESIDENT_MAXK and dtype != torch.float32:
+        shapes = list(dict.fromkeys(shapes + R.attn_shapes('resident', D) + R.attn_shapes('stream', D)))
+    for Lq, Lk in shapes:
+        modes = ('pairs', 'edges', 'last') if (Lq, Lk) == R.ATTN_MAIN else ('pairs',)
+        for mode in modes:
+            c = R.attn_select_case(D, Lq, Lk, dtype, mode)
+            S64, S32 = _attn_scores(c)
+            assert torch.equal(S64, c['scores'].double()) and torch.equal(S32.double(), S64)
+            assert S64.abs().max() <= 64 * D and torch.equal(S64, S64.round())
+            live = ~c['mask'][:, None, None, :]
+            sel_s = torch.gather(S64, 3, c['sel'][..., None])
+            others = S64.masked_fill(~live.expand_as(S64), float('-inf')).scatter(3, c['sel'][..., None], float('-inf'))
+            alive = ~c['mask'].all(1)
+            if Lk > 1:
+                assert (sel_s - others.amax(-1, keepdim=True))[alive].min() >= 128
+            assert not torch.gather(c['mask'][:, None, :].expand(-1, c['heads'], -1), 2, c['sel'])[alive].any()
+            v = R._attn_split(c['v'], c['heads'])
+            want = torch.gather(v, 2, c['sel'][..., None].expand(-1, -1, -1, D))
+            want[~alive] = 0
+            assert torch.equal(R.attn_bits(R._attn_merge(want)), R.attn_bits(c['expected']))
+            assert torch.isfinite(c['v'].double()).all()
+            assert torch.equal(_attn_exact_model(c, dtype), R.attn_bits(c['expected'])), (Lq, Lk, mode)
+            # a masked key holds the largest finite values: a leak shows
+            vm = v.double().abs()[c['mask'][:, None, :, None].expand_as(v)]
+            assert (vm == torch.finfo(dtype).max).all()
+            # the case differs per batch, head and query
+            assert not torch.equal(c['q'][0], c['q'][1]) or Lk == 1
+            if Lq > 1 and Lk > 2 and mode == 'pairs':
+                e = R._attn_split(c['expected'], c['heads'])
+                assert not torch.equal(e[0, 0], e[0, 1]) and not torch.equal(e[0, 0, 0], e[0, 0, 1])
+
+
+@pytest.mark.parametrize('Lk', [2 * _KT + 5, 3 * _KT])
+@pytest.mark.parametrize('D', [32, 36])
+def test_attn_select_cases_cover_slots_dims_and_order(D, Lk):
+    """The builder's guarantees on the three-tile cases: every slot of the first block, of the last block of the
+    second tile and of the last (ragged) block is selected -- one block in each tile of the streaming kernel; for
+    every head dim a live pair differing in that dim only, each member selected by some query (so the selected key
+    sits blocks before its runner-up for one query and blocks after it for another); masked-best-match queries."""
+    c = R.attn_select_case(D, 129, Lk, torch.bfloat16, 'pairs')
+    lo, hi, mid = R.attn_pair_keys(D, Lk)
+    nblk = (Lk + 31) // 32
+    assert mid == 2 * _KT // 32 - 1 and len(lo) == D and nblk - 1 >= 2 * _KT // 32
+    chosen = set(c['sel'].flatten().tolist())
+    for blk in (0, mid, nblk - 1):
+        assert set(range(blk * 32, min(blk * 32 + 32, Lk))) <= chosen, blk
+    assert 0 // _KT == 0 and (mid * 32) // _KT == 1 and ((nblk - 1) * 32) // _KT == 2
+    codes, mask, sel = c['codes'], c['mask'], c['sel']
+    before = after = best_match = 0
+    for d in range(D):
+        diff = (codes[:, :, lo[d]] != codes[:, :, hi[d]])
+        assert diff[..., d].all() and diff.sum(-1).eq(1).all()
+        assert hi[d] // 32 > lo[d] // 32 + 1
+        ok = False
+        for b in range(R.ATTN_B):
+            if not mask[b, lo[d]] and not mask[b, hi[d]]:
+                s = set(sel[b].flatten().tolist())
+                ok |= lo[d] in s and hi[d] in s
+                before += lo[d] in s          # selected before the runner-up's block: the max stays
+                after += hi[d] in s           # selected after it: the max rises, O is rescaled to 0
+        assert ok, d
+    for b in range(R.ATTN_B):
+        t_masked = torch.gather(mask[b][None, :].expand(c['heads'], -1), 1, c['target'][b])
+        partner = {**dict(zip(lo, hi)), **dict(zip(hi, lo))}
+        for h, i in t_masked.nonzero().tolist():
+            assert int(sel[b, h, i]) == partner[int(c['target'][b, h, i])]
+            best_match += 1
+    assert before >= D // 2 and after >= D // 2 and best_match >= 8
+    assert mask[0].any() and mask[1].any() and not torch.equal(mask[0], mask[1])
+
+
+@pytest.mark.parametrize('dtype', _ATTN_DT, ids=str)
+@pytest.mark.parametrize('D', [16, 32, 36, 64])
+def test_attn_tie_case_means_are_exact(D, dtype):
+    c = R.attn_tie_case(D, 129, dtype)
+    groups = R.attn_tie_groups()
+    assert {len(ks) for ks in groups.values()} == {2, 4, 8, 16, 32, 64}
+    lane = lambda j: (j % 32 % 16) // 4                                   # noqa: E731
+    assert len({lane(j) for j in groups['lane8']}) == 1 and len({j // 32 for j in groups['lane8']}) == 1
+    assert {lane(j) for j in groups['groups4']} == {0, 1, 2, 3} == {lane(j) for j in groups['groups16']}
+    for n in ('consec64', 'consec2'):
+        blocks = sorted({j // 32 for j in groups[n]})
+        assert blocks == [blocks[0], blocks[0] + 1] and blocks[0] // (_KT // 32) == blocks[1] // (_KT // 32)
+    assert {j // _KT for j in groups['edge4']} == {0, 1}
+    assert {j // _KT for j in groups['tiles02_2']} == {0, 2} == {j // _KT for j in groups['tiles02_8']}
+    assert groups['groups4'][0] // 32 == _KT // 32 - 1 and groups['groups16'][0] // 32 == 2 * _KT // 32 - 1
+    assert set(c['group'].flatten().tolist()) == set(range(len(groups)))
+    S64, S32 = _attn_scores(c)
+    assert torch.equal(S64, c['scores'].double()) and torch.equal(S32.double(), S64)
+    # the f32 sum of a group's values is exact and the mean is a value of the output type
+    v = R._attn_split(c['v'], c['heads'])
+    s32 = c['tied'].float() @ v.float().masked_fill(c['mask'][:, None, :, None], 0)
+    assert torch.equal(s32.double(), c['tied'].double() @ v.double().masked_fill(c['mask'][:, None, :, None], 0))
+    assert torch.equal(c['expected'].double(), c['mean64'])
+    assert c['mask'][:, R.ATTN_TIE_DECOY[0]].all() and not c['tied'][..., R.ATTN_TIE_DECOY[0]].any()
+    assert torch.equal(_attn_exact_model(c, dtype), R.attn_bits(c['expected']))
+
+
+@pytest.mark.parametrize('variant', R.ATTN_VARIANTS)
+@pytest.mark.parametrize('D', [32, 36])
+def test_attn_blockwise_is_the_reference(D, variant):
+    for maskmode in ('random', 'first_tile', 'dead_batch'):
+        c = R.attn_generic_case(D, 65, 2 * _KT + 5, torch.bfloat16, variant, maskmode)
+        assert (R.attn_blockwise(c) - c['o']).abs().max() <= 1e-12 * max(1.0, c['o'].abs().max().item())
+
+
+def _attn_generic_cases(dtype, D):
+    yield 'plain', R.attn_generic_case(D, 65, 2 * _KT + 5, dtype, 'plain', 'random')
+    yield 'wide', R.attn_generic_case(D, 65, 2 * _KT + 5, dtype, 'wide', 'random')
+    yield 'offset', R.attn_generic_case(D, 65, 2 * _KT + 5, dtype, 'offset', 'random')
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16], ids=str)
+@pytest.mark.parametrize('D', [32, 36])
+def test_attn_bound_admits_the_kernel_model_and_f32_sdpa(D, dtype):
+    """The f64 block model with p rounded to the 16-bit type (the MFMA kernels' one deliberate deviation) and torch's
+    f32 SDPA, both rounded to the output type, are inside the bound; the scores of 'wide' reach +-60 and those of
+    'offset' sit near 200."""
+    for name, c in _attn_generic_cases(dtype, D):
+        bound = R.attn_fwd_bound(c, 'resident', dtype)
+        for got in (R.attn_blockwise(c, pround=dtype), c['sdpa']):
+            worst, share, zeros = R.attn_ratio(got.to(dtype).double(), c, bound)
+            assert worst < 1.0 and zeros and share > 0.99, (name, worst, share)
+        S = (R._attn_split(c['q'].double(), 3) @ R._attn_split(c['k'].double(), 3).transpose(-1, -2)) * c['scale']
+        if name == 'wide':
+            assert S.max() > 60 and S.min() < -60
+        if name == 'offset':
+            assert S.min() > 150
+    sub = R.attn_subnormal_case(D, dtype)
+    bound = R.attn_fwd_bound(sub, 'resident', dtype)
+    kept = R.attn_blockwise(sub, pround=dtype).to(dtype).double()
+    assert R.attn_ratio(kept, sub, bound)[0] < 1.0
+    if dtype == torch.float16:
+        flushed = torch.full_like(kept, 1.0 / (1.0 + 256 * 2.0 ** -16)).to(dtype).double()
+        assert R.attn_ratio(flushed, sub, bound)[0] > 1.0          # the case tells the two models apart
+
+
+@pytest.mark.parametrize('mut', R.ATTN_MUTATIONS)
+@pytest.mark.parametrize('D', [32, 36])
+def test_attn_mutations_are_caught(D, mut):
+    """Each way the block step could be broken, applied to the model: class 1 and class 2 must see a wrong bit,
+    class 3 an element over the bound.  'l_rounded' is the exception.  It changes l by at most u16 relative, and only
+    where p is neither 0 nor 1: the exact classes have p in {0, 1} and cannot see it, and on N(0, 1) operands it moves
+    the output by at most u16 |o|, inside terms (a) + (b) -- the bound is too wide for it there.  The class-3 case
+    built for it, R.attn_bias_case, catches it (the model of the kernels as they are stays inside)."""
+    dt = torch.bfloat16
+    c1 = R.attn_select_case(D, *R.ATTN_MAIN, dt, 'pairs')
+    c2 = R.attn_tie_case(D, 129, dt)
+    caught = {}
+    for name, c in (('select', c1), ('tie', c2)):
+        arg = R.attn_mutation_arg(mut, c)
+        if arg is not None:
+            got = R.attn_blockwise(c, mut, arg, pround=dt).to(dt)
+            caught[name] = not torch.equal(R.attn_bits(got), R.attn_bits(c['expected']))
+    worst = 0.0
+    for dtype in (torch.bfloat16, torch.float16):
+        for name, c in _attn_generic_cases(dtype, D):
+            arg = R.attn_mutation_arg(mut, c)
+            if arg is not None:
+                got = R.attn_blockwise(c, mut, arg, pround=dtype).to(dtype).double()
+                worst = max(worst, R.attn_ratio(got, c, _attn_bound(D, dtype, name))[0])
+                caught['generic'] = worst > 1.0
+    if mut == 'l_rounded':
+        assert caught == {'select': False, 'tie': False, 'generic': False}, (caught, worst)
+        for dtype in (torch.bfloat16, torch.float16):
+            c = R.attn_bias_case(D, dtype)
+            bound = R.attn_fwd_bound(c, 'resident', dtype)
+            as_is, broken, sdpa = (R.attn_ratio(o.to(dtype).double(), c, bound)[0] for o in
+                                   (R.attn_blockwise(c, pround=dtype), R.attn_blockwise(c, mut, True, pround=dtype), c['sdpa']))
+            assert as_is < 1.0 < broken and sdpa < 1.0, (as_is, broken, sdpa)
+    elif mut == 'drop_dim35' and D == 32:
+        assert caught == {}
+    else:
+        # a lost head dim ties no two keys of the tie case, which has no pair by design: class 1's pairs catch it
+        assert caught == {'select': True, 'tie': not mut.startswith('drop_dim'), 'generic': True}, (caught, worst)
+
+
+@functools.lru_cache(maxsize=None)
+def _attn_bound(D, dtype, name):
+    return R.attn_fwd_bound(dict(_attn_generic_cases(dtype, D))[name], 'resident', dtype)
