@@ -75,6 +75,50 @@ int kinet_mha_backward(const float* Q, int ldq, const float* K, int ldk, const f
                        int heads, int head_dim, float scale, const uint8_t* key_mask, float* workspace,
                        float dropout_p, const int64_t* dropout_seed, kinet_stream_t stream);
 
+/* ---- the f32 attention training pair for long key sets (kinet_amd/csrc/attn_train.hip): both
+ * products of every kernel on v_mfma_f32_16x16x4_f32, head_dim 32 or 36 (others: KINET_ERR_ARG).
+ *
+ * kinet_mha_train_forward: kinet_mha_core_dropout on f32 operands (same layout rules, key_mask,
+ * dropout_p and device seed, same keep mask) that also writes
+ *   lse[b, h, i] = log sum_j exp(scale * Q_bh[i] . K_bh[j])   over the unmasked keys, (B, heads, Lq);
+ * a row with no unmasked key gets a zero O row and lse = -inf.
+ *
+ * kinet_mha_train_backward: given Q, K, V, the forward's O and lse, and dO (row stride lddo),
+ * writes dQ, dK, dV with the strides of Q, K, V.  The probabilities are recomputed tile by tile as
+ * exp(scale * S - lse); workspace: kinet_mha_train_backward_workspace = batch * heads * Lq floats
+ * (delta_i = dO_i . O_i), nothing that grows with Lq * Lk.  No atomics: reruns are bit-identical.
+ * Fully masked rows or batches get exactly zero gradients.
+ *
+ * kinet_mha_train_plan (host side, no GPU call): the three launches for a described problem,
+ * KINET_MHATP_FIELDS ints in, KINET_MHATPL_FIELDS ints out (csrc/attn_train_plan.h).
+ * kinet_mha_train_calls: kinet_mha_train_forward launches made by the calling thread so far. */
+enum kinet_mha_train_problem_field {
+    KINET_MHATP_HEAD_DIM = 0, KINET_MHATP_BATCH, KINET_MHATP_HEADS, KINET_MHATP_LQ, KINET_MHATP_LK,
+    KINET_MHATP_FIELDS
+};
+enum kinet_mha_train_plan_field {
+    KINET_MHATPL_SUPPORTED = 0,   /* 0: the pair refuses this head dim / grid */
+    KINET_MHATPL_DENSE_DEFAULT,   /* 1: the dense transformer layers take this pair at this key count */
+    KINET_MHATPL_QT, KINET_MHATPL_KT,                 /* queries / keys per tile */
+    KINET_MHATPL_ROW_STRIDE, KINET_MHATPL_COL_STRIDE, /* floats per row of the two LDS images (0: refused) */
+    KINET_MHATPL_FWD,             /* grid x, y, z, block, dynamic LDS bytes of the forward ... */
+    KINET_MHATPL_DQ = KINET_MHATPL_FWD + 5,   /* ... of the backward by query tile ... */
+    KINET_MHATPL_DKV = KINET_MHATPL_DQ + 5,   /* ... and by key tile */
+    KINET_MHATPL_FIELDS = KINET_MHATPL_DKV + 5
+};
+int kinet_mha_train_plan(const int* problem, int* plan_out);
+int kinet_mha_train_calls(void);
+int kinet_mha_train_forward(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O,
+                            int ldo, float* lse, int batch, int Lq, int Lk, int heads, int head_dim, float scale,
+                            const uint8_t* key_mask, float dropout_p, const int64_t* dropout_seed,
+                            kinet_stream_t stream);
+int64_t kinet_mha_train_backward_workspace(int batch, int Lq, int heads);
+int kinet_mha_train_backward(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv,
+                             const float* O, int ldo, const float* dO, int lddo, const float* lse, float* dQ,
+                             float* dK, float* dV, int batch, int Lq, int Lk, int heads, int head_dim, float scale,
+                             const uint8_t* key_mask, float* workspace, float dropout_p,
+                             const int64_t* dropout_seed, kinet_stream_t stream);
+
 /* ---- training-path glue (kinet_amd/csrc/train_ops.hip), f32, replacing torch elementwise ops.
  * Dropout keep masks: the counter hash of kinet_dropout_mask (include/kinet_ops.h) over the
  * element's flat index, keyed by the device int64 *dropout_seed; kept values scaled 1/(1-p). */

@@ -99,6 +99,11 @@ _SIGS = {
     'kinet_mha_backward_workspace': [I, I, I, I],
     'kinet_mha_backward': [P, I, P, I, P, I, P, I, P, P, P, I, I, I, I, I, F, P, P, F, P, P],
     'kinet_mha_core_dropout': [P, I, P, I, P, I, P, I] + [I] * 5 + [F, I, P, F, P, P],
+    'kinet_mha_train_plan': [P, P],
+    'kinet_mha_train_calls': [],
+    'kinet_mha_train_forward': [P, I, P, I, P, I, P, I, P] + [I] * 5 + [F, P, F, P, P],
+    'kinet_mha_train_backward_workspace': [I, I, I],
+    'kinet_mha_train_backward': [P, I, P, I, P, I, P, I, P, I, P, P, P, P] + [I] * 5 + [F, P, P, F, P, P],
     'kinet_dropout_mask': [P, I64, F, P, P],
     'kinet_dropout_add_layernorm': [P] * 5 + [I, I, F, F, P, P],
     'kinet_dropout_add_layernorm_backward_workspace': [I, I],
@@ -147,6 +152,7 @@ _RESTYPES = {'kinet_last_error': ctypes.c_char_p, 'kinet_version': ctypes.c_char
              'kinet_dropout_add_layernorm_backward_workspace': ctypes.c_int64,
              'kinet_groupnorm_backward_workspace': ctypes.c_int64,
              'kinet_mha_backward_workspace': ctypes.c_int64,
+             'kinet_mha_train_backward_workspace': ctypes.c_int64,
              'kinet_focal_set_loss_workspace': ctypes.c_int64,
              'kinet_segm_mask_loss_workspace': ctypes.c_long, 'kinet_segm_attention_backward_workspace': ctypes.c_long,
              'kinet_segm_out_conv_backward_workspace': ctypes.c_long}

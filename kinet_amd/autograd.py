@@ -17,6 +17,7 @@ sigmoid / masked_fill glue of the heads.
     group_norm_nhwc(x, groups, w, b, eps)   nn.GroupNorm on (B, HW, C)
     conv_nhwc(x, weight, ...)               nn.Conv2d (+ FrozenBatchNorm2d, residual, ReLU) on NHWC
     mha_core(q, k, v, heads, key_mask)      the softmax(QK^T / sqrt(d)) V core of nn.MultiheadAttention
+    mha_core_stream(q, k, v, heads, ...)    the same on the key-streaming f32 MFMA pair (long key sets)
     dropout_add_layer_norm(x, r, ln, drop)  ln(x + drop(r)), the post-norm residual sub-layer
     dropout_act(x, drop)                    drop(relu(x)), the FFN hidden
     msda_prep(off, logits, refs, ...)       MSDeformAttn sampling locations + softmaxed weights
@@ -235,6 +236,38 @@ def mha_core(q, k, v, heads, scale, key_mask=None, dropout_p=0.0, seed=None):
     if dropout_p > 0 and seed is None:
         seed = K.dropout_seed(q.device)
     return _MHACore.apply(q, k, v, heads, scale, key_mask, float(dropout_p), seed)
+
+
+class _MHACoreStream(Function):
+    """mha_core on the f32 MFMA training pair (csrc/attn_train.hip): the forward also saves its output
+    and the per-row log-sum-exp, from which the backward recomputes the probabilities tile by tile."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, scale, key_mask, dropout_p, seed):
+        _f32(q)
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        o, lse = K.mha_train_forward(q, k, v, heads, scale, key_mask, dropout_p, seed)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.conf = (heads, scale, key_mask, dropout_p, seed)
+        return o
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, do):
+        q, k, v, o, lse = ctx.saved_tensors
+        heads, scale, key_mask, dropout_p, seed = ctx.conf
+        dq, dk, dv = K.mha_train_backward(q, k, v, o, do.contiguous().float(), lse, heads, scale, key_mask, dropout_p,
+                                          seed)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def mha_core_stream(q, k, v, heads, scale, key_mask=None, dropout_p=0.0, seed=None):
+    """mha_core for long key sets (the dense attention of vanilla DETR: every H*W key), head dim
+    32 / 36: same value, same dropout mask for the same seed, on the key-streaming f32 MFMA pair whose
+    backward needs no workspace that grows with Lq * Lk."""
+    if dropout_p > 0 and seed is None:
+        seed = K.dropout_seed(q.device)
+    return _MHACoreStream.apply(q, k, v, heads, scale, key_mask, float(dropout_p), seed)
 
 
 class _MHACoreQK(Function):

@@ -1815,6 +1815,71 @@ def mha_backward(q, k, v, do, heads, scale, key_mask=None, dropout_p=0.0, seed=N
     return dq, dk, dv
 
 
+# field order of kinet_mha_train_plan's plan record (include/kinet_grad.h)
+MHA_TRAIN_PLAN_FIELDS = ('supported', 'dense_default', 'qt', 'kt', 'row_stride', 'col_stride') + tuple(
+    f'{k}_{f}' for k in ('fwd', 'dq', 'dkv') for f in ('grid_x', 'grid_y', 'grid_z', 'block', 'lds'))
+
+
+def mha_train_plan(head_dim, batch, heads, Lq, Lk):
+    """The launches of the f32 attention training pair for this problem (kinet_mha_train_plan,
+    csrc/attn_train_plan.h; no GPU call): a dict of MHA_TRAIN_PLAN_FIELDS."""
+    prob = (ctypes.c_int * 5)(head_dim, batch, heads, Lq, Lk)
+    out = (ctypes.c_int * len(MHA_TRAIN_PLAN_FIELDS))()
+    N.call('kinet_mha_train_plan', ctypes.cast(prob, ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p))
+    return dict(zip(MHA_TRAIN_PLAN_FIELDS, out))
+
+
+def mha_train_calls():
+    """kinet_mha_train_forward launches the calling thread has made so far."""
+    return N.lib().kinet_mha_train_calls()
+
+
+def _mha_train_rows(name, *ts):
+    for t in ts:
+        if t.dtype != torch.float32 or t.stride(-1) != 1 or t.stride(0) != t.shape[1] * t.stride(1):
+            raise RuntimeError(f'{name}: f32 rows, unit stride, packed batches')
+
+
+def mha_train_forward(q, k, v, heads, scale, key_mask=None, dropout_p=0.0, seed=None, out=None):
+    """mha_core for f32 training on the f32 MFMA (kinet_mha_train_forward; head_dim 32 / 36): returns
+    o (B, Lq, E) and lse (B, heads, Lq), the log-sum-exp of the scaled scores over the unmasked keys."""
+    B, Lq, E = q.shape
+    Lk = k.shape[1]
+    o = out if out is not None else torch.empty((B, Lq, E), dtype=torch.float32, device=q.device)
+    _mha_train_rows('mha_train_forward', q, k, v, o)
+    lse = torch.empty((B, heads, Lq), dtype=torch.float32, device=q.device)
+    km = key_mask.to(torch.uint8).contiguous() if key_mask is not None else None
+    N.call('kinet_mha_train_forward', N.ptr(q), q.stride(1), N.ptr(k), k.stride(1), N.ptr(v), v.stride(1), N.ptr(o),
+           o.stride(1), N.ptr(lse), B, Lq, Lk, heads, E // heads, float(scale), N.ptr(km), float(dropout_p),
+           N.ptr(seed) if dropout_p > 0 else None, N.stream(q.device),
+           work={'family': 'attn', 'flops': 4.0 * B * heads * Lq * Lk * (E // heads)})
+    return o, lse
+
+
+def mha_train_backward(q, k, v, o, do, lse, heads, scale, key_mask=None, dropout_p=0.0, seed=None, out=None):
+    """Backward of mha_train_forward (kinet_mha_train_backward): dq, dk, dv with the row strides of q, k, v
+    (`out`: the three tensors to write, laid out as q, k, v; default packed, for packed q, k, v)."""
+    B, Lq, E = q.shape
+    Lk = k.shape[1]
+    if out is None:
+        if q.stride(1) != E or k.stride(1) != E or v.stride(1) != E:
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        out = tuple(torch.empty_like(t) for t in (q, k, v))
+    dq, dk, dv = out
+    _mha_train_rows('mha_train_backward', q, k, v, o, do, dq, dk, dv)
+    if (dq.stride(1), dk.stride(1), dv.stride(1)) != (q.stride(1), k.stride(1), v.stride(1)):
+        raise RuntimeError('mha_train_backward: dq / dk / dv take the row strides of q / k / v')
+    ws = torch.empty(max(1, N.lib().kinet_mha_train_backward_workspace(B, Lq, heads)), dtype=torch.float32,
+                     device=q.device)
+    km = key_mask.to(torch.uint8).contiguous() if key_mask is not None else None
+    N.call('kinet_mha_train_backward', N.ptr(q), q.stride(1), N.ptr(k), k.stride(1), N.ptr(v), v.stride(1), N.ptr(o),
+           o.stride(1), N.ptr(do), do.stride(1), N.ptr(lse.contiguous()), N.ptr(dq), N.ptr(dk), N.ptr(dv), B, Lq, Lk,
+           heads, E // heads, float(scale), N.ptr(km), N.ptr(ws), float(dropout_p),
+           N.ptr(seed) if dropout_p > 0 else None, N.stream(q.device),
+           work={'family': 'attn', 'flops': 10.0 * B * heads * Lq * Lk * (E // heads)})
+    return dq, dk, dv
+
+
 # ------------------------------------------------------------------- segmentation head
 def segm_attention(qp, kp, mask, Q, heads, out=None):
     """Joint-softmax attention map (kinet_segm_attention): qp (B*Q, d), kp (B, HW, d), mask (B, HW)

@@ -8,7 +8,7 @@ src/trackformer/models/__init__.py:16-125.
 `args` is the reference's Namespace (cfgs/train.yaml + named configs).  All three model
 families are built: the deformable image branch (:51-71, the hot path), the KineT kinematic
 branch (`args.kine`, :72-107, kinet_amd/models/kinet.py) and vanilla DETR (:111-125, the
-reference's default `deformable: false`; kinet_amd/models/detr.py, inference only).  The
+reference's default `deformable: false`; kinet_amd/models/detr.py, inference and f32 training).  The
 deformable branch also builds the two-stage variant (`two_stage: true`; the proposal stage runs on
 csrc/two_stage.hip; what build_model returns is the inference model, and training it is opt-in:
 kinet_amd.train.build_two_stage_training(args) returns the same model with `two_stage_training` set

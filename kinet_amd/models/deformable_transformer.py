@@ -75,6 +75,11 @@ def fast_path(module=None):
     return module is None or not _active_dropout(module)
 
 
+def in_reference_path():
+    """Inside a reference_path() block."""
+    return _FORCE_REFERENCE[0] > 0
+
+
 class reference_path:
     """Run the op-for-op module path even without grad (e.g. the no-grad previous-frame
     pass of training, which the reference runs in train mode -- with dropout)."""

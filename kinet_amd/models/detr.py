@@ -11,16 +11,24 @@ projection as a GEMM, the sine embedding kernel, q|k projections with the positi
 the GEMM's second operand, the dense attention core (`kernels.mha_core`: all H*W keys, so the
 key-streaming MFMA kernel in the 16-bit modes once H*W exceeds the resident kernels' caps), the
 fused out-projection / FFN launches, the heads as GEMMs.  What depends on the frame geometry only
-(the flattened padding mask as bytes, the position embedding) is cached per geometry.  Training
-of vanilla DETR is not built: a forward with autograd on or active dropout raises.
+(the flattened padding mask as bytes, the position embedding) is cached per geometry.
+
+Training (autograd on; or train mode with active dropout under torch.no_grad() inside
+reference_path(), as DETRTrackingBase runs the previous frame -- outside it that combination still
+raises: it is a forgotten eval()) is the same graph in f32 on the kinet_amd.autograd
+Functions: the differentiable backbone (stage-4 feature only, as the reference), the input projection
+as a Linear, the same sine rows, `transformer.run(..., fast=False)` -- whose dense attentions run the
+key-streaming f32 MFMA pair `autograd.mha_core_stream` (csrc/attn_train.hip) --, the heads as Linear
+Functions.  Track queries in `targets` stay differentiable.  Same output dict, tuple and aux outputs.
 """
 import torch
 from torch import nn
 
+from kinet_amd import autograd as A
 from kinet_amd import kernels as K
 from kinet_amd.models.backbone import interp_mask, nhwc_as_nchw
 from kinet_amd.models.deformable_detr import MLP
-from kinet_amd.models.deformable_transformer import fast_path, mlp_fast
+from kinet_amd.models.deformable_transformer import fast_path, in_reference_path, mlp_fast
 from kinet_amd.models.misc import NestedTensor, nested_tensor_from_tensor_list
 
 
@@ -60,16 +68,17 @@ class DETR(nn.Module):
         self._geo_cache.clear()
         return self
 
-    def _geometry(self, samples, hw):
+    def _geometry(self, samples, hw, dtype=None):
         """(padding mask at the feature resolution, the same flattened as bytes for the attention
-        kernels, position embedding rows (B, H*W, d) in the compute dtype); cached per image
-        sizes when they determine the mask (NestedTensor.sizes)."""
-        key = None if samples.sizes is None else (samples.sizes, tuple(samples.mask.shape), hw, self.compute_dtype,
+        kernels, position embedding rows (B, H*W, d) in `dtype`, default the compute dtype); cached
+        per image sizes when they determine the mask (NestedTensor.sizes)."""
+        dtype = self.compute_dtype if dtype is None else dtype
+        key = None if samples.sizes is None else (samples.sizes, tuple(samples.mask.shape), hw, dtype,
                                                   str(samples.mask.device))
         geo = self._geo_cache.get(key) if key is not None else None
         if geo is None:
             mask = interp_mask(samples.mask, hw)
-            pos = self.backbone[1].rows(mask, out_dtype=self.compute_dtype)
+            pos = self.backbone[1].rows(mask, out_dtype=dtype)
             geo = (mask, mask.flatten(1).to(torch.uint8).contiguous(), pos.view(mask.shape[0], hw[0] * hw[1], -1))
             if key is not None:
                 if len(self._geo_cache) > 16:
@@ -81,8 +90,12 @@ class DETR(nn.Module):
         if not isinstance(samples, NestedTensor):
             samples = nested_tensor_from_tensor_list(samples)
         if not fast_path(self):
-            raise NotImplementedError('vanilla DETR runs the inference kernels only: call it in eval mode under '
-                                      'torch.no_grad() (training config 1 is not built)')
+            if not (torch.is_grad_enabled() or in_reference_path()):
+                # a bare train-mode call with active dropout and no autograd: most likely a missing eval()
+                raise NotImplementedError('vanilla DETR in train mode with active dropout under torch.no_grad(): call '
+                                          'eval() for the inference kernels; the no-grad previous-frame pass of '
+                                          'training enters through reference_path()')
+            return self._forward_train(samples, targets)
         dt = self.compute_dtype
         device = samples.tensors.device
         feats = self.backbone[0].forward_nhwc(samples.tensors, dt)      # [layer4] NHWC
@@ -113,6 +126,44 @@ class DETR(nn.Module):
         outputs_coord = mlp_fast(self.bbox_embed, hs).sigmoid()
         out = {'pred_logits': outputs_class[-1], 'pred_boxes': outputs_coord[-1],
                'hs_embed': hs_without_norm[-1].float()}
+        if self.aux_loss:
+            out['aux_outputs'] = self._set_aux_loss(outputs_class, outputs_coord)
+        return out, targets, features, memory.permute(0, 2, 1).view(B, d, h, w), hs
+
+    def _forward_train(self, samples, targets):
+        """detr.py:66-141 in f32 on the kinet_amd.autograd Functions (module docstring)."""
+        if samples.tensors.device.type != 'cuda':
+            raise NotImplementedError('vanilla DETR has no CPU path: inference and training both run the HIP kernels, '
+                                      'move the model and the samples to the GPU')
+        body = self.backbone[0]
+        xs = body.body.forward_autograd(samples.tensors.float())
+        feats = [xs[str(i)] for i in body.return_idx]                   # NCHW views of NHWC buffers
+        x = feats[-1].permute(0, 2, 3, 1)
+        B, h, w, C = x.shape
+        d = self.hidden_dim
+        mask, mask_bytes, pos = self._geometry(samples, (h, w), torch.float32)
+        features = [NestedTensor(f, mask if f is feats[-1] else interp_mask(samples.mask, f.shape[-2:]), samples.sizes)
+                    for f in feats]
+        proj = self.input_proj
+        src = A.linear(x.reshape(B * h * w, C), proj.weight.view(d, C), proj.bias).view(B, h * w, d)
+
+        query_embed = self.query_embed.weight[None].expand(B, -1, -1)
+        if targets is not None and 'track_query_hs_embeds' in targets[0]:
+            # detr.py:99-117, differentiable w.r.t. the track embeddings
+            track = torch.stack([t['track_query_hs_embeds'] for t in targets]).float()
+            n_track = track.shape[1]
+            query_embed = torch.cat([query_embed.new_zeros((B, n_track, d)), query_embed], 1)
+            tgt = torch.cat([track, track.new_zeros((B, self.num_queries, d))], 1)
+            for i, target in enumerate(targets):
+                target['track_query_hs_embeds'] = tgt[i]
+        else:
+            tgt = torch.zeros((B, self.num_queries, d), dtype=torch.float32, device=x.device)
+
+        hs, hs_without_norm, memory = self.transformer.run(src, mask_bytes, query_embed, pos, tgt, fast=False)
+
+        outputs_class = A.linear_module(hs, self.class_embed)
+        outputs_coord = self.bbox_embed(hs).sigmoid()
+        out = {'pred_logits': outputs_class[-1], 'pred_boxes': outputs_coord[-1], 'hs_embed': hs_without_norm[-1]}
         if self.aux_loss:
             out['aux_outputs'] = self._set_aux_loss(outputs_class, outputs_coord)
         return out, targets, features, memory.permute(0, 2, 1).view(B, d, h, w), hs

@@ -50,7 +50,7 @@ class DeformableDETRTracking(DETRTrackingBase, DeformableDETR):
 
 
 class DETRTracking(DETRTrackingBase, DETR):
-    """Vanilla DETR with track queries (tracking mode; DETR itself runs inference only)."""
+    """Vanilla DETR with track queries (tracking mode, and the two-pass training step on DETR's training forward)."""
 
     def __init__(self, tracking_kwargs, detr_kwargs):
         DETR.__init__(self, **detr_kwargs)

@@ -61,11 +61,11 @@ def _linear(x, mod, fast, relu=False, residual=None, ln=None, x_add=None, drop=N
     return y if ln is None else A.layer_norm(y, ln)
 
 
-def _attention(mod, query, key, value, fast, q_add=None, k_add=None, key_padding_mask=None):
+def _attention(mod, query, key, value, fast, q_add=None, k_add=None, key_padding_mask=None, dense=False):
     """nn.MultiheadAttention(query [+ q_add], key [+ k_add], value, key_padding_mask)[0]
     BEFORE its out_proj (the caller fuses out_proj with residual + LayerNorm); batch-first.
     In training the attention probabilities are dropped with the module's `dropout` (as
-    kinet_amd.autograd.multihead_attention)."""
+    kinet_amd.autograd.multihead_attention); `dense` (a layer's `dense_attn`): see below."""
     E = mod.embed_dim
     w, b = mod.in_proj_weight, mod.in_proj_bias
     scale = mod.head_dim ** -0.5
@@ -81,8 +81,14 @@ def _attention(mod, query, key, value, fast, q_add=None, k_add=None, key_padding
     q = A.linear(query if q_add is None else query + q_add, w[:E], b[:E])
     k = A.linear(key if k_add is None else key + k_add, w[E:2 * E], b[E:2 * E])
     v = A.linear(value, w[2 * E:], b[2 * E:])
-    return A.mha_core(q, k, v, mod.num_heads, scale, key_padding_mask,
-                      dropout_p=mod.dropout if mod.training else 0.0)
+    core = A.mha_core
+    if dense:
+        # vanilla DETR (models/transformer.py): every H*W key; the key-streaming f32 MFMA pair where its
+        # planner takes the shape (csrc/attn_train_plan.h), head dims it refuses stay on mha_core
+        plan = K.mha_train_plan(mod.head_dim, q.shape[0], mod.num_heads, q.shape[1], k.shape[1])
+        if plan['supported'] and plan['dense_default']:
+            core = A.mha_core_stream
+    return core(q, k, v, mod.num_heads, scale, key_padding_mask, dropout_p=mod.dropout if mod.training else 0.0)
 
 
 def _layer_norm(x, ln, fast, residual=None):
@@ -200,10 +206,12 @@ class TransformerEncoderLayer(nn.Module):
         self.dropout2 = nn.Dropout(dropout)
 
     fused_ffn = False   # see _ffn
+    dense_attn = False  # see _attention: training attention on autograd.mha_core_stream
 
     def run(self, src, pos, key_padding_mask, fast):
         sa = self.self_attn
-        o = _attention(sa, src, src, src, fast, q_add=pos, k_add=pos, key_padding_mask=key_padding_mask)
+        o = _attention(sa, src, src, src, fast, q_add=pos, k_add=pos, key_padding_mask=key_padding_mask,
+                       dense=self.dense_attn)
         if fast and self.fused_ffn and K.attn_out_ffn_supported(o, sa.out_proj, self.linear1, self.linear2):
             # out_proj + residual + norm1 + FFN + norm2 in one launch
             return K.attn_out_ffn_fused(o, sa.out_proj, src, self.norm1, self.linear1, self.linear2, self.norm2)
@@ -231,13 +239,14 @@ class TransformerDecoderLayer(nn.Module):
         self.dropout3 = nn.Dropout(dropout)
 
     fused_ffn = False   # see _ffn
+    dense_attn = False  # see _attention: training attention on autograd.mha_core_stream
 
     def run(self, tgt, memory, pos, query_pos, memory_key_padding_mask, fast):
         sa, ca = self.self_attn, self.multihead_attn
-        o = _attention(sa, tgt, tgt, tgt, fast, q_add=query_pos, k_add=query_pos)
+        o = _attention(sa, tgt, tgt, tgt, fast, q_add=query_pos, k_add=query_pos, dense=self.dense_attn)
         tgt = _linear(o, sa.out_proj, fast, residual=tgt, ln=self.norm1, drop=self.dropout1)
         o = _attention(ca, tgt, memory, memory, fast, q_add=query_pos, k_add=pos,
-                       key_padding_mask=memory_key_padding_mask)
+                       key_padding_mask=memory_key_padding_mask, dense=self.dense_attn)
         tgt = _linear(o, ca.out_proj, fast, residual=tgt, ln=self.norm2, drop=self.dropout2)
         return _ffn(self, tgt, self.norm3, self.dropout3, fast)
 

@@ -8,7 +8,11 @@ reference's (`encoder.layers.N.*`, `decoder.layers.N.*`, `decoder.norm`).  Both 
 dense over all H*W keys (1050 at 800x1333), which is what the key-streaming MFMA kernel of
 csrc/attn.hip is for.  Batch-first (B, L, d) throughout.
 
-Inference only: `run` is the kernel path; pre-norm, non-ReLU activations and `track_attention`
+`run` is the interface: the inference kernels with fast=True, the kinet_amd.autograd Functions (f32,
+differentiable, the reference's dropouts) with fast=False.  The layers carry `dense_attn`, so in
+training both attentions run the key-streaming f32 MFMA pair `autograd.mha_core_stream`
+(csrc/attn_train.hip) where its planner takes the shape (csrc/attn_train_plan.h); KineT's layers, of
+the same classes, keep `autograd.mha_core`.  Pre-norm, non-ReLU activations and `track_attention`
 (false in every shipped config) raise at construction.
 """
 from torch import nn
@@ -29,6 +33,7 @@ class Transformer(nn.Module):
         enc = TransformerEncoderLayer(d_model, nhead, dim_feedforward, dropout, activation, normalize_before)
         dec = TransformerDecoderLayer(d_model, nhead, dim_feedforward, dropout, activation, normalize_before)
         enc.fused_ffn = dec.fused_ffn = True   # instance attributes: the clones carry them
+        enc.dense_attn = dec.dense_attn = True
         self.encoder = TransformerEncoder(enc, num_encoder_layers)
         self.decoder = TransformerDecoder(dec, num_decoder_layers, d_model, return_intermediate_dec)
         for p in self.parameters():
@@ -37,16 +42,16 @@ class Transformer(nn.Module):
         self.d_model = d_model
         self.nhead = nhead
 
-    def run(self, src, mask, query_embed, pos, tgt):
+    def run(self, src, mask, query_embed, pos, tgt, fast=True):
         """src / pos (B, HW, d), mask (B, HW) uint8 or bool (True = padding), query_embed / tgt
         (B, Q, d) -> hs (layers, B, Q, d) after the decoder norm, the same before it, memory
-        (B, HW, d)."""
-        memory = self.encoder.run(src, pos, mask, True)
-        hs, hs_without_norm = self.decoder.run(tgt, memory, pos, query_embed, mask, True)
+        (B, HW, d).  fast=False: the differentiable f32 graph (module docstring)."""
+        memory = self.encoder.run(src, pos, mask, fast)
+        hs, hs_without_norm = self.decoder.run(tgt, memory, pos, query_embed, mask, fast)
         return hs, hs_without_norm, memory
 
     def forward(self, *args, **kwargs):
-        raise NotImplementedError('Transformer is driven by DETR.forward through run() (inference kernels only)')
+        raise NotImplementedError('Transformer is driven by DETR.forward through run()')
 
 
 def build_transformer(args):
