@@ -141,6 +141,11 @@ _SIGS = {
     'kinet_segm_relu_up_add_backward': [P, P, P, P] + [I] * 9 + [P],
     'kinet_segm_out_conv_backward_workspace': [I, I, I, I],
     'kinet_segm_out_conv_backward': [P] * 6 + [I] * 4 + [P, P],
+    'kinet_track_decide': [P] * 6 + [I, I, I, I, F, F, F, I, P],
+    'kinet_nms_segments': [P, I64, P, I64, I64, P, P, P, P, I, I, F, P],
+    'kinet_track_commit': [P, P, P, I64, P, P, I, P, I64, I, P],
+    'kinet_track_gather': [P, I64, I, P, P, P, P, P, P, I, I, I, P],
+    'kinet_track_reid_dist': [P, I64, P, I64, I, P, P, P, P, P, P, I, I, P],
     'kinet_last_error': [],
     'kinet_version': [],
 }

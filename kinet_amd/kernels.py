@@ -2155,3 +2155,135 @@ def segm_out_conv_backward(dy, x, wt, need_x=True, need_w=True):
     N.call('kinet_segm_out_conv_backward', N.ptr(dy), N.ptr(x), N.ptr(wt), N.ptr(dx), N.ptr(dwt), N.ptr(db), rows, H, W,
            C, N.ptr(ws), N.stream(x.device), work={'family': 'segm', 'bytes': 4 * (dy.numel() + 2 * x.numel())})
     return dx, dwt, db
+
+
+# ------------------------------------------------------------------- multi-sequence tracker
+TRACK_MAX_ROWS = 4096                       # KINET_TRACK_MAX_ROWS (include/kinet_track.h)
+TRACK_DEC_TRACK, TRACK_DEC_REID, TRACK_DEC_DET, TRACK_DEC_PERSON = 1, 2, 4, 8
+
+
+def _track_arg(t, dtype, what):
+    if t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError(f'{what} must be contiguous {dtype}: got {t.dtype}, strides {t.stride()}')
+    return t
+
+
+def track_decide_views(out, S, N_):
+    """(boxes (S, N, 4) f32, scores (S, N) f32, labels (S, N) int32, decisions (S, N) uint8) of a packed
+    kinet_track_decide buffer (a uint8 torch tensor or numpy array of S*N*25 bytes)."""
+    r = S * N_
+    if isinstance(out, torch.Tensor):
+        return (out[:16 * r].view(torch.float32).view(S, N_, 4), out[16 * r:20 * r].view(torch.float32).view(S, N_),
+                out[20 * r:24 * r].view(torch.int32).view(S, N_), out[24 * r:25 * r].view(S, N_))
+    import numpy as np
+    return (out[:16 * r].view(np.float32).reshape(S, N_, 4), out[16 * r:20 * r].view(np.float32).reshape(S, N_),
+            out[20 * r:24 * r].view(np.int32).reshape(S, N_), out[24 * r:25 * r].reshape(S, N_))
+
+
+def track_decide(pred_logits, pred_boxes, sizes, n_active, n_inactive, Kmax, track_thresh, reid_thresh,
+                 detection_thresh, clip, out=None):
+    """DeformablePostProcess + clip_boxes_to_image + the tracker's threshold compares for S sequences in
+    one launch (kinet_track_decide): pred_logits (S, N, C) f32, pred_boxes (S, N, 4) f32, sizes (S, 2) f32
+    (h, w), n_active / n_inactive (S) int32 -> one packed uint8 buffer (S*N*25 bytes; track_decide_views)."""
+    N.require_gpu(pred_logits, pred_boxes, sizes, n_active, n_inactive, out)
+    if pred_logits.dim() != 3 or pred_boxes.shape != pred_logits.shape[:2] + (4,):
+        raise RuntimeError(f'track_decide: pred_logits (S, N, C) and pred_boxes (S, N, 4): got '
+                           f'{tuple(pred_logits.shape)}, {tuple(pred_boxes.shape)}')
+    S, N_, C = pred_logits.shape
+    _track_arg(pred_logits, torch.float32, 'track_decide: pred_logits')
+    _track_arg(pred_boxes, torch.float32, 'track_decide: pred_boxes')
+    _track_arg(sizes, torch.float32, 'track_decide: sizes')
+    _track_arg(n_active, torch.int32, 'track_decide: n_active')
+    _track_arg(n_inactive, torch.int32, 'track_decide: n_inactive')
+    if tuple(sizes.shape) != (S, 2) or n_active.numel() != S or n_inactive.numel() != S:
+        raise RuntimeError('track_decide: sizes must be (S, 2) and the counts (S,)')
+    if out is None:
+        out = torch.empty(S * N_ * 25, dtype=torch.uint8, device=pred_logits.device)
+    elif out.dtype != torch.uint8 or out.numel() != S * N_ * 25 or not out.is_contiguous():
+        raise RuntimeError('track_decide: out must be a contiguous uint8 buffer of S*N*25 bytes')
+    N.call('kinet_track_decide', N.ptr(pred_logits), N.ptr(pred_boxes), N.ptr(sizes), N.ptr(n_active), N.ptr(n_inactive),
+           N.ptr(out), S, N_, C, int(Kmax), float(track_thresh), float(reid_thresh), float(detection_thresh),
+           1 if clip else 0, N.stream(pred_logits.device), work={'family': 'track', 'bytes': S * N_ * (4 * C + 41)})
+    return out
+
+
+def nms_segments(boxes, scores, idx, offsets, total, iou_threshold, inf_flag=None, keep=None):
+    """S independent NMS problems in one launch (kinet_nms_segments): boxes (rows, 4) and scores (rows) f32
+    views of a shared bank (any row stride, unit inner stride), idx (>= total) int32 bank rows, offsets
+    (S + 1) int32, inf_flag (>= total) uint8 or None -> keep (total) uint8, one byte per list entry."""
+    N.require_gpu(boxes, scores, idx, offsets, inf_flag, keep)
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] != 4 \
+            or scores.dim() != 1 or scores.shape[0] != boxes.shape[0] or (boxes.shape[0] and boxes.stride(1) != 1):
+        raise RuntimeError('nms_segments: boxes (rows, 4) with unit inner stride and scores (rows) in f32')
+    _track_arg(idx, torch.int32, 'nms_segments: idx')
+    _track_arg(offsets, torch.int32, 'nms_segments: offsets')
+    S, total = offsets.numel() - 1, int(total)
+    if S < 0 or idx.numel() < total or (inf_flag is not None and (inf_flag.dtype != torch.uint8 or inf_flag.numel() < total
+                                                                    or not inf_flag.is_contiguous())):
+        raise RuntimeError('nms_segments: offsets (S + 1), idx and inf_flag (uint8) of at least `total` entries')
+    if keep is None:
+        keep = torch.empty(total, dtype=torch.uint8, device=boxes.device)
+    elif keep.dtype != torch.uint8 or keep.numel() < total or not keep.is_contiguous():
+        raise RuntimeError('nms_segments: keep must be contiguous uint8 of at least `total` entries')
+    rows = boxes.shape[0]
+    N.call('kinet_nms_segments', N.ptr(boxes), max(boxes.stride(0), 4) if rows else 4, N.ptr(scores),
+           max(scores.stride(0), 1) if rows else 1, rows, N.ptr(idx), N.ptr(offsets), N.ptr(inf_flag), N.ptr(keep), S,
+           total, float(iou_threshold), N.stream(boxes.device), work={'family': 'track', 'bytes': 24 * total})
+    return keep
+
+
+def track_commit(hs_embed, boxes, scores, rows, slots, n, bank):
+    """bank[slots[p]] = (hs_embed[rows[p]] | boxes[rows[p]] | scores[rows[p]]), p < n (kinet_track_commit):
+    hs_embed (R, d), boxes (R, 4), scores (R) f32 of the frame, rows / slots int32 (>= n), bank (capacity, d + 5)."""
+    N.require_gpu(hs_embed, boxes, scores, rows, slots, bank)
+    R, d = hs_embed.shape
+    for t, what in ((hs_embed, 'hs_embed'), (boxes, 'boxes'), (scores, 'scores'), (bank, 'bank')):
+        _track_arg(t, torch.float32, 'track_commit: ' + what)
+    _track_arg(rows, torch.int32, 'track_commit: rows')
+    _track_arg(slots, torch.int32, 'track_commit: slots')
+    if boxes.numel() != 4 * R or scores.numel() != R or bank.dim() != 2 or bank.shape[1] != d + 5 \
+            or rows.numel() < n or slots.numel() < n:
+        raise RuntimeError('track_commit: boxes (R, 4), scores (R), bank (capacity, d + 5), n rows and slots')
+    N.call('kinet_track_commit', N.ptr(hs_embed), N.ptr(boxes), N.ptr(scores), R, N.ptr(rows), N.ptr(slots), int(n),
+           N.ptr(bank), bank.shape[0], d, N.stream(bank.device), work={'family': 'track', 'bytes': 8 * n * (d + 5)})
+
+
+def track_gather(bank, slots, offsets, sizes, Kmax, Q):
+    """Next frame's track queries (kinet_track_gather): bank (capacity, d + 5) f32, slots int32, offsets
+    (S + 1) int32, sizes (S, 2) f32 (h, w) -> (embeds (S, Kmax, d) f32, cxcywh boxes (S, Kmax, 4) f32
+    normalised by the frame size, placeholder mask (S, Kmax + Q) bool)."""
+    N.require_gpu(bank, slots, offsets, sizes)
+    _track_arg(bank, torch.float32, 'track_gather: bank')
+    _track_arg(slots, torch.int32, 'track_gather: slots')
+    _track_arg(offsets, torch.int32, 'track_gather: offsets')
+    _track_arg(sizes, torch.float32, 'track_gather: sizes')
+    S, d = offsets.numel() - 1, bank.shape[1] - 5
+    if bank.dim() != 2 or d < 1 or tuple(sizes.shape) != (S, 2):
+        raise RuntimeError('track_gather: bank (capacity, d + 5), offsets (S + 1), sizes (S, 2)')
+    dev = bank.device
+    embeds = torch.empty((S, Kmax, d), dtype=torch.float32, device=dev)
+    boxes = torch.empty((S, Kmax, 4), dtype=torch.float32, device=dev)
+    mask = torch.empty((S, Kmax + Q), dtype=torch.bool, device=dev)
+    N.call('kinet_track_gather', N.ptr(bank), bank.shape[0], d, N.ptr(slots), N.ptr(offsets), N.ptr(sizes), N.ptr(embeds),
+           N.ptr(boxes), N.ptr(mask), S, int(Kmax), int(Q), N.stream(dev),
+           work={'family': 'track', 'bytes': 8 * S * Kmax * (d + 4)})
+    return embeds, boxes, mask
+
+
+def track_reid_dist(bank, hs_embed, slots, slot_off, rows, row_off, out_off, total):
+    """||bank_embed - hs_embed + 1e-6||_2 for every (inactive slot, detection row) pair of every sequence
+    (kinet_track_reid_dist), packed: sequence s's (a, b) matrix at out[out_off[s]:out_off[s + 1]]."""
+    N.require_gpu(bank, hs_embed, slots, slot_off, rows, row_off, out_off)
+    _track_arg(bank, torch.float32, 'track_reid_dist: bank')
+    _track_arg(hs_embed, torch.float32, 'track_reid_dist: hs_embed')
+    for t in (slots, slot_off, rows, row_off, out_off):
+        _track_arg(t, torch.int32, 'track_reid_dist: index lists')
+    R, d = hs_embed.shape
+    S = out_off.numel() - 1
+    if bank.dim() != 2 or bank.shape[1] != d + 5 or slot_off.numel() != S + 1 or row_off.numel() != S + 1:
+        raise RuntimeError('track_reid_dist: bank (capacity, d + 5), hs_embed (R, d), three (S + 1) offset lists')
+    out = torch.empty(int(total), dtype=torch.float32, device=bank.device)
+    N.call('kinet_track_reid_dist', N.ptr(bank), bank.shape[0], N.ptr(hs_embed), R, d, N.ptr(slots), N.ptr(slot_off),
+           N.ptr(rows), N.ptr(row_off), N.ptr(out_off), N.ptr(out), S, int(total), N.stream(bank.device),
+           work={'family': 'track', 'bytes': 8 * int(total) * d})
+    return out

@@ -599,6 +599,18 @@ class DeformableTransformer(nn.Module):
             query_embed_ = torch.cat([prev_query_embed.to(query_embed_.dtype), query_embed_], dim=1)
             tgt = torch.cat([prev_hs_embed.to(tgt.dtype), tgt], dim=1)
             reference_points = torch.cat([prev_boxes[..., :2].to(reference_points.dtype), reference_points], dim=1)
+            if 'track_queries_placeholder_mask' in targets[0]:
+                # ragged track queries (the reference's commented-out :230): sample i holds K_i <= Kmax
+                # queries, rows K_i..Kmax-1 are placeholders with finite values.  As keys they get
+                # probability exactly 0 in the decoder's self-attention, as queries they sample
+                # nothing; their own outputs are unspecified and no other row reads them.
+                if not fast_path(self):
+                    raise NotImplementedError('ragged track queries (track_queries_placeholder_mask) run the '
+                                              'inference path only: eval mode under torch.no_grad()')
+                query_attn_mask = torch.stack([t['track_queries_placeholder_mask'] for t in targets]).to(torch.uint8)
+                if tuple(query_attn_mask.shape) != tuple(tgt.shape[:2]):
+                    raise ValueError(f'track_queries_placeholder_mask must be (Kmax + Q,) = ({tgt.shape[1]},) per '
+                                     f'sample: got {tuple(query_attn_mask.shape[1:])}')
         init_reference_out = reference_points
         if fast_path(self) and tracking:
             dt = memory.dtype

@@ -87,6 +87,9 @@ class DETR(nn.Module):
         return geo
 
     def forward(self, samples, targets: list = None, prev_features=None):
+        if targets is not None and len(targets) and 'track_queries_placeholder_mask' in targets[0]:
+            raise NotImplementedError('vanilla DETR does not take ragged track queries '
+                                      '(track_queries_placeholder_mask): the Deformable detector does')
         if not isinstance(samples, NestedTensor):
             samples = nested_tensor_from_tensor_list(samples)
         if not fast_path(self):

@@ -60,6 +60,66 @@ def box_iou(boxes1, boxes2):
     return inter / (a1[:, None] + a2 - inter)
 
 
+def public_detections_mask(mode, new_det_boxes, public_det_boxes, iou_device=None):
+    """tracker.py:127-170 as a host mask: which of the new detections (xyxy) a public detection
+    claims.  `mode` is tracker_cfg['public_detections']; the IoU matrix of 'min_iou_0_5' is taken on
+    `iou_device` (None: where new_det_boxes lives).  Shared by Tracker and MultiTracker."""
+    n = new_det_boxes.size(0)
+    if not mode:
+        return torch.ones(n, dtype=torch.bool)
+    if not len(public_det_boxes) or not n:
+        return torch.zeros(n, dtype=torch.bool)
+    mask = torch.zeros(n, dtype=torch.bool)
+    if mode == 'center_distance':
+        nb = new_det_boxes.cpu()
+        item_size = ((nb[:, 2] - nb[:, 0]) * (nb[:, 3] - nb[:, 1])).numpy().astype(np.float32)
+        a = box_xyxy_to_cxcywh(nb).numpy()[:, :2]
+        b = box_xyxy_to_cxcywh(public_det_boxes.cpu()).numpy()[:, :2]
+        dist3 = ((a.reshape(-1, 1, 2) - b.reshape(1, -1, 2)) ** 2).sum(axis=2)
+        for j in range(len(public_det_boxes)):
+            i = dist3[:, j].argmin()
+            if dist3[i, j] < item_size[i]:
+                dist3[i, :] = 1e18
+                mask[i] = True
+    elif mode == 'min_iou_0_5':
+        dev = new_det_boxes.device if iou_device is None else iou_device
+        iou = box_iou(new_det_boxes.to(dev), public_det_boxes.to(dev)).cpu()
+        for j in range(len(public_det_boxes)):
+            i = iou[:, j].argmax()
+            if iou[i, j] >= 0.5:
+                iou[i, :] = 0
+                mask[i] = True
+    else:
+        raise NotImplementedError(mode)
+    return mask
+
+
+def reid_match_greedy(nb, ib):
+    """tracker.py:190-233: greedy centre-distance matching of inactive tracks (ib, (a, 4) cxcywh numpy)
+    with new detections (nb, (b, 4) cxcywh numpy) -> (dist_mat, rows, cols).  Shared by Tracker and
+    MultiTracker."""
+    dist_mat = ((ib[:, :2].reshape(-1, 1, 2) - nb[:, :2].reshape(1, -1, 2)) ** 2).sum(axis=2)
+    track_size = ib[:, 2] * ib[:, 3]
+    item_size = nb[:, 2] * nb[:, 3]
+    invalid = (dist_mat > track_size.reshape(-1, 1)) + (dist_mat > item_size.reshape(1, -1))
+    dist_mat = dist_mat + invalid * 1e18
+    matched = []
+    for i in range(dist_mat.shape[0]):
+        j = dist_mat[i].argmin()
+        if dist_mat[i][j] < 1e16:
+            dist_mat[:, j] = 1e18
+            dist_mat[i, j] = 0.0
+            matched.append([i, j])
+    matched = np.array(matched, np.int32).reshape(-1, 2)
+    return dist_mat, matched[:, 0], matched[:, 1]
+
+
+def reid_match_lsa(dist_mat):
+    """tracker.py:236-246: the linear-sum assignment of an (inactive track, detection) embedding
+    distance matrix -> (rows, cols).  Shared by Tracker and MultiTracker."""
+    return linear_sum_assignment(dist_mat)
+
+
 class Track:
     """tracker.py:1056-1130."""
 
@@ -196,33 +256,7 @@ class Tracker:
 
     def _public_detections_mask(self, new_det_boxes, public_det_boxes):
         """The mask on the host (step reads it there too: the rows that survive are host knowledge)."""
-        n = new_det_boxes.size(0)
-        if not self.public_detections:
-            return torch.ones(n, dtype=torch.bool)
-        if not len(public_det_boxes) or not n:
-            return torch.zeros(n, dtype=torch.bool)
-        mask = torch.zeros(n, dtype=torch.bool)
-        if self.public_detections == 'center_distance':
-            nb = new_det_boxes.cpu()
-            item_size = ((nb[:, 2] - nb[:, 0]) * (nb[:, 3] - nb[:, 1])).numpy().astype(np.float32)
-            a = box_xyxy_to_cxcywh(nb).numpy()[:, :2]
-            b = box_xyxy_to_cxcywh(public_det_boxes.cpu()).numpy()[:, :2]
-            dist3 = ((a.reshape(-1, 1, 2) - b.reshape(1, -1, 2)) ** 2).sum(axis=2)
-            for j in range(len(public_det_boxes)):
-                i = dist3[:, j].argmin()
-                if dist3[i, j] < item_size[i]:
-                    dist3[i, :] = 1e18
-                    mask[i] = True
-        elif self.public_detections == 'min_iou_0_5':
-            iou = box_iou(new_det_boxes, public_det_boxes.to(self.device)).cpu()
-            for j in range(len(public_det_boxes)):
-                i = iou[:, j].argmax()
-                if iou[i, j] >= 0.5:
-                    iou[i, :] = 0
-                    mask[i] = True
-        else:
-            raise NotImplementedError(self.public_detections)
-        return mask
+        return public_detections_mask(self.public_detections, new_det_boxes, public_det_boxes, self.device)
 
     def reid(self, new_det_boxes, new_det_scores, new_det_hs_embeds, new_det_rows=None):
         """tracker.py:172-267: re-identify inactive tracks with the new detections.  new_det_rows
@@ -237,25 +271,12 @@ class Tracker:
         if self.reid_greedy_matching:
             nb = box_xyxy_to_cxcywh(new_det_boxes).cpu().numpy()
             ib = box_xyxy_to_cxcywh(torch.stack([t.pos for t in self.inactive_tracks])).cpu().numpy()
-            dist_mat = ((ib[:, :2].reshape(-1, 1, 2) - nb[:, :2].reshape(1, -1, 2)) ** 2).sum(axis=2)
-            track_size = ib[:, 2] * ib[:, 3]
-            item_size = nb[:, 2] * nb[:, 3]
-            invalid = (dist_mat > track_size.reshape(-1, 1)) + (dist_mat > item_size.reshape(1, -1))
-            dist_mat = dist_mat + invalid * 1e18
-            matched = []
-            for i in range(dist_mat.shape[0]):
-                j = dist_mat[i].argmin()
-                if dist_mat[i][j] < 1e16:
-                    dist_mat[:, j] = 1e18
-                    dist_mat[i, j] = 0.0
-                    matched.append([i, j])
-            matched = np.array(matched, np.int32).reshape(-1, 2)
-            rows, cols = matched[:, 0], matched[:, 1]
+            dist_mat, rows, cols = reid_match_greedy(nb, ib)
         else:
             # F.pairwise_distance(track_sim, det_sim): ||x - y + 1e-6||_2, as one batched op
             sims = torch.stack([t.hs_embed[-1] for t in self.inactive_tracks])
             dist_mat = (sims[:, None, :] - new_det_hs_embeds[None, :, :] + 1e-6).norm(dim=-1).cpu().numpy()
-            rows, cols = linear_sum_assignment(dist_mat)
+            rows, cols = reid_match_lsa(dist_mat)
         assigned, remove_inactive = [], []
         for r, c in zip(rows, cols):
             if dist_mat[r, c] <= self.reid_sim_threshold:
@@ -773,3 +794,426 @@ class TrackerKinematic(Tracker):
         for t in self.inactive_tracks:
             t.count_inactive += 1
         self.frame_index += 1
+
+
+# ---------------------------------------------------------------------------------- multi-sequence
+# S independent sequences advanced in lock-step on ONE batched detector forward per frame (DESIGN.md
+# section 4 "Multi-sequence tracker").  Sequence i holds K_i track queries; the batch carries
+# Kmax = max K_i rows per sample and marks rows K_i..Kmax-1 as placeholders
+# (targets[i]['track_queries_placeholder_mask'], kinet_amd/models/deformable_transformer.py).  The
+# tracks' embeddings, boxes and scores live in a device table (the track bank, one row = slot per
+# track, include/kinet_track.h); the state machine of each sequence is Tracker.step's, statement by
+# statement, on host mirrors (numpy) of the boxes and scores.
+
+def plan_track_queries(n_active, n_inactive, num_queries):
+    """The host plan of one frame's track queries: per-sequence counts of active and inactive tracks ->
+    {'K': (S,) int32 K_i = n_active[i] + n_inactive[i], 'Kmax': max K_i, 'offsets': (S + 1,) int32 starts of
+    the sequences' slot lists in one flat list, 'mask': (S, Kmax + Q) bool, True exactly on rows K_i..Kmax-1}."""
+    k = np.asarray(n_active, np.int64).reshape(-1) + np.asarray(n_inactive, np.int64).reshape(-1)
+    if k.size == 0 or (k < 0).any():
+        raise ValueError(f'plan_track_queries: counts {list(n_active)}, {list(n_inactive)}')
+    kmax = int(k.max())
+    if kmax + num_queries > K.TRACK_MAX_ROWS:
+        raise ValueError(f'{kmax} track queries + {num_queries} object queries exceed the tracker kernels\' '
+                         f'{K.TRACK_MAX_ROWS} rows per sequence')
+    offsets = np.zeros(k.size + 1, np.int32)
+    offsets[1:] = np.cumsum(k)
+    col = np.arange(kmax + num_queries)[None, :]
+    mask = (col >= k[:, None]) & (col < kmax)
+    return {'K': k.astype(np.int32), 'Kmax': kmax, 'offsets': offsets, 'mask': mask}
+
+
+class _SlotTrack:
+    """One track of a MultiTracker sequence: Track's bookkeeping fields with host mirrors (numpy f32) of
+    the box and the score; the embedding and the device copies are row `slot` of the track bank.  (Track's
+    last_pos history feeds nothing the tracker outputs and is not kept.)"""
+    __slots__ = ('id', 'pos', 'score', 'slot', 'obj_ind', 'count_inactive', 'count_termination')
+
+    def __init__(self, pos, score, track_id, slot, obj_ind):
+        self.id, self.pos, self.score, self.slot, self.obj_ind = track_id, pos, score, slot, obj_ind
+        self.count_inactive = 0
+        self.count_termination = 0
+
+
+class _Sequence:
+    def __init__(self):
+        self.retired = False
+        self.tracks, self.inactive_tracks = [], []
+        self.track_num = self.frame_index = self.num_reids = 0
+        self.results = {}
+
+
+class MultiTracker:
+    """`num_sequences` Trackers in one: reset(), step(blobs) with one blob per live sequence (the keys
+    Tracker.step reads; frame sizes may differ), retire(i), get_results() -> one Tracker.get_results()
+    dict per sequence.  Track ids, track_num, num_reids and frame_index are per sequence
+    (`sequence(i)`).  Every device -> host transfer of step goes through `_to_host`, which counts
+    them in `sync_count`: at most four per step (decisions, track NMS, re-identification distances,
+    detection NMS), each skipped when no sequence needs it, whatever S is."""
+
+    def __init__(self, obj_detector, obj_detector_post, tracker_cfg, num_sequences, logger=None,
+                 generate_attention_maps=False):
+        from kinet_amd.models.deformable_detr import DeformablePostProcess
+        from kinet_amd.models.kinet import KinematicDetectorTransformer
+        if generate_attention_maps or tracker_cfg.get('generate_attention_maps', False):
+            raise NotImplementedError('attention maps (tracker.py:38-40) need the decoder\'s attention '
+                                      'probabilities, which the fused attention kernels do not export')
+        if tracker_cfg.get('masks', False):
+            raise NotImplementedError('MultiTracker does not carry segmentation masks (MOTS): use Tracker')
+        if 'segm' in obj_detector_post:
+            raise NotImplementedError('MultiTracker takes the \'bbox\' postprocessor alone (no \'segm\')')
+        if type(obj_detector_post.get('bbox')) is not DeformablePostProcess:
+            raise NotImplementedError('MultiTracker runs DeformablePostProcess on the device '
+                                      '(kinet_track_decide); other postprocessors are not built')
+        if isinstance(obj_detector, KinematicDetectorTransformer):
+            raise NotImplementedError('MultiTracker does not drive the kinematic detector: use TrackerKinematic')
+        if num_sequences < 1:
+            raise ValueError(f'num_sequences={num_sequences}')
+        self.obj_detector = obj_detector
+        self.obj_detector_post = obj_detector_post
+        self.num_sequences = int(num_sequences)
+        self.detection_obj_score_thresh = tracker_cfg['detection_obj_score_thresh']
+        self.track_obj_score_thresh = tracker_cfg['track_obj_score_thresh']
+        self.detection_nms_thresh = tracker_cfg['detection_nms_thresh']
+        self.track_nms_thresh = tracker_cfg['track_nms_thresh']
+        self.public_detections = tracker_cfg['public_detections']
+        self.inactive_patience = float(tracker_cfg['inactive_patience'])
+        self.reid_sim_threshold = tracker_cfg['reid_sim_threshold']
+        self.reid_sim_only = tracker_cfg['reid_sim_only']
+        self.reid_score_thresh = tracker_cfg['reid_score_thresh']
+        self.reid_greedy_matching = tracker_cfg['reid_greedy_matching']
+        self.prev_frame_dist = tracker_cfg['prev_frame_dist']
+        self.steps_termination = tracker_cfg['steps_termination']
+        self._logger = logger if logger is not None else (lambda *a: None)
+        self.sync_count = 0
+        self.reset()
+
+    @property
+    def num_object_queries(self):
+        return self.obj_detector.num_queries
+
+    @property
+    def device(self):
+        return next(self.obj_detector.parameters()).device
+
+    def reset(self):
+        self._seqs = [_Sequence() for _ in range(self.num_sequences)]
+        self._prev_features = deque([None], maxlen=self.prev_frame_dist)
+        self._bank = None            # (capacity, d + 5) f32, allocated at the first frame (d is the detector's)
+        self._free_slots, self._next_slot = [], 0
+        self._pending = ([], [])     # (frame rows, bank slots) to commit with the next launch
+        self._sizes_key, self._sizes = None, None
+        self.sync_count = 0
+
+    def sequence(self, i):
+        """The per-sequence counters: .track_num, .num_reids, .frame_index, .tracks, .inactive_tracks."""
+        return self._seqs[i]
+
+    def live_sequences(self):
+        return [i for i, q in enumerate(self._seqs) if not q.retired]
+
+    def get_results(self):
+        return [q.results for q in self._seqs]
+
+    def retire(self, i):
+        """Remove sequence i for good: its results stay, its slots are freed and every cached
+        previous-feature NestedTensor loses its batch row."""
+        q = self._seqs[i]
+        if q.retired:
+            raise ValueError(f'sequence {i} is already retired')
+        row = self.live_sequences().index(i)
+        for t in q.tracks + q.inactive_tracks:
+            self._free(t.slot)
+        q.tracks, q.inactive_tracks = [], []
+        q.retired = True
+        self._sizes_key = None
+        for features in self._prev_features:
+            if features is None:
+                continue
+            for f in features:
+                if not hasattr(f, 'tensors'):
+                    continue
+                keep = [r for r in range(f.tensors.shape[0]) if r != row]
+                f.tensors = f.tensors[keep]
+                if f.mask is not None:
+                    f.mask = f.mask[keep]
+                if getattr(f, 'sizes', None) is not None:
+                    f.sizes = tuple(s for r, s in enumerate(f.sizes) if r != row)
+
+    # ------------------------------------------------------------------ device plumbing
+    def _to_host(self, t):
+        """THE device -> host transfer of step (each one waits for the stream)."""
+        self.sync_count += 1
+        return t.cpu().numpy()
+
+    def _upload(self, *arrays):
+        """Small host index arrays (int32 / uint8) as views of ONE device buffer: one pinned,
+        non-blocking copy per phase of the step."""
+        parts, spans, o = [], [], 0
+        for a in arrays:
+            b = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+            pad = (-b.size) % 4
+            parts += [b, np.zeros(pad, np.uint8)]
+            spans.append((o, b.size, a.dtype))
+            o += b.size + pad
+        host = np.concatenate(parts) if o else np.zeros(4, np.uint8)
+        buf = torch.from_numpy(host)
+        buf = buf.pin_memory().to(self.device, non_blocking=True) if self.device.type == 'cuda' else buf
+        return [buf[s:s + n] if dt == np.uint8 else buf[s:s + n].view(torch.int32) for s, n, dt in spans]
+
+    def _alloc(self):
+        if self._free_slots:
+            return self._free_slots.pop()
+        if self._next_slot == self._bank.shape[0]:
+            grown = torch.zeros((2 * self._bank.shape[0], self._bank.shape[1]), dtype=torch.float32, device=self.device)
+            grown[:self._bank.shape[0]] = self._bank
+            self._bank = grown
+        self._next_slot += 1
+        return self._next_slot - 1
+
+    def _free(self, slot):
+        rows, slots = self._pending
+        if slot in slots:
+            keep = [p for p, s in enumerate(slots) if s != slot]
+            self._pending = ([rows[p] for p in keep], [slots[p] for p in keep])
+        self._free_slots.append(slot)
+
+    def _flush(self, frame, *arrays):
+        """Upload `arrays` together with the pending commits and launch the commit -> the arrays' device views."""
+        rows, slots = self._pending
+        self._pending = ([], [])
+        if not rows and not arrays:
+            return []
+        dev = self._upload(np.asarray(rows, np.int32), np.asarray(slots, np.int32), *arrays)
+        if rows:
+            K.track_commit(frame['hs'], frame['boxes'], frame['scores'], dev[0], dev[1], len(rows), self._bank)
+        return dev[2:]
+
+    def _nms(self, frame, segments, thresh, flags=None):
+        """One kinet_nms_segments launch over the bank for the listed sequences' slot lists -> the keep
+        lists, or None when no sequence has a segment (no launch, no transfer; the pending commits wait
+        for the next launch)."""
+        if not any(len(s) for s in segments):
+            return None
+        offsets = np.zeros(len(segments) + 1, np.int32)
+        offsets[1:] = np.cumsum([len(s) for s in segments])
+        idx = np.asarray([t for s in segments for t in s], np.int32)
+        total = int(offsets[-1])
+        d = self._bank.shape[1] - 5
+        if flags is None:
+            idx_d, off_d = self._flush(frame, idx, offsets)
+            flag_d = None
+        else:
+            idx_d, off_d, flag_d = self._flush(frame, idx, offsets, np.asarray([f for s in flags for f in s], np.uint8))
+        keep = self._to_host(K.nms_segments(self._bank[:, d:d + 4], self._bank[:, d + 4], idx_d, off_d, total, thresh,
+                                            inf_flag=flag_d))
+        return [keep[offsets[b]:offsets[b + 1]] for b in range(len(segments))]
+
+    # ------------------------------------------------------------------ bookkeeping (Tracker's, per sequence)
+    def _prune_inactive(self, q):
+        kept = []
+        for t in q.inactive_tracks:
+            if t.pos[2] > t.pos[0] and t.pos[3] > t.pos[1] and t.count_inactive <= self.inactive_patience:
+                kept.append(t)
+            else:
+                self._free(t.slot)
+        q.inactive_tracks = kept
+
+    def _remove_tracks(self, q, keep, what, thresh):
+        remove = [t for t, k in zip(q.tracks, keep) if not k]
+        if remove:
+            self._logger(f'REMOVE TRACK IDS ({what}={thresh}): {[t.id for t in remove]}')
+            for t in remove:
+                self._free(t.slot)
+            q.tracks = [t for t in q.tracks if t not in remove]
+
+    # ------------------------------------------------------------------ one frame of every live sequence
+    @torch.no_grad()
+    def step(self, blobs):
+        """Tracker.step for every live sequence: blobs[j] belongs to the j-th live sequence."""
+        from kinet_amd.models.misc import nested_tensor_from_tensor_list
+        live = self.live_sequences()
+        if len(blobs) != len(live):
+            raise ValueError(f'step takes one blob per live sequence: {len(live)} live, {len(blobs)} blobs')
+        if not live:
+            return
+        seqs = [self._seqs[i] for i in live]
+        B, Q, dev = len(seqs), self.num_object_queries, self.device
+        for q in seqs:
+            self._prune_inactive(q)
+            self._logger(f'FRAME: {q.frame_index + 1}')
+        samples = nested_tensor_from_tensor_list([b['img'].to(dev).reshape(b['img'].shape[-3:]) for b in blobs])
+        key = tuple(b['orig_size'] for b in blobs)
+        if self._sizes_key is None or len(key) != len(self._sizes_key) or any(a is not b for a, b in zip(key, self._sizes_key)):
+            # (the blobs of a sequence usually share one orig_size tensor: converted once)
+            self._sizes_key = key
+            self._sizes = torch.cat([t.reshape(-1)[:2].reshape(1, 2) for t in key]).to(dev, torch.float32).contiguous()
+        sizes = self._sizes
+
+        plan = plan_track_queries([len(q.tracks) for q in seqs], [len(q.inactive_tracks) for q in seqs], Q)
+        Kmax, Nrows = plan['Kmax'], plan['Kmax'] + Q
+        n_act = np.asarray([len(q.tracks) for q in seqs], np.int32)
+        slots = np.asarray([t.slot for q in seqs for t in q.tracks + q.inactive_tracks], np.int32)
+        n_act_d, n_inact_d, off_d, slots_d = self._upload(n_act, plan['K'] - n_act, plan['offsets'], slots)
+        targets = None
+        if Kmax:
+            embeds, qboxes, mask = K.track_gather(self._bank, slots_d, off_d, sizes, Kmax, Q)
+            targets = [{'track_query_boxes': qboxes[b], 'track_query_hs_embeds': embeds[b],
+                        'track_queries_placeholder_mask': mask[b]} for b in range(B)]
+        outputs, _, features, _, _ = self.obj_detector(samples, targets, self._prev_features[0])
+        hs = outputs['hs_embed'].float().contiguous()
+        logits = outputs['pred_logits'].float().contiguous()
+        if tuple(logits.shape[:2]) != (B, Nrows):
+            raise RuntimeError(f'the detector returned {tuple(logits.shape[:2])} rows for {B} sequences of {Kmax} track '
+                               f'+ {Q} object queries')
+        d = hs.shape[-1]
+        if self._bank is None:
+            self._bank = torch.zeros((256, d + 5), dtype=torch.float32, device=dev)
+        packed = K.track_decide(logits, outputs['pred_boxes'].float().contiguous(), sizes, n_act_d, n_inact_d, Kmax,
+                                self.track_obj_score_thresh, self.reid_score_thresh, self.detection_obj_score_thresh,
+                                not self.obj_detector.overflow_boxes)
+        boxes_d, scores_d, _, _ = K.track_decide_views(packed, B, Nrows)
+        frame = {'hs': hs.view(B * Nrows, d), 'boxes': boxes_d.view(B * Nrows, 4), 'scores': scores_d.view(B * Nrows)}
+        # every box, score and threshold decision of this frame, all sequences, in ONE copy
+        boxes, scores, _, dec = K.track_decide_views(self._to_host(packed), B, Nrows)
+        person = (dec & K.TRACK_DEC_PERSON) != 0
+
+        def update(b, row, track):
+            """The track takes row `row` of sequence b's outputs: host mirrors now, its bank slot with the
+            next launch."""
+            track.score = scores[b, row]
+            track.pos = boxes[b, row].copy()
+            self._pending[0].append(b * Nrows + row)
+            self._pending[1].append(track.slot)
+
+        # tracks kept / terminated / re-identified by score, then track NMS (tracker.py:351-447)
+        segments = []
+        for b, q in enumerate(seqs):
+            nt = int(plan['K'][b])
+            if not nt:
+                segments.append([])
+                continue
+            track_keep = ((dec[b, :nt] & K.TRACK_DEC_TRACK) != 0) & person[b, :nt]
+            reid_keep = ((dec[b, :nt] & K.TRACK_DEC_REID) != 0) & person[b, :nt]
+            to_inactive, from_inactive = [], []
+            for i, track in enumerate(q.tracks):
+                if track_keep[i]:
+                    update(b, i, track)
+                    track.count_termination = 0
+                else:
+                    track.count_termination += 1
+                    if track.count_termination >= self.steps_termination:
+                        to_inactive.append(track)
+            for i, track in enumerate(q.inactive_tracks, start=len(q.tracks)):
+                if reid_keep[i]:
+                    update(b, i, track)
+                    from_inactive.append(track)
+            if to_inactive:
+                self._logger(f'NEW INACTIVE TRACK IDS (track_obj_score_thresh={self.track_obj_score_thresh}): '
+                             f'{[t.id for t in to_inactive]}')
+            q.num_reids += len(from_inactive)
+            for track in from_inactive:
+                q.inactive_tracks.remove(track)
+                q.tracks.append(track)
+            q.tracks = [t for t in q.tracks if t not in to_inactive]
+            q.inactive_tracks += to_inactive
+            segments.append([t.slot for t in q.tracks] if self.track_nms_thresh else [])
+        keeps = self._nms(frame, segments, self.track_nms_thresh)
+        if keeps is not None:
+            for q, seg, keep in zip(seqs, segments, keeps):
+                if seg:
+                    self._remove_tracks(q, keep, 'track_nms_thresh', self.track_nms_thresh)
+
+        # new detections (tracker.py:456-505): thresholds and public-detection gating on the host mirrors
+        dets = []
+        for b, (q, blob) in enumerate(zip(seqs, blobs)):
+            det_keep = (((dec[b, Kmax:] & K.TRACK_DEC_DET) != 0) & person[b, Kmax:]).nonzero()[0]
+            new_boxes = torch.from_numpy(boxes[b, Kmax:][det_keep])
+            pub_dets = blob['dets'][0] if 'dets' in blob else []
+            pub = public_detections_mask(self.public_detections, new_boxes,
+                                         pub_dets.cpu() if torch.is_tensor(pub_dets) else pub_dets).numpy()
+            det_keep = det_keep[pub]
+            self._prune_inactive(q)                          # (Tracker._reid's first statement)
+            dets.append(det_keep)
+        dist = [None] * B
+        if not self.reid_greedy_matching:
+            need = [b for b, q in enumerate(seqs) if q.inactive_tracks and len(dets[b])]
+            if need:
+                # the embedding distances of every sequence that has inactive tracks and new detections
+                a_off, r_off, o_off = (np.zeros(B + 1, np.int32) for _ in range(3))
+                a_list, r_list = [], []
+                for b, q in enumerate(seqs):
+                    if b in need:
+                        a_list += [t.slot for t in q.inactive_tracks]
+                        r_list += (dets[b] + (b * Nrows + Kmax)).tolist()
+                    a_off[b + 1], r_off[b + 1] = len(a_list), len(r_list)
+                    o_off[b + 1] = o_off[b] + (a_off[b + 1] - a_off[b]) * (r_off[b + 1] - r_off[b])
+                a_d, ao_d, r_d, ro_d, oo_d = self._flush(frame, np.asarray(a_list, np.int32), a_off,
+                                                         np.asarray(r_list, np.int32), r_off, o_off)
+                flat = self._to_host(K.track_reid_dist(self._bank, frame['hs'], a_d, ao_d, r_d, ro_d, oo_d, int(o_off[-1])))
+                for b in need:
+                    dist[b] = flat[o_off[b]:o_off[b + 1]].reshape(a_off[b + 1] - a_off[b], r_off[b + 1] - r_off[b])
+
+        # re-identification, new tracks, detection NMS (tracker.py:172-267, :505-527)
+        segments, flags = [], []
+        for b, q in enumerate(seqs):
+            det_keep = dets[b]
+            n = len(det_keep)
+            reid_mask = np.ones(n, bool)
+            if q.inactive_tracks and n:
+                if self.reid_greedy_matching:
+                    nb = box_xyxy_to_cxcywh(torch.from_numpy(boxes[b, Kmax:][det_keep])).numpy()
+                    ib = box_xyxy_to_cxcywh(torch.from_numpy(np.stack([t.pos for t in q.inactive_tracks]))).numpy()
+                    dist_mat, rows, cols = reid_match_greedy(nb, ib)
+                else:
+                    dist_mat = dist[b]
+                    rows, cols = reid_match_lsa(dist_mat)
+                remove_inactive = []
+                for r, c in zip(rows, cols):
+                    if dist_mat[r, c] <= self.reid_sim_threshold:
+                        track = q.inactive_tracks[r]
+                        self._logger(f'REID: track.id={track.id} - count_inactive={track.count_inactive} - '
+                                     f'to_inactive_frame={q.frame_index - track.count_inactive}')
+                        track.count_inactive = 0
+                        update(b, Kmax + int(det_keep[c]), track)
+                        reid_mask[c] = False
+                        remove_inactive.append(track)
+                        q.tracks.append(track)
+                        q.num_reids += 1
+                for track in remove_inactive:
+                    q.inactive_tracks.remove(track)
+            new_ids = []
+            for j in det_keep[reid_mask].tolist():
+                track = _SlotTrack(None, None, q.track_num + len(new_ids), self._alloc(), j)
+                update(b, Kmax + j, track)
+                q.tracks.append(track)
+                new_ids.append(track.id)
+            q.track_num += len(new_ids)
+            if new_ids:
+                self._logger(f'INIT TRACK IDS (detection_obj_score_thresh={self.detection_obj_score_thresh}): {new_ids}')
+            if self.detection_nms_thresh and q.tracks:
+                fresh = set(new_ids)
+                segments.append([t.slot for t in q.tracks])
+                flags.append([t.id not in fresh for t in q.tracks])   # existing tracks always win (:519)
+            else:
+                segments.append([])
+                flags.append([])
+        keeps = self._nms(frame, segments, self.detection_nms_thresh, flags)
+        if keeps is not None:
+            for q, seg, keep in zip(seqs, segments, keeps):
+                if seg:
+                    self._remove_tracks(q, keep, 'detection_nms_thresh', self.detection_nms_thresh)
+        self._flush(frame)                                   # (commits no launch of this frame carried)
+
+        # results (tracker.py:529-552) from the host mirrors: decide already clipped them to the image
+        for q in seqs:
+            for track in q.tracks:
+                q.results.setdefault(track.id, {})[q.frame_index] = {
+                    'bbox': track.pos.copy(), 'score': np.float32(track.score), 'obj_ind': int(track.obj_ind)}
+            for t in q.inactive_tracks:
+                t.count_inactive += 1
+            q.frame_index += 1
+            if self.reid_sim_only:
+                q.inactive_tracks += q.tracks
+                q.tracks = []
+        self._prev_features.append(features)
