@@ -86,6 +86,62 @@ int kinet_segm_track_resolve(const float* logits, const int32_t* src, const int1
                              float threshold, kinet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ragged rows (the multi-sequence tracker's masks): the kept rows of several frames in one call.
+ * The three entry points above that broadcast a per-frame operand have a twin that takes
+ * `row_frame`, a DEVICE list of one int32 per row of the call: row r reads frame row_frame[r]
+ * where the frame-major entry point reads frame (row0 + r) / Q.  The kernels are the same (one
+ * body; the frame-major entry points pass NULL), so a row's result is bit-identical to what the
+ * frame-major call gives that row.  The list lives on the device, so the kernels guard it: a row
+ * whose entry is outside [0, B) reads nothing through it and its output row is left untouched.
+ * All other limits are those of the twin.
+ * ------------------------------------------------------------------------------------------- */
+
+/* kinet_segm_attention over gathered rows: qp (rows, d), kp (B, HW, d), mask (B, HW) or NULL,
+ * out (rows, HW, heads). */
+int kinet_segm_attention_rows(const void* qp, const void* kp, const uint8_t* mask, const int32_t* row_frame, void* out,
+                              int rows, int B, int HW, int heads, int d, float scale, int dtype, kinet_stream_t stream);
+
+/* kinet_segm_lay1: y[r] = frame[row_frame[r]] + conv3x3_pad1(att[r]; w_att). */
+int kinet_segm_lay1_rows(const void* att, const float* w_att, const float* frame, const int32_t* row_frame, void* y,
+                         int rows, int B, int H, int W, int Ca, int Cout, int dtype, kinet_stream_t stream);
+
+/* kinet_segm_gn_relu_up_add with f[row_frame[r]] as the FPN operand.  Without f nothing is read per
+ * frame: row_frame may be NULL and is not looked at.  ws: kinet_segm_gn_workspace(rows, h*w, groups). */
+int kinet_segm_gn_relu_up_add_rows(const void* x, const float* gamma, const float* beta, const void* f,
+                                   const int32_t* row_frame, void* y, int rows, int B, int h, int w, int H, int W, int C,
+                                   int groups, float eps, int dtype, float* ws, kinet_stream_t stream);
+
+/* kinet_segm_track_resolve for S sequences in one launch, with each slot's pixel count and box.
+ * Sequence s owns the slots src[src_off[s] .. src_off[s+1]-1] (entries as above: >= 0 a row of the
+ * shared logits (n, h, w), < 0 the stale slot -e-1 of ITS previous map), the frame geometry
+ * geom[s] = (img_h, img_w, oh, ow) inside the one padded (max_h, max_w), the (oh, ow) label map at
+ * labels + pix_off[s] (elements; pix_off[s+1] - pix_off[s] >= oh*ow) and its previous map at
+ * prev_labels + prev_off[s] (prev_off[s] < 0: none, every stale slot is then empty).  labels and
+ * prev_labels are two buffers.
+ *   labels: per pixel the LOCAL slot t - src_off[s] that owns it or -1, exactly what
+ *           kinet_segm_track_resolve writes for that sequence alone (the same device functions);
+ *   stats (total, 5) int32: per slot (count, x0, y0, x1, y1), the number of pixels that carry its
+ *           label and their half-open box; (0, 0, 0, 0, 0) for a slot without a pixel.
+ * src, logits, labels, prev_labels, stats are DEVICE buffers; src_off (S + 1) int32, geom (S, 4)
+ * int32, pix_off (S + 1) int64 and prev_off (S) int64 are HOST arrays (checked here, before any
+ * launch, and handed to the kernel as arguments, RESOLVE_SEGS = 32 segments per launch: S <= 32
+ * is one resolve launch, more take ceil(S / 32)).  A segment holds at most 32767 slots and may be
+ * empty (its map is all -1); a segment with oh*ow == 0 has no map and nothing of it is touched.
+ * A fresh entry >= n counts as 0.0 and reads nothing.  S == 0, or no slot and no pixel, launches
+ * nothing.
+ * The statistics are integer counts and extrema: the first 256 slots of a segment gather in an LDS
+ * table per workgroup (LDS integer atomics) and merge into stats with global integer atomics,
+ * later slots use global atomics directly; integer add / min / max commute, so reruns are
+ * bit-identical.  stats is cleared by a memset before and finished by a small kernel after the
+ * resolve launch (both on `stream`).  No float atomics.
+ * Callers that want one device -> host copy put stats (20 bytes per slot) and labels into one
+ * allocation, stats first. */
+int kinet_segm_track_resolve_segments(const float* logits, const int32_t* src, const int32_t* src_off,
+                                      const int32_t* geom, const int64_t* pix_off, const int16_t* prev_labels,
+                                      const int64_t* prev_off, int16_t* labels, int32_t* stats, int S, int total, int n,
+                                      int h, int w, int max_h, int max_w, float threshold, kinet_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Mask training (csrc/segm_train.hip): the fused mask losses and the backward of the head's own
  * ops.  f32 only (the training path is f32).  No float atomics; every sum is taken in an order
  * fixed by the shapes alone, so reruns are bit-identical.

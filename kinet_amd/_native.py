@@ -132,6 +132,10 @@ _SIGS = {
     'kinet_segm_out_conv': [P, P, P, P, I, I, I, I, I, P],
     'kinet_segm_postprocess': [P, P] + [I] * 9 + [F, I, P],
     'kinet_segm_track_resolve': [P, P, P, P] + [I] * 10 + [F, P],
+    'kinet_segm_attention_rows': [P, P, P, P, P, I, I, I, I, I, F, I, P],
+    'kinet_segm_lay1_rows': [P] * 5 + [I] * 7 + [P],
+    'kinet_segm_gn_relu_up_add_rows': [P] * 6 + [I] * 8 + [F, I, P, P],
+    'kinet_segm_track_resolve_segments': [P] * 9 + [I] * 7 + [F, P],
     'kinet_segm_mask_loss_workspace': [I, I, I],
     'kinet_segm_mask_loss': [P, P, P, P] + [I] * 5 + [F, F, F, P, P],
     'kinet_segm_mask_loss_backward': [P] * 5 + [I] * 5 + [F, F, F, P],

@@ -36,6 +36,13 @@ inline int segm_grid(long total) {
     return (int)(blocks < 1 ? 1 : (blocks > 8L * kMaxGridStride ? 8L * kMaxGridStride : blocks));
 }
 
+// The frame whose per-frame operand row r of a call reads: frame-major rows (row_frame == nullptr:
+// global row / Q) or a ragged list with one entry per row of the call.  A workgroup-uniform read;
+// the kernels leave a row alone when the entry is outside [0, B).
+__device__ __forceinline__ int segm_row_frame(const int32_t* __restrict__ row_frame, int r, int global_row, int Q) {
+    return row_frame ? row_frame[r] : global_row / Q;
+}
+
 // ---------------------------------------------------------------------------------
 // attention map: one workgroup per (frame, query) row, items (pixel, head) strided over the
 // threads so that a thread keeps its head (256 % heads == 0) and a wave reads whole key rows
@@ -64,11 +71,15 @@ __device__ __forceinline__ float att_logit(const T* __restrict__ krow, const flo
 
 template <typename T>
 __global__ __launch_bounds__(256) void segm_attention_kernel(const T* __restrict__ qp, const T* __restrict__ kp,
-                                                             const uint8_t* __restrict__ mask, T* __restrict__ out,
-                                                             int Q, int HW, int heads, int d, float scale) {
+                                                             const uint8_t* __restrict__ mask,
+                                                             const int32_t* __restrict__ row_frame,
+                                                             T* __restrict__ out, int B, int Q, int HW, int heads,
+                                                             int d, float scale) {
     extern __shared__ float q_s[];   // [d], pre-scaled (the reference scales q, :210)
     __shared__ MaxSum wave_ms[4];
-    const int r = blockIdx.x, b = r / Q;
+    const int r = blockIdx.x;
+    const int b = segm_row_frame(row_frame, r, r, Q);
+    if (b < 0 || b >= B) return;   // (a ragged row whose entry names no frame: the whole workgroup leaves)
     const int D = d / heads;
     for (int k = threadIdx.x; k < d; k += 256) q_s[k] = to_f32(qp[(long)r * d + k]) * scale;
     __syncthreads();
@@ -118,10 +129,13 @@ constexpr int LAY1_TR = 4, LAY1_TW = 32, LAY1_CA = 8;
 
 template <typename T>
 __global__ __launch_bounds__(512) void segm_lay1_kernel(const T* __restrict__ att, const float* __restrict__ w_att,
-                                                         const float* __restrict__ frame, T* __restrict__ y, int row0,
-                                                         int Q, int H, int W, int Cout) {
+                                                         const float* __restrict__ frame,
+                                                         const int32_t* __restrict__ row_frame, T* __restrict__ y,
+                                                         int row0, int Q, int B, int H, int W, int Cout) {
     __shared__ float4 tile[LAY1_TR + 2][LAY1_TW + 2][LAY1_CA / 4];
-    const int r = blockIdx.z, b = (row0 + r) / Q;
+    const int r = blockIdx.z;
+    const int b = segm_row_frame(row_frame, r, row0 + r, Q);
+    if (b < 0 || b >= B) return;
     const int y0 = blockIdx.y * LAY1_TR, x0 = blockIdx.x * LAY1_TW;
     float* tf = reinterpret_cast<float*>(tile);
     constexpr int TILE_N = (LAY1_TR + 2) * (LAY1_TW + 2) * LAY1_CA;
@@ -276,10 +290,13 @@ __global__ __launch_bounds__(256) void segm_gn_apply_kernel(const T* __restrict_
                                                             const float* __restrict__ piv,
                                                             const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, const T* __restrict__ f,
-                                                            T* __restrict__ y, int row0, int Q, int h, int w, int H,
-                                                            int W, int C, int groups, float eps, float sh, float sw) {
+                                                            const int32_t* __restrict__ row_frame, T* __restrict__ y,
+                                                            int row0, int Q, int B, int h, int w, int H, int W, int C,
+                                                            int groups, float eps, float sh, float sw) {
     extern __shared__ float mr[];   // [groups] mean, [groups] rstd
     const int n = blockIdx.y;
+    const int fb = segm_row_frame(row_frame, n, row0 + n, Q);
+    if (row_frame && (fb < 0 || fb >= B)) return;
     const int cpg = C / groups, CV = C / SEGM_GN_V;
     const float cnt = (float)h * (float)w * (float)cpg;
     for (int g = threadIdx.x; g < groups; g += 256) {
@@ -312,7 +329,7 @@ __global__ __launch_bounds__(256) void segm_gn_apply_kernel(const T* __restrict_
         }
         if (f) {
             float fv[SEGM_GN_V];
-            load8(f + (((long)((row0 + n) / Q) * H + Y) * W + X) * C + c0, fv);
+            load8(f + (((long)fb * H + Y) * W + X) * C + c0, fv);
 #pragma unroll
             for (int k = 0; k < SEGM_GN_V; ++k) o[k] += fv[k];
         }
@@ -438,43 +455,178 @@ __global__ __launch_bounds__(256) void segm_track_resolve_kernel(const float* __
     }
 }
 
+// ---------------------------------------------------------------------------------
+// Tracker masks of S sequences in one launch: the pixel rule above per segment, plus per slot the
+// pixel count and bounding box of its label.  A workgroup owns RESOLVE_PPB consecutive pixels of ONE
+// segment's map (the segments' tables ride in the kernel arguments, so the host has checked them);
+// the statistics are integers -- count by add, the box as four maxima (x0 and y0 as INT_MAX - x, so
+// that an all-zero table is the neutral element) -- gathered in an LDS table of RESOLVE_LDS_SLOTS
+// slots with LDS atomics and merged into global memory with one atomic per non-empty (slot, field)
+// of the workgroup; slots beyond the table go to global memory directly.  Integer add and max
+// commute: reruns are bit-identical.  segm_resolve_stats_finish turns the two coded minima back.
+// ---------------------------------------------------------------------------------
+constexpr int RESOLVE_SEGS = 32;          // segments per launch (their tables are kernel arguments)
+constexpr int RESOLVE_LDS_SLOTS = 256;    // slots of a segment whose statistics gather in LDS
+constexpr int RESOLVE_PPB = 1024;         // pixels per workgroup (4 per thread)
+constexpr int RESOLVE_CODE = 0x7fffffff;
+
+struct ResolveSeg {
+    long pix_off, prev_off;   // elements into labels / prev (prev_off < 0: no previous map)
+    int src_off, T;           // the segment's slots are src[src_off .. src_off + T)
+    int img_h, img_w, oh, ow;
+    int blk0;                 // its first workgroup
+    float nh, nw;             // nearest scales img / out, as kinet_segm_track_resolve forms them
+};
+struct ResolveSegs {
+    ResolveSeg s[RESOLVE_SEGS];
+};
+
+__global__ __launch_bounds__(256) void segm_track_resolve_segments_kernel(
+    const float* __restrict__ logits, const int32_t* __restrict__ src, const int16_t* __restrict__ prev,
+    int16_t* __restrict__ labels, int32_t* __restrict__ stats, const ResolveSegs segs, int nseg, int n, int h, int w,
+    float bh, float bw, float threshold) {
+    __shared__ int tab[5][RESOLVE_LDS_SLOTS];
+    // the segment of this workgroup: the last one that starts at or before it (a segment without
+    // pixels owns no workgroup and shares its successor's start).  Constant indices: the tables stay
+    // in the argument segment.
+    ResolveSeg g = segs.s[0];
+#pragma unroll
+    for (int k = 1; k < RESOLVE_SEGS; ++k)
+        if (k < nseg && segs.s[k].blk0 <= (int)blockIdx.x) g = segs.s[k];
+    for (int k = threadIdx.x; k < 5 * RESOLVE_LDS_SLOTS; k += 256) (&tab[0][0])[k] = 0;
+    __syncthreads();
+    const long hw = (long)h * w;
+    const long total = (long)g.oh * g.ow;
+    const long base = (long)((int)blockIdx.x - g.blk0) * RESOLVE_PPB;
+    const int32_t* sseg = src + g.src_off;
+    int32_t* gst = stats + (long)g.src_off * 5;
+    for (int k = 0; k < RESOLVE_PPB / 256; ++k) {
+        const long i = base + k * 256 + threadIdx.x;
+        if (i >= total) break;
+        const int ox = (int)(i % g.ow);
+        const int oy = (int)(i / g.ow);
+        const SegmTap tap = segm_tap(oy, ox, h, w, g.img_h, g.img_w, bh, bw, g.nh, g.nw);
+        const int was = g.prev_off >= 0 ? (int)prev[g.prev_off + i] : -1;
+        int best = -1;
+        float pbest = 0.f;
+        for (int t = 0; t < g.T; ++t) {
+            const int s = sseg[t];
+            float p;
+            if (s >= 0) p = s < n ? segm_prob(logits + (long)s * hw, tap) : 0.f;   // (a row outside logits is never read)
+            else p = was == -s - 1 ? 1.f : 0.f;
+            if (best < 0 || (pbest == pbest && (p > pbest || p != p))) {
+                best = t;
+                pbest = p;
+            }
+        }
+        const int lab = pbest > threshold ? best : -1;
+        labels[g.pix_off + i] = (int16_t)lab;
+        if (lab >= 0) {
+            if (lab < RESOLVE_LDS_SLOTS) {
+                atomicAdd(&tab[0][lab], 1);
+                atomicMax(&tab[1][lab], RESOLVE_CODE - ox);
+                atomicMax(&tab[2][lab], RESOLVE_CODE - oy);
+                atomicMax(&tab[3][lab], ox + 1);
+                atomicMax(&tab[4][lab], oy + 1);
+            } else {
+                int32_t* st = gst + (long)lab * 5;
+                atomicAdd(st, 1);
+                atomicMax(st + 1, RESOLVE_CODE - ox);
+                atomicMax(st + 2, RESOLVE_CODE - oy);
+                atomicMax(st + 3, ox + 1);
+                atomicMax(st + 4, oy + 1);
+            }
+        }
+    }
+    __syncthreads();
+    const int nt = min(g.T, RESOLVE_LDS_SLOTS);
+    for (int t = threadIdx.x; t < nt; t += 256) {
+        const int c = tab[0][t];
+        if (c == 0) continue;
+        int32_t* st = gst + (long)t * 5;
+        atomicAdd(st, c);
+#pragma unroll
+        for (int k = 1; k < 5; ++k) atomicMax(st + k, tab[k][t]);
+    }
+}
+
+// (count, INT_MAX - x0, INT_MAX - y0, x1, y1) -> (count, x0, y0, x1, y1); a slot without a pixel is all zero already
+__global__ __launch_bounds__(256) void segm_resolve_stats_finish(int32_t* __restrict__ stats, int total) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= total || stats[(long)t * 5] == 0) return;
+    stats[(long)t * 5 + 1] = RESOLVE_CODE - stats[(long)t * 5 + 1];
+    stats[(long)t * 5 + 2] = RESOLVE_CODE - stats[(long)t * 5 + 2];
+}
+
 }  // namespace
 }  // namespace kinet
 
 using namespace kinet;
 
-extern "C" int kinet_segm_attention(const void* qp, const void* kp, const uint8_t* mask, void* out, int B, int Q,
-                                    int HW, int heads, int d, float scale, int dtype, kinet_stream_t stream) {
+// The launchers below serve the frame-major entry point (row_frame == nullptr: `rows` rows from
+// row0 on, Q per frame) and its ragged twin (row_frame: one device int per row, row0 = 0, Q = 1).
+static int segm_attention_launch(const void* qp, const void* kp, const uint8_t* mask, const int32_t* row_frame,
+                                 void* out, long rows, int B, int Q, int HW, int heads, int d, float scale, int dtype,
+                                 kinet_stream_t stream) {
     KINET_CHECK_ARG(segm_dtype_ok(dtype), "segm_attention: dtype must be f32, bf16 or f16");
-    KINET_CHECK_ARG(B >= 0 && Q >= 0 && HW > 0, "segm_attention: bad geometry");
+    KINET_CHECK_ARG(B >= 0 && Q >= 0 && rows >= 0 && HW > 0, "segm_attention: bad geometry");
     KINET_CHECK_ARG(heads > 0 && heads <= 32 && (heads & (heads - 1)) == 0, "segm_attention: heads must be a power of two <= 32");
     KINET_CHECK_ARG(d > 0 && d <= 1024 && d % heads == 0, "segm_attention: d must be a multiple of heads, <= 1024");
-    KINET_CHECK_ARG((long)B * Q <= 0x7fffffffL, "segm_attention: too many rows");
-    if ((long)B * Q == 0) return KINET_OK;
+    KINET_CHECK_ARG(rows <= 0x7fffffffL, "segm_attention: too many rows");
+    if (rows == 0) return KINET_OK;
     KINET_CHECK_ARG(qp && kp && out, "segm_attention: null pointer");
-    SEGM_DISPATCH(dtype, hipLaunchKernelGGL((segm_attention_kernel<T>), dim3(B * Q), dim3(256), d * sizeof(float),
-                                            (hipStream_t)stream, (const T*)qp, (const T*)kp, mask, (T*)out, Q, HW,
-                                            heads, d, scale));
+    SEGM_DISPATCH(dtype, hipLaunchKernelGGL((segm_attention_kernel<T>), dim3((unsigned)rows), dim3(256),
+                                            d * sizeof(float), (hipStream_t)stream, (const T*)qp, (const T*)kp, mask,
+                                            row_frame, (T*)out, B, Q, HW, heads, d, scale));
     KINET_LAUNCH_CHECK();
     return KINET_OK;
 }
 
-extern "C" int kinet_segm_lay1(const void* att, const float* w_att, const float* frame, void* y, int rows, int row0,
-                               int Q, int B, int H, int W, int Ca, int Cout, int dtype, kinet_stream_t stream) {
+extern "C" int kinet_segm_attention(const void* qp, const void* kp, const uint8_t* mask, void* out, int B, int Q,
+                                    int HW, int heads, int d, float scale, int dtype, kinet_stream_t stream) {
+    return segm_attention_launch(qp, kp, mask, nullptr, out, (long)(B > 0 ? B : 0) * (Q > 0 ? Q : 0), B, Q, HW, heads,
+                                 d, scale, dtype, stream);
+}
+
+extern "C" int kinet_segm_attention_rows(const void* qp, const void* kp, const uint8_t* mask, const int32_t* row_frame,
+                                         void* out, int rows, int B, int HW, int heads, int d, float scale, int dtype,
+                                         kinet_stream_t stream) {
+    KINET_CHECK_ARG(rows >= 0 && B >= 0, "segm_attention_rows: bad geometry");
+    KINET_CHECK_ARG(rows == 0 || B > 0, "segm_attention_rows: rows without a frame");
+    KINET_CHECK_ARG(rows == 0 || row_frame != nullptr, "segm_attention_rows: null pointer (row_frame)");
+    return segm_attention_launch(qp, kp, mask, row_frame, out, rows, B, 1, HW, heads, d, scale, dtype, stream);
+}
+
+static int segm_lay1_launch(const void* att, const float* w_att, const float* frame, const int32_t* row_frame, void* y,
+                            int rows, int row0, int Q, int B, int H, int W, int Ca, int Cout, int dtype,
+                            kinet_stream_t stream) {
     KINET_CHECK_ARG(segm_dtype_ok(dtype), "segm_lay1: dtype must be f32, bf16 or f16");
     KINET_CHECK_ARG(Ca == LAY1_CA, "segm_lay1: 8 attention channels only");
     KINET_CHECK_ARG(Cout > 0 && Cout <= 512, "segm_lay1: Cout must be in 1..512");
     KINET_CHECK_ARG(rows >= 0 && row0 >= 0 && Q > 0 && B > 0 && H > 0 && W > 0, "segm_lay1: bad geometry");
-    KINET_CHECK_ARG((long)row0 + rows <= (long)B * Q, "segm_lay1: rows [row0, row0 + rows) outside the B*Q rows");
+    KINET_CHECK_ARG(row_frame != nullptr || (long)row0 + rows <= (long)B * Q,
+                    "segm_lay1: rows [row0, row0 + rows) outside the B*Q rows");
     KINET_CHECK_ARG(rows <= 65535 && (H + LAY1_TR - 1) / LAY1_TR <= 65535, "segm_lay1: at most 65535 rows per call");
     if (rows == 0) return KINET_OK;
     KINET_CHECK_ARG(att && w_att && frame && y, "segm_lay1: null pointer");
     const dim3 grid((W + LAY1_TW - 1) / LAY1_TW, (H + LAY1_TR - 1) / LAY1_TR, rows);
     const int threads = (Cout + 63) / 64 * 64;
     SEGM_DISPATCH(dtype, hipLaunchKernelGGL((segm_lay1_kernel<T>), grid, dim3(threads), 0, (hipStream_t)stream,
-                                            (const T*)att, w_att, frame, (T*)y, row0, Q, H, W, Cout));
+                                            (const T*)att, w_att, frame, row_frame, (T*)y, row0, Q, B, H, W, Cout));
     KINET_LAUNCH_CHECK();
     return KINET_OK;
+}
+
+extern "C" int kinet_segm_lay1(const void* att, const float* w_att, const float* frame, void* y, int rows, int row0,
+                               int Q, int B, int H, int W, int Ca, int Cout, int dtype, kinet_stream_t stream) {
+    return segm_lay1_launch(att, w_att, frame, nullptr, y, rows, row0, Q, B, H, W, Ca, Cout, dtype, stream);
+}
+
+extern "C" int kinet_segm_lay1_rows(const void* att, const float* w_att, const float* frame, const int32_t* row_frame,
+                                    void* y, int rows, int B, int H, int W, int Ca, int Cout, int dtype,
+                                    kinet_stream_t stream) {
+    KINET_CHECK_ARG(rows <= 0 || row_frame != nullptr, "segm_lay1_rows: null pointer (row_frame)");
+    return segm_lay1_launch(att, w_att, frame, row_frame, y, rows, 0, 1, B, H, W, Ca, Cout, dtype, stream);
 }
 
 extern "C" long kinet_segm_gn_workspace(int rows, int hw, int groups) {
@@ -483,14 +635,15 @@ extern "C" long kinet_segm_gn_workspace(int rows, int hw, int groups) {
     return (long)rows * groups * (3 + 2 * nblk);
 }
 
-extern "C" int kinet_segm_gn_relu_up_add(const void* x, const float* gamma, const float* beta, const void* f, void* y,
-                                         int rows, int row0, int Q, int B, int h, int w, int H, int W, int C,
-                                         int groups, float eps, int dtype, float* ws, kinet_stream_t stream) {
+static int segm_gn_launch(const void* x, const float* gamma, const float* beta, const void* f,
+                          const int32_t* row_frame, void* y, int rows, int row0, int Q, int B, int h, int w, int H, int W,
+                          int C, int groups, float eps, int dtype, float* ws, kinet_stream_t stream) {
     KINET_CHECK_ARG(segm_dtype_ok(dtype), "segm_gn: dtype must be f32, bf16 or f16");
     KINET_CHECK_ARG(rows >= 0 && row0 >= 0 && Q > 0 && B > 0 && h > 0 && w > 0 && H > 0 && W > 0, "segm_gn: bad geometry");
     KINET_CHECK_ARG(C > 0 && C <= 2048 && groups > 0 && groups <= 128 && C % groups == 0 && C % SEGM_GN_V == 0,
                     "segm_gn: C must be a multiple of groups and of 8 (C <= 2048, groups <= 128)");
-    KINET_CHECK_ARG((long)row0 + rows <= (long)B * Q, "segm_gn: rows [row0, row0 + rows) outside the B*Q rows");
+    KINET_CHECK_ARG(row_frame != nullptr || (long)row0 + rows <= (long)B * Q,
+                    "segm_gn: rows [row0, row0 + rows) outside the B*Q rows");
     KINET_CHECK_ARG(f != nullptr || (H == h && W == w), "segm_gn: without an FPN operand the output has the input's size");
     KINET_CHECK_ARG(rows <= 65535, "segm_gn: at most 65535 rows per call");
     KINET_CHECK_ARG((long)h * w <= 0x3fffffffL && (long)H * W * (C / SEGM_GN_V) <= 0x3fffffffL, "segm_gn: map too large");
@@ -515,11 +668,29 @@ extern "C" int kinet_segm_gn_relu_up_add(const void* x, const float* gamma, cons
         hipLaunchKernelGGL(segm_gn_finalize_kernel, dim3(rows), dim3(256), 0, s, (const float*)part, stats, nblk,
                            groups);
         hipLaunchKernelGGL((segm_gn_apply_kernel<T>), dim3(gx, rows), dim3(256), 2 * groups * sizeof(float), s,
-                           (const T*)x, (const float*)stats, (const float*)piv, gamma, beta, (const T*)f, (T*)y, row0,
-                           Q, h, w, H, W, C, groups, eps, sh, sw);
+                           (const T*)x, (const float*)stats, (const float*)piv, gamma, beta, (const T*)f, row_frame,
+                           (T*)y, row0, Q, B, h, w, H, W, C, groups, eps, sh, sw);
     });
     KINET_LAUNCH_CHECK();
     return KINET_OK;
+}
+
+extern "C" int kinet_segm_gn_relu_up_add(const void* x, const float* gamma, const float* beta, const void* f, void* y,
+                                         int rows, int row0, int Q, int B, int h, int w, int H, int W, int C,
+                                         int groups, float eps, int dtype, float* ws, kinet_stream_t stream) {
+    return segm_gn_launch(x, gamma, beta, f, nullptr, y, rows, row0, Q, B, h, w, H, W, C, groups, eps, dtype, ws,
+                          stream);
+}
+
+extern "C" int kinet_segm_gn_relu_up_add_rows(const void* x, const float* gamma, const float* beta, const void* f,
+                                              const int32_t* row_frame, void* y, int rows, int B, int h, int w, int H,
+                                              int W, int C, int groups, float eps, int dtype, float* ws,
+                                              kinet_stream_t stream) {
+    KINET_CHECK_ARG(rows <= 0 || f == nullptr || row_frame != nullptr,
+                    "segm_gn_rows: null pointer (row_frame: an FPN operand needs the rows' frames)");
+    // (without an FPN operand nothing is read per frame: the list is not looked at)
+    return segm_gn_launch(x, gamma, beta, f, f ? row_frame : nullptr, y, rows, 0, f ? 1 : (rows > 0 ? rows : 1),
+                          f ? B : 1, h, w, H, W, C, groups, eps, dtype, ws, stream);
 }
 
 extern "C" int kinet_segm_out_conv(const void* x, const float* wt, const float* bias, float* y, int rows, int H, int W,
@@ -575,6 +746,73 @@ extern "C" int kinet_segm_track_resolve(const float* logits, const int32_t* src,
     const float nh = (float)img_h / (float)oh, nw = (float)img_w / (float)ow;
     hipLaunchKernelGGL(segm_track_resolve_kernel, dim3(segm_grid(total)), dim3(256), 0, (hipStream_t)stream, logits, src,
                        prev_labels, labels, T, n, total, h, w, img_h, img_w, ow, bh, bw, nh, nw, threshold);
+    KINET_LAUNCH_CHECK();
+    return KINET_OK;
+}
+
+extern "C" int kinet_segm_track_resolve_segments(const float* logits, const int32_t* src, const int32_t* src_off,
+                                                 const int32_t* geom, const int64_t* pix_off,
+                                                 const int16_t* prev_labels, const int64_t* prev_off, int16_t* labels,
+                                                 int32_t* stats, int S, int total, int n, int h, int w, int max_h,
+                                                 int max_w, float threshold, kinet_stream_t stream) {
+    KINET_CHECK_ARG(S >= 0 && total >= 0 && n >= 0 && h > 0 && w > 0 && max_h > 0 && max_w > 0,
+                    "segm_track_resolve_segments: bad geometry");
+    if (S == 0) return KINET_OK;
+    KINET_CHECK_ARG(src_off && geom && pix_off && prev_off,
+                    "segm_track_resolve_segments: null pointer (the segments' host tables)");
+    KINET_CHECK_ARG(src_off[0] >= 0 && pix_off[0] >= 0, "segm_track_resolve_segments: negative offset");
+    long blocks = 0, pixels = 0;
+    bool stale_map = false;
+    for (int s = 0; s < S; ++s) {
+        const long T = (long)src_off[s + 1] - src_off[s];
+        KINET_CHECK_ARG(T >= 0 && pix_off[s + 1] >= pix_off[s], "segm_track_resolve_segments: offsets must ascend");
+        KINET_CHECK_ARG(T <= 32767, "segm_track_resolve_segments: at most 32767 track slots per segment (labels are int16)");
+        const int32_t* g = geom + 4L * s;
+        const long px = (long)g[2] * g[3];
+        KINET_CHECK_ARG(g[2] >= 0 && g[3] >= 0 && px <= pix_off[s + 1] - pix_off[s],
+                        "segm_track_resolve_segments: a map of (oh, ow) must fit its range of pix_off");
+        if (px == 0) continue;   // (no map: nothing of this segment is read or written, its stats stay 0)
+        KINET_CHECK_ARG(g[0] > 0 && g[0] <= max_h && g[1] > 0 && g[1] <= max_w,
+                        "segm_track_resolve_segments: a frame's size must lie inside (max_h, max_w)");
+        blocks += (px + RESOLVE_PPB - 1) / RESOLVE_PPB;
+        pixels += px;
+        stale_map = stale_map || prev_off[s] >= 0;
+    }
+    KINET_CHECK_ARG(src_off[S] <= total, "segm_track_resolve_segments: src_off[S] beyond the `total` slots");
+    KINET_CHECK_ARG(blocks <= 0x7fffffffL, "segm_track_resolve_segments: maps too large");
+    if (pixels == 0 && total == 0) return KINET_OK;
+    KINET_CHECK_ARG(pixels == 0 || labels != nullptr, "segm_track_resolve_segments: null pointer (labels)");
+    KINET_CHECK_ARG(total == 0 || (src != nullptr && stats != nullptr), "segm_track_resolve_segments: null pointer (src, stats)");
+    KINET_CHECK_ARG(n == 0 || logits != nullptr, "segm_track_resolve_segments: null pointer (logits)");
+    KINET_CHECK_ARG(!stale_map || prev_labels != nullptr, "segm_track_resolve_segments: null pointer (prev_labels)");
+    KINET_CHECK_ARG(labels == nullptr || labels != prev_labels,
+                    "segm_track_resolve_segments: labels and prev_labels must be two buffers");
+    hipStream_t st = (hipStream_t)stream;
+    if (total > 0) KINET_CHECK_HIP(hipMemsetAsync(stats, 0, (size_t)total * 5 * sizeof(int32_t), st));
+    if (pixels == 0) return KINET_OK;
+    const float bh = (float)h / (float)max_h, bw = (float)w / (float)max_w;
+    for (int s0 = 0; s0 < S; s0 += RESOLVE_SEGS) {
+        ResolveSegs segs = {};
+        const int ns = std::min(RESOLVE_SEGS, S - s0);
+        int blk = 0;
+        for (int k = 0; k < ns; ++k) {
+            const int s = s0 + k;
+            const int32_t* g = geom + 4L * s;
+            ResolveSeg& r = segs.s[k];
+            const long px = (long)g[2] * g[3];
+            r.pix_off = pix_off[s], r.prev_off = prev_off[s];
+            r.src_off = src_off[s], r.T = src_off[s + 1] - src_off[s];
+            r.img_h = g[0], r.img_w = g[1], r.oh = g[2], r.ow = g[3];
+            r.blk0 = blk;
+            r.nh = px ? (float)g[0] / (float)g[2] : 0.f, r.nw = px ? (float)g[1] / (float)g[3] : 0.f;
+            blk += (int)((px + RESOLVE_PPB - 1) / RESOLVE_PPB);
+        }
+        if (blk == 0) continue;
+        hipLaunchKernelGGL(segm_track_resolve_segments_kernel, dim3(blk), dim3(256), 0, st, logits, src, prev_labels,
+                           labels, stats, segs, ns, n, h, w, bh, bw, threshold);
+    }
+    if (total > 0)
+        hipLaunchKernelGGL(segm_resolve_stats_finish, dim3((total + 255) / 256), dim3(256), 0, st, stats, total);
     KINET_LAUNCH_CHECK();
     return KINET_OK;
 }

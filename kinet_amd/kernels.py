@@ -1915,25 +1915,74 @@ def pack_segm_lay1_src(weight, d, dtype):
                   lambda t: t.detach()[:, :d].permute(0, 2, 3, 1).to(dtype).contiguous())
 
 
-def segm_lay1(att, w_att, frame, row0, Q):
+def _row_frame(row_frame, rows, what):
+    """The ragged entry points' frame list: a contiguous device int32 tensor, one entry per row."""
+    N.require_gpu(row_frame)
+    if row_frame.dtype != torch.int32 or row_frame.dim() != 1 or row_frame.numel() != rows \
+            or not row_frame.is_contiguous():
+        raise RuntimeError(f'{what}: row_frame must be a contiguous int32 tensor of one frame per row ({rows}): got '
+                           f'{row_frame.dtype} {tuple(row_frame.shape)}')
+    return row_frame
+
+
+def segm_attention_rows(qp, kp, mask, row_frame, heads, out=None):
+    """segm_attention over gathered rows of several frames (kinet_segm_attention_rows): qp (rows, d), kp
+    (B, HW, d), mask (B, HW) or None, row_frame (rows) device int32 -> (rows, HW, heads); row r attends
+    frame row_frame[r], bit-identical to that row of segm_attention on its frame."""
+    N.require_gpu(qp, kp)
+    B, HW, d = kp.shape
+    qp, kp = qp.contiguous(), kp.contiguous()
+    rows = qp.shape[0]
+    if qp.dim() != 2 or qp.shape[1] != d or kp.dtype != qp.dtype:
+        raise RuntimeError(f'segm_attention_rows: qp {tuple(qp.shape)} {qp.dtype} does not match kp {tuple(kp.shape)} '
+                           f'{kp.dtype}')
+    _row_frame(row_frame, rows, 'segm_attention_rows')
+    m = None
+    if mask is not None:
+        m = mask.reshape(B, HW).contiguous()
+        m = m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
+    if out is None:
+        out = torch.empty((rows, HW, heads), dtype=qp.dtype, device=qp.device)
+    elif out.dtype != qp.dtype or tuple(out.shape) != (rows, HW, heads) or not out.is_contiguous():
+        raise RuntimeError('segm_attention_rows: out must be contiguous (rows, HW, heads) in qp\'s dtype')
+    N.call('kinet_segm_attention_rows', N.ptr(qp), N.ptr(kp), N.ptr(m), N.ptr(row_frame), N.ptr(out), rows, B, HW,
+           heads, d, float(d // heads) ** -0.5 if heads else 0.0, N.dtype_code(qp.dtype), N.stream(qp.device),
+           work={'family': 'segm', 'flops': 4.0 * rows * HW * d})
+    return out
+
+
+def segm_lay1(att, w_att, frame, row0, Q, row_frame=None, out=None):
     """y[r] = frame[(row0 + r) // Q] + conv3x3(att[r]; w_att) (kinet_segm_lay1): att (rows, H, W, 8),
-    w_att (3, 3, 8, Cout) f32, frame (B, H, W, Cout) f32 -> (rows, H, W, Cout) in att's dtype."""
+    w_att (3, 3, 8, Cout) f32, frame (B, H, W, Cout) f32 -> (rows, H, W, Cout) in att's dtype.  With
+    row_frame (rows, device int32) row r reads frame[row_frame[r]] instead (kinet_segm_lay1_rows; row0
+    and Q are not used)."""
     N.require_gpu(att, frame)
     rows, H, W, Ca = att.shape
     B, Cout = frame.shape[0], frame.shape[3]
     if frame.dtype != torch.float32 or tuple(frame.shape[1:3]) != (H, W) or tuple(w_att.shape) != (3, 3, Ca, Cout):
         raise RuntimeError('segm_lay1: frame must be f32 (B, H, W, Cout) and w_att (3, 3, Ca, Cout)')
-    y = torch.empty((rows, H, W, Cout), dtype=att.dtype, device=att.device)
+    if out is None:
+        out = torch.empty((rows, H, W, Cout), dtype=att.dtype, device=att.device)
+    elif out.dtype != att.dtype or tuple(out.shape) != (rows, H, W, Cout) or not out.is_contiguous():
+        raise RuntimeError('segm_lay1: out must be contiguous (rows, H, W, Cout) in att\'s dtype')
+    y = out
+    work = {'family': 'segm', 'flops': 2.0 * rows * H * W * Cout * 9 * Ca, 'bytes': y.numel() * y.element_size()}
+    if row_frame is not None:
+        _row_frame(row_frame, rows, 'segm_lay1')
+        N.call('kinet_segm_lay1_rows', N.ptr(att.contiguous()), N.ptr(w_att), N.ptr(frame.contiguous()),
+               N.ptr(row_frame), N.ptr(y), rows, B, H, W, Ca, Cout, N.dtype_code(att.dtype), N.stream(att.device),
+               work=work)
+        return y
     N.call('kinet_segm_lay1', N.ptr(att.contiguous()), N.ptr(w_att), N.ptr(frame.contiguous()), N.ptr(y), rows, row0,
-           Q, B, H, W, Ca, Cout, N.dtype_code(att.dtype), N.stream(att.device),
-           work={'family': 'segm', 'flops': 2.0 * rows * H * W * Cout * 9 * Ca,
-                 'bytes': y.numel() * y.element_size()})
+           Q, B, H, W, Ca, Cout, N.dtype_code(att.dtype), N.stream(att.device), work=work)
     return y
 
 
-def segm_gn_relu(x, weight, bias, groups, eps=1e-5, fpn=None, row0=0, Q=None):
+def segm_gn_relu(x, weight, bias, groups, eps=1e-5, fpn=None, row0=0, Q=None, row_frame=None, out=None):
     """relu(GroupNorm(x)) per row, optionally nearest-upsampled to fpn's size and added to
-    fpn[(row0 + r) // Q] (kinet_segm_gn_relu_up_add): x (rows, h, w, C), fpn (B, H, W, C) or None."""
+    fpn[(row0 + r) // Q] (kinet_segm_gn_relu_up_add): x (rows, h, w, C), fpn (B, H, W, C) or None.  With
+    row_frame (rows, device int32) and an fpn, row r adds fpn[row_frame[r]] instead
+    (kinet_segm_gn_relu_up_add_rows); without an fpn the list is not used."""
     N.require_gpu(x)
     rows, h, w, C = x.shape
     x = x.contiguous()
@@ -1943,13 +1992,24 @@ def segm_gn_relu(x, weight, bias, groups, eps=1e-5, fpn=None, row0=0, Q=None):
         fpn = fpn.contiguous()
         B, H, W = fpn.shape[:3]
     else:
-        B, H, W, Q = 1, h, w, None      # no per-frame operand: the rows are one "frame"
+        B, H, W, Q, row_frame = 1, h, w, None, None      # no per-frame operand: the rows are one "frame"
     Qn = int(Q) if Q is not None else max(rows + row0, 1)
-    y = torch.empty((rows, H, W, C), dtype=x.dtype, device=x.device)
+    if out is None:
+        out = torch.empty((rows, H, W, C), dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or tuple(out.shape) != (rows, H, W, C) or not out.is_contiguous():
+        raise RuntimeError('segm_gn_relu: out must be contiguous (rows, H, W, C) in x\'s dtype')
+    y = out
     ws = torch.empty(max(1, N.lib().kinet_segm_gn_workspace(rows, h * w, groups)), dtype=torch.float32, device=x.device)
+    work = {'family': 'segm', 'bytes': (2 * x.numel() + y.numel()) * x.element_size()}
+    if row_frame is not None:
+        _row_frame(row_frame, rows, 'segm_gn_relu')
+        N.call('kinet_segm_gn_relu_up_add_rows', N.ptr(x), N.ptr(f32(weight)), N.ptr(f32(bias)), N.ptr(fpn),
+               N.ptr(row_frame), N.ptr(y), rows, B, h, w, H, W, C, groups, float(eps), N.dtype_code(x.dtype), N.ptr(ws),
+               N.stream(x.device), work=work)
+        return y
     N.call('kinet_segm_gn_relu_up_add', N.ptr(x), N.ptr(f32(weight)), N.ptr(f32(bias)), N.ptr(fpn), N.ptr(y), rows,
            row0, Qn, B, h, w, H, W, C, groups, float(eps), N.dtype_code(x.dtype), N.ptr(ws), N.stream(x.device),
-           work={'family': 'segm', 'bytes': (2 * x.numel() + y.numel()) * x.element_size()})
+           work=work)
     return y
 
 
@@ -2022,6 +2082,88 @@ def segm_track_resolve(logits, src, prev_labels, max_hw, img_hw, out_hw, thresho
            T, n, h, w, int(max_hw[0]), int(max_hw[1]), int(img_hw[0]), int(img_hw[1]), oh, ow, float(threshold),
            N.stream(logits.device), work={'family': 'segm', 'bytes': out.numel() * 4})
     return out
+
+
+RESOLVE_STAT_BYTES = 20     # (count, x0, y0, x1, y1) int32 per slot of kinet_segm_track_resolve_segments
+
+
+def segm_resolve_views(buf, total, pixels):
+    """(stats (total, 5) int32, labels (pixels,) int16) of a packed kinet_segm_track_resolve_segments buffer
+    (a uint8 torch tensor or numpy array: stats first, then the sequences' label maps)."""
+    nb = RESOLVE_STAT_BYTES * total
+    if isinstance(buf, torch.Tensor):
+        return buf[:nb].view(torch.int32).view(total, 5), buf[nb:nb + 2 * pixels].view(torch.int16)
+    import numpy as np
+    return buf[:nb].view(np.int32).reshape(total, 5), buf[nb:nb + 2 * pixels].view(np.int16)
+
+
+def segm_track_resolve_segments(logits, src, src_off, geom, prev_labels, prev_off, max_hw, threshold=0.5, out=None):
+    """The tracker's overlap resolution for S sequences in one launch (kinet_segm_track_resolve_segments).
+    logits (n, h, w) f32: the kept rows of all sequences; src: DEVICE int32 (total), sequence s's slots
+    src[src_off[s]:src_off[s + 1]] (>= 0: a row of logits, < 0: slot -e-1 of its previous map); src_off a HOST
+    sequence of S + 1 ints; geom a HOST (S, 4) of (img_h, img_w, oh, ow), oh*ow == 0 for a sequence without a
+    map; prev_labels: the previous call's labels view (device int16) or None; prev_off a HOST sequence of S
+    element offsets into it, < 0 (or None) for no previous map.
+    -> (buf, stats, labels, pix_off): buf one uint8 allocation (stats | labels, a multiple of 4 bytes: one
+    copy carries both), stats (total, 5) int32 = (count, x0, y0, x1, y1) per slot, labels int16 (pixels,) with
+    sequence s's (oh, ow) map at pix_off[s]:pix_off[s + 1] holding LOCAL slot indices or -1.  `out`: a uint8
+    device buffer to reuse when it is large enough (it must not hold prev_labels)."""
+    import numpy as np
+    N.require_gpu(logits, src, prev_labels, out)
+    logits = logits.float().contiguous()
+    n, h, w = logits.shape
+    src_off = np.ascontiguousarray(np.asarray(src_off, np.int64).reshape(-1))
+    S = src_off.size - 1
+    geom = np.ascontiguousarray(np.asarray(geom, np.int64).reshape(-1, 4))
+    if S < 0 or geom.shape[0] != S:
+        raise RuntimeError('segm_track_resolve_segments: src_off (S + 1) and geom (S, 4)')
+    if S and (src_off[0] != 0 or (np.diff(src_off) < 0).any()):
+        raise RuntimeError('segm_track_resolve_segments: src_off must start at 0 and ascend')
+    if S and (np.diff(src_off) > 32767).any():
+        raise RuntimeError('segm_track_resolve_segments: a segment holds at most 32767 slots (labels are int16)')
+    total = int(src_off[-1]) if S else 0
+    if (geom < 0).any() or (geom > 0x7fffffff).any():
+        raise RuntimeError('segm_track_resolve_segments: geom out of range')
+    px = geom[:, 2] * geom[:, 3]
+    live = px > 0
+    if (live & ((geom[:, 0] < 1) | (geom[:, 0] > int(max_hw[0])) | (geom[:, 1] < 1) | (geom[:, 1] > int(max_hw[1])))).any():
+        raise RuntimeError('segm_track_resolve_segments: a frame\'s size must lie inside max_hw')
+    if total:
+        if src is None or src.dtype != torch.int32 or src.numel() != total or not src.is_contiguous():
+            raise RuntimeError(f'segm_track_resolve_segments: src must be a contiguous device int32 tensor of {total} slots')
+    pix_off = np.zeros(S + 1, np.int64)
+    pix_off[1:] = np.cumsum(px)
+    pixels = int(pix_off[-1])
+    poff = np.full(S, -1, np.int64) if prev_off is None else np.ascontiguousarray(np.asarray(prev_off, np.int64).reshape(-1))
+    if poff.size != S:
+        raise RuntimeError('segm_track_resolve_segments: prev_off holds one offset per sequence')
+    poff = np.where(live, poff, -1)
+    if (poff >= 0).any():
+        if prev_labels is None or prev_labels.dtype != torch.int16 or not prev_labels.is_contiguous():
+            raise RuntimeError('segm_track_resolve_segments: a previous map needs prev_labels, contiguous int16')
+        if (poff + px > prev_labels.numel())[poff >= 0].any():
+            raise RuntimeError('segm_track_resolve_segments: a previous map reaches beyond prev_labels')
+    nbytes = (RESOLVE_STAT_BYTES * total + 2 * pixels + 3) // 4 * 4
+    if out is None or out.numel() < nbytes:
+        out = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=logits.device)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.data_ptr() % 4:
+        raise RuntimeError('segm_track_resolve_segments: out must be a contiguous, 4-byte aligned uint8 buffer')
+    buf = out[:nbytes]
+    stats, labels = segm_resolve_views(buf, total, pixels)
+    if not total and not pixels:
+        return buf, stats, labels, pix_off
+    if prev_labels is not None and pixels:
+        lo, hi = labels.data_ptr(), labels.data_ptr() + 2 * pixels
+        plo, phi = prev_labels.data_ptr(), prev_labels.data_ptr() + 2 * prev_labels.numel()
+        if lo < phi and plo < hi:
+            raise RuntimeError('segm_track_resolve_segments: out and prev_labels must be two buffers')
+    so, ge = src_off.astype(np.int32), geom.astype(np.int32)
+    N.call('kinet_segm_track_resolve_segments', N.ptr(logits) if n else None, N.ptr(src) if total else None,
+           so.ctypes.data, ge.ctypes.data, pix_off.ctypes.data, N.ptr(prev_labels) if (poff >= 0).any() else None,
+           poff.ctypes.data, N.ptr(labels) if pixels else None, N.ptr(stats) if total else None, S, total, n, h, w,
+           int(max_hw[0]), int(max_hw[1]), float(threshold), N.stream(logits.device),
+           work={'family': 'segm', 'bytes': pixels * 4 + total * RESOLVE_STAT_BYTES})
+    return buf, stats, labels, pix_off
 
 
 # ------------------------------------------------------------------- mask training

@@ -20,7 +20,9 @@ kernel choice depends on the chunk (split-K is off), so pred_masks does not depe
 
 `defer_masks` (the tracker's MOTS path): forward returns `out` without 'pred_masks' and keeps the
 head's operands until the next forward; `mask_logits(rows, frame)` then runs the attention map and
-the head on the chosen query rows only, bit-identical to those rows of the full head.
+the head on the chosen query rows only, bit-identical to those rows of the full head;
+`mask_logits_rows(rows, frames)` does so for rows of several frames in ONE pass (the multi-sequence
+tracker's path): the kernels that read a per-frame operand take the rows' frames as a device list.
 
 Mask training (opt-in: `mask_training = True`, set by kinet_amd.train.build_mask_training; a model
 from build_model raises under autograd as before).  Off the fast path the detector runs
@@ -142,21 +144,23 @@ class MaskHeadSmallConv(nn.Module):
         return K.conv2d_nhwc(x, K.pack_conv_weight(conv.weight, x.dtype), 1, 1, bias=K.f32(conv.bias), ksplit=1)
 
     @staticmethod
-    def _gn(x, gn, fpn=None, row0=0, Q=None):
-        return K.segm_gn_relu(x, gn.weight, gn.bias, gn.num_groups, gn.eps, fpn=fpn, row0=row0, Q=Q)
+    def _gn(x, gn, fpn=None, row0=0, Q=None, row_frame=None):
+        return K.segm_gn_relu(x, gn.weight, gn.bias, gn.num_groups, gn.eps, fpn=fpn, row0=row0, Q=Q,
+                              row_frame=row_frame)
 
-    def rows(self, att, frame, fpn_adapted, row0, Q, out):
-        """The head for rows [row0, row0 + n) of the B*Q rows: att (n, h, w, heads) -> out (n, H, W) f32."""
+    def rows(self, att, frame, fpn_adapted, row0, Q, out, row_frame=None):
+        """The head for rows [row0, row0 + n) of the B*Q rows: att (n, h, w, heads) -> out (n, H, W) f32.
+        With row_frame (n, device int32) the rows are a ragged list and row r reads frame row_frame[r]."""
         d = self.dim - att.shape[3]
-        x = K.segm_lay1(att, K.segm_lay1_weights(self.lay1.weight, d), frame, row0, Q)
+        x = K.segm_lay1(att, K.segm_lay1_weights(self.lay1.weight, d), frame, row0, Q, row_frame=row_frame)
         x = self._gn(x, self.gn1)
         x = self._conv(x, self.lay2)
         # the first "interpolate" (:156) maps stride 16 onto stride 16: the identity of the same entry point
-        x = self._gn(x, self.gn2, fpn_adapted[0], row0, Q)
+        x = self._gn(x, self.gn2, fpn_adapted[0], row0, Q, row_frame)
         x = self._conv(x, self.lay3)
-        x = self._gn(x, self.gn3, fpn_adapted[1], row0, Q)
+        x = self._gn(x, self.gn3, fpn_adapted[1], row0, Q, row_frame)
         x = self._conv(x, self.lay4)
-        x = self._gn(x, self.gn4, fpn_adapted[2], row0, Q)
+        x = self._gn(x, self.gn4, fpn_adapted[2], row0, Q, row_frame)
         x = self._conv(x, self.lay5)
         x = self._gn(x, self.gn5)
         return K.segm_out_conv(x, K.segm_out_weights(self.out_lay.weight), K.f32(self.out_lay.bias), out=out)
@@ -200,8 +204,10 @@ class MaskHeadSmallConv(nn.Module):
                                       'torch.no_grad())')
         return self.run(att, self.frame_part(src), self.adapters(fpns), Q, chunk)
 
-    def run(self, att, frame, adapted, Q, chunk=None):
-        """The head over all rows of att in chunks, on per-frame operands that are already computed."""
+    def run(self, att, frame, adapted, Q, chunk=None, row_frame=None):
+        """The head over all rows of att in chunks, on per-frame operands that are already computed.
+        row_frame (rows, device int32): the rows' frames when they are a ragged list (Q is then not used);
+        a chunk takes its slice of the list."""
         R = att.shape[0]
         H, W = adapted[2].shape[1:3]
         out = torch.empty((R, H, W), dtype=torch.float32, device=att.device)
@@ -214,7 +220,8 @@ class MaskHeadSmallConv(nn.Module):
         chunk = max(1, min(int(chunk), 65535))
         for r0 in range(0, R, chunk):
             r1 = min(R, r0 + chunk)
-            self.rows(att[r0:r1], frame, adapted, r0, Q, out[r0:r1])
+            self.rows(att[r0:r1], frame, adapted, r0, Q, out[r0:r1],
+                      None if row_frame is None else row_frame[r0:r1])
         return out
 
 
@@ -425,6 +432,48 @@ class DETRSegmBase(nn.Module):
         att = att.view(n, h, w, -1)
         return self.mask_head.run(att, ctx['frame'][b:b + 1], [a[b:b + 1] for a in ctx['adapted']], n,
                                   self.mask_query_chunk)
+
+    def _mask_operands(self, ctx):
+        """The per-frame operands of the deferred head, computed once per forward (mask_logits' statements)."""
+        if 'qp' not in ctx:
+            hs = ctx['hs']
+            B, Q, d = hs.shape
+            att_mod = self.bbox_attention
+            ctx['qp'] = K.linear(hs.reshape(B * Q, d), att_mod.q_linear.weight, att_mod.q_linear.bias)
+            ctx['kp'] = K.linear(ctx['k_rows'].reshape(-1, d), att_mod.k_linear.weight,
+                                 att_mod.k_linear.bias).view(B, -1, att_mod.hidden_dim)
+            ctx['frame'] = self.mask_head.frame_part(ctx['src'])
+            ctx['adapted'] = self.mask_head.adapters(ctx['fpns'])
+        return ctx
+
+    @torch.no_grad()
+    def mask_logits_rows(self, rows, frames):
+        """pred_masks[frames[i], rows[i]] of the last forward run with defer_masks, for rows of ANY frames in
+        one pass of the head: rows a device int64 tensor of query rows, frames a device int32 tensor of the
+        same length (each in [0, B); a row whose frame is outside is left unwritten by the kernels) ->
+        (len(rows), H/4, W/4) f32.  Bit-identical to mask_logits(rows[frames == b], b) for every b: the
+        per-frame operands are mask_logits' (shared with it), q_linear's rows are gathered at
+        frames * Q + rows, and the attention map and the head run once over all rows through the ragged
+        entry points (kinet_segm_*_rows), whose kernels are the frame-major ones."""
+        ctx = self._mask_ctx
+        if ctx is None:
+            raise RuntimeError('mask_logits_rows needs a forward with defer_masks set (and none since without it)')
+        hs = ctx['hs']
+        B, Q, d = hs.shape
+        if rows.dtype != torch.int64 or rows.dim() != 1:
+            raise RuntimeError('mask_logits_rows: rows must be a 1-d int64 tensor')
+        if frames.dtype != torch.int32 or frames.dim() != 1 or frames.numel() != rows.numel():
+            raise RuntimeError('mask_logits_rows: frames must be a 1-d int32 tensor, one frame per row')
+        n = rows.numel()
+        if n == 0:      # (no launch)
+            return torch.empty((0,) + tuple(ctx['fpns'][2].shape[1:3]), dtype=torch.float32, device=hs.device)
+        self._mask_operands(ctx)
+        h, w = ctx['hw']
+        frames = frames.to(hs.device).contiguous()
+        qp = ctx['qp'].index_select(0, frames.to(torch.int64) * Q + rows.to(hs.device))
+        att = K.segm_attention_rows(qp, ctx['kp'], ctx['mask'], frames, self.bbox_attention.num_heads)
+        att = att.view(n, h, w, -1)
+        return self.mask_head.run(att, ctx['frame'], ctx['adapted'], 1, self.mask_query_chunk, row_frame=frames)
 
 
 class DeformableDETRSegm(DETRSegmBase, DeformableDETR):

@@ -31,6 +31,7 @@ probabilities: its slot is "stale" and names its slot in the previous label map 
 ping-pong).  results[id][frame]['mask'] is a numpy bool (oh, ow), as in the reference.
 """
 import math
+import time
 from collections import deque
 
 import numpy as np
@@ -823,16 +824,47 @@ def plan_track_queries(n_active, n_inactive, num_queries):
     return {'K': k.astype(np.int32), 'Kmax': kmax, 'offsets': offsets, 'mask': mask}
 
 
+def plan_mask_resolve(tracks, out_hws):
+    """The host plan of one frame's mask resolution (Tracker._resolve_masks for every sequence at once):
+    tracks[b] the tracks of sequence b alive at the end of the frame, in slot order (objects with id,
+    mask_row -- the GLOBAL frame row b * Nrows + row of this frame's detector output, or None --, mask_slot
+    and mask_size), out_hws[b] its (oh, ow) ->
+    {'rows': the distinct frame rows whose mask logits are needed, in order of first use (a row named by
+     two tracks -- of one sequence or of two -- is computed once), 'src': (total,) int32, >= 0 an index into
+     'rows', < 0 the stale slot -e-1 of the sequence's previous map, 'src_off': (S + 1,) int32}.
+    Raises Tracker's two RuntimeErrors: a stale track whose kept map has another size, and a track with
+    neither a row of this frame nor a kept mask."""
+    rows, src = {}, []
+    src_off = np.zeros(len(tracks) + 1, np.int32)
+    for b, (seq, out_hw) in enumerate(zip(tracks, out_hws)):
+        for track in seq:
+            if track.mask_row is not None:
+                src.append(rows.setdefault(int(track.mask_row), len(rows)))
+            elif track.mask_slot is not None:
+                if tuple(track.mask_size) != tuple(out_hw):
+                    raise RuntimeError(f'track {track.id} keeps a mask of size {track.mask_size}, the frame is '
+                                       f'{tuple(out_hw)} (the reference\'s torch.stack fails there too)')
+                src.append(-int(track.mask_slot) - 1)
+            else:
+                raise RuntimeError(f'track {track.id} has neither a mask row of this frame nor a kept mask')
+        src_off[b + 1] = len(src)
+    return {'rows': list(rows), 'src': np.asarray(src, np.int32), 'src_off': src_off}
+
+
 class _SlotTrack:
     """One track of a MultiTracker sequence: Track's bookkeeping fields with host mirrors (numpy f32) of
     the box and the score; the embedding and the device copies are row `slot` of the track bank.  (Track's
-    last_pos history feeds nothing the tracker outputs and is not kept.)"""
-    __slots__ = ('id', 'pos', 'score', 'slot', 'obj_ind', 'count_inactive', 'count_termination')
+    last_pos history feeds nothing the tracker outputs and is not kept.)  Masks: mask_row is the global
+    frame row b * Nrows + row this frame's mask comes from, mask_slot the track's slot in its sequence's
+    previous label map, mask_size that map's (oh, ow) (Track's fields)."""
+    __slots__ = ('id', 'pos', 'score', 'slot', 'obj_ind', 'count_inactive', 'count_termination', 'mask_row',
+                 'mask_slot', 'mask_size')
 
     def __init__(self, pos, score, track_id, slot, obj_ind):
         self.id, self.pos, self.score, self.slot, self.obj_ind = track_id, pos, score, slot, obj_ind
         self.count_inactive = 0
         self.count_termination = 0
+        self.mask_row = self.mask_slot = self.mask_size = None
 
 
 class _Sequence:
@@ -841,6 +873,7 @@ class _Sequence:
         self.tracks, self.inactive_tracks = [], []
         self.track_num = self.frame_index = self.num_reids = 0
         self.results = {}
+        self.map_off = None     # masks: element offset of the sequence's map in the previous packed label buffer
 
 
 class MultiTracker:
@@ -849,7 +882,14 @@ class MultiTracker:
     dict per sequence.  Track ids, track_num, num_reids and frame_index are per sequence
     (`sequence(i)`).  Every device -> host transfer of step goes through `_to_host`, which counts
     them in `sync_count`: at most four per step (decisions, track NMS, re-identification distances,
-    detection NMS), each skipped when no sequence needs it, whatever S is."""
+    detection NMS), each skipped when no sequence needs it, whatever S is.
+    Masks (tracker_cfg['masks'] with the 'segm' postprocessor; blob['size'] is then required): after the
+    detection NMS the mask head runs ONCE on the surviving tracks' rows of all sequences
+    (DETRSegmBase.mask_logits_rows; the detector runs with defer_masks), ONE
+    kinet_segm_track_resolve_segments launch writes every sequence's int16 label map and each slot's pixel
+    count and box into one packed buffer, and a fifth transfer carries it: results[id][frame]['mask'] is
+    a numpy bool (oh, ow) built inside the slot's box only.  Two packed buffers ping-pong (a stale track
+    names its slot in its sequence's previous map)."""
 
     def __init__(self, obj_detector, obj_detector_post, tracker_cfg, num_sequences, logger=None,
                  generate_attention_maps=False):
@@ -858,10 +898,13 @@ class MultiTracker:
         if generate_attention_maps or tracker_cfg.get('generate_attention_maps', False):
             raise NotImplementedError('attention maps (tracker.py:38-40) need the decoder\'s attention '
                                       'probabilities, which the fused attention kernels do not export')
-        if tracker_cfg.get('masks', False):
-            raise NotImplementedError('MultiTracker does not carry segmentation masks (MOTS): use Tracker')
-        if 'segm' in obj_detector_post:
-            raise NotImplementedError('MultiTracker takes the \'bbox\' postprocessor alone (no \'segm\')')
+        self.masks = bool(tracker_cfg.get('masks', False))
+        if self.masks and 'segm' not in obj_detector_post:
+            raise NotImplementedError('MultiTracker carries segmentation masks (MOTS) only with the \'segm\' '
+                                      'postprocessor of a masks model')
+        if 'segm' in obj_detector_post and not self.masks:
+            raise NotImplementedError('MultiTracker takes the \'segm\' postprocessor only with '
+                                      'tracker_cfg[\'masks\'] = True')
         if type(obj_detector_post.get('bbox')) is not DeformablePostProcess:
             raise NotImplementedError('MultiTracker runs DeformablePostProcess on the device '
                                       '(kinet_track_decide); other postprocessors are not built')
@@ -903,6 +946,9 @@ class MultiTracker:
         self._free_slots, self._next_slot = [], 0
         self._pending = ([], [])     # (frame rows, bank slots) to commit with the next launch
         self._sizes_key, self._sizes = None, None
+        self._mask_bufs, self._mask_cur = [None, None], 0   # masks: the packed stats + labels buffers (ping-pong)
+        self._prev_labels = None                            # masks: the labels view of the last resolve
+        self.mask_seconds = 0.0                             # masks: host time spent building the bool masks
         self.sync_count = 0
 
     def sequence(self, i):
@@ -926,6 +972,7 @@ class MultiTracker:
             self._free(t.slot)
         q.tracks, q.inactive_tracks = [], []
         q.retired = True
+        q.map_off = None
         self._sizes_key = None
         for features in self._prev_features:
             if features is None:
@@ -1027,6 +1074,57 @@ class MultiTracker:
                 self._free(t.slot)
             q.tracks = [t for t in q.tracks if t not in remove]
 
+    # ------------------------------------------------------------------ masks
+    def _resolve_masks(self, seqs, outputs, Nrows, out_hws, net_hws):
+        """Tracker._resolve_masks for every sequence at once (tracker.py:515-527): slot t of sequence b's
+        label map is seqs[b].tracks[t].  One pass of the head over the distinct fresh rows of all
+        sequences, one segmented resolve launch, one transfer of the packed statistics + label maps ->
+        per sequence the tracks' bool (oh, ow) masks, each built inside its slot's box.  0.5 is the
+        reference's constant (:522).  Nothing is launched or copied when no sequence has a track."""
+        plan = plan_mask_resolve([q.tracks for q in seqs], out_hws)
+        total = int(plan['src_off'][-1])
+        if not total:
+            for q in seqs:
+                q.map_off = None
+            return [[] for _ in seqs]
+        idx = torch.from_numpy(np.asarray(plan['rows'], np.int64)).to(self.device)
+        if hasattr(self.obj_detector, 'mask_logits_rows'):
+            logits = self.obj_detector.mask_logits_rows(idx % Nrows, (idx // Nrows).to(torch.int32))
+        else:
+            logits = outputs['pred_masks'].flatten(0, 1).index_select(0, idx)
+        # PostProcessSegm's rule: the bilinear target is the element-wise maximum of the batch's sizes
+        max_hw = (max(s[0] for s in net_hws), max(s[1] for s in net_hws))
+        geom = [net_hws[b] + out_hws[b] if q.tracks else (0, 0, 0, 0) for b, q in enumerate(seqs)]
+        # (a sequence reads its previous map only when one of its slots is stale: the plan has checked its size)
+        so = plan['src_off']
+        prev_off = [q.map_off if q.map_off is not None and (plan['src'][so[b]:so[b + 1]] < 0).any() else -1
+                    for b, q in enumerate(seqs)]
+        src_d, = self._upload(plan['src'])
+        cur = self._mask_cur
+        buf, _, labels_d, pix_off = K.segm_track_resolve_segments(
+            logits, src_d, plan['src_off'], geom, self._prev_labels, prev_off, max_hw, 0.5, out=self._mask_bufs[cur])
+        if self._mask_bufs[cur] is None or self._mask_bufs[cur].numel() < buf.numel():
+            self._mask_bufs[cur] = buf
+        self._mask_cur, self._prev_labels = 1 - cur, labels_d
+        stats, labels = K.segm_resolve_views(self._to_host(buf), total, int(pix_off[-1]))
+        t0 = time.perf_counter()
+        out = []
+        for b, q in enumerate(seqs):
+            oh, ow = out_hws[b]
+            q.map_off = int(pix_off[b]) if q.tracks else None
+            lab = labels[pix_off[b]:pix_off[b + 1]].reshape(oh, ow) if q.tracks else None
+            per = []
+            for slot, track in enumerate(q.tracks):
+                track.mask_row, track.mask_slot, track.mask_size = None, slot, (oh, ow)
+                n, x0, y0, x1, y1 = (int(v) for v in stats[plan['src_off'][b] + slot])
+                m = np.zeros((oh, ow), np.bool_)
+                if n:
+                    m[y0:y1, x0:x1] = lab[y0:y1, x0:x1] == slot
+                per.append(m)
+            out.append(per)
+        self.mask_seconds += time.perf_counter() - t0
+        return out
+
     # ------------------------------------------------------------------ one frame of every live sequence
     @torch.no_grad()
     def step(self, blobs):
@@ -1039,6 +1137,9 @@ class MultiTracker:
             return
         seqs = [self._seqs[i] for i in live]
         B, Q, dev = len(seqs), self.num_object_queries, self.device
+        if self.masks and any('size' not in b for b in blobs):
+            raise ValueError('tracker masks need blob[\'size\'], the (1, 2) network-input frame size '
+                             '(max_target_sizes of PostProcessSegm, tracker.py:322)')
         for q in seqs:
             self._prune_inactive(q)
             self._logger(f'FRAME: {q.frame_index + 1}')
@@ -1060,7 +1161,15 @@ class MultiTracker:
             embeds, qboxes, mask = K.track_gather(self._bank, slots_d, off_d, sizes, Kmax, Q)
             targets = [{'track_query_boxes': qboxes[b], 'track_query_hs_embeds': embeds[b],
                         'track_queries_placeholder_mask': mask[b]} for b in range(B)]
-        outputs, _, features, _, _ = self.obj_detector(samples, targets, self._prev_features[0])
+        defer = self.masks and hasattr(self.obj_detector, 'mask_logits_rows')
+        if defer:
+            # the head runs after the bookkeeping, on the surviving tracks' rows only
+            was_deferred, self.obj_detector.defer_masks = self.obj_detector.defer_masks, True
+        try:
+            outputs, _, features, _, _ = self.obj_detector(samples, targets, self._prev_features[0])
+        finally:
+            if defer:
+                self.obj_detector.defer_masks = was_deferred
         hs = outputs['hs_embed'].float().contiguous()
         logits = outputs['pred_logits'].float().contiguous()
         if tuple(logits.shape[:2]) != (B, Nrows):
@@ -1075,7 +1184,23 @@ class MultiTracker:
         boxes_d, scores_d, _, _ = K.track_decide_views(packed, B, Nrows)
         frame = {'hs': hs.view(B * Nrows, d), 'boxes': boxes_d.view(B * Nrows, 4), 'scores': scores_d.view(B * Nrows)}
         # every box, score and threshold decision of this frame, all sequences, in ONE copy
-        boxes, scores, _, dec = K.track_decide_views(self._to_host(packed), B, Nrows)
+        out_hws = net_hws = None
+        if self.masks:
+            # the frames' two sizes as host ints; where they live on the device they ride in the same copy
+            size_t = [t.reshape(-1)[:2] for blob in blobs for t in (blob['orig_size'], blob['size'])]
+            if any(t.is_cuda for t in size_t):
+                extra = torch.cat([t.to(dev, torch.int32) for t in size_t]).view(torch.uint8)
+                host = self._to_host(torch.cat([packed, extra]))
+                hw = np.frombuffer(host[packed.numel():].tobytes(), np.int32).reshape(B, 2, 2)
+                host = host[:packed.numel()]
+            else:
+                host = self._to_host(packed)
+                hw = np.asarray([[int(v) for v in t.tolist()] for t in size_t], np.int32).reshape(B, 2, 2)
+            out_hws = [(int(hw[b, 0, 0]), int(hw[b, 0, 1])) for b in range(B)]
+            net_hws = [(int(hw[b, 1, 0]), int(hw[b, 1, 1])) for b in range(B)]
+        else:
+            host = self._to_host(packed)
+        boxes, scores, _, dec = K.track_decide_views(host, B, Nrows)
         person = (dec & K.TRACK_DEC_PERSON) != 0
 
         def update(b, row, track):
@@ -1083,6 +1208,8 @@ class MultiTracker:
             next launch."""
             track.score = scores[b, row]
             track.pos = boxes[b, row].copy()
+            if self.masks:
+                track.mask_row = b * Nrows + row
             self._pending[0].append(b * Nrows + row)
             self._pending[1].append(track.slot)
 
@@ -1205,11 +1332,15 @@ class MultiTracker:
                     self._remove_tracks(q, keep, 'detection_nms_thresh', self.detection_nms_thresh)
         self._flush(frame)                                   # (commits no launch of this frame carried)
 
+        masks = self._resolve_masks(seqs, outputs, Nrows, out_hws, net_hws) if self.masks else None
+
         # results (tracker.py:529-552) from the host mirrors: decide already clipped them to the image
-        for q in seqs:
-            for track in q.tracks:
+        for b, q in enumerate(seqs):
+            for slot, track in enumerate(q.tracks):
                 q.results.setdefault(track.id, {})[q.frame_index] = {
                     'bbox': track.pos.copy(), 'score': np.float32(track.score), 'obj_ind': int(track.obj_ind)}
+                if masks is not None:
+                    q.results[track.id][q.frame_index]['mask'] = masks[b][slot]
             for t in q.inactive_tracks:
                 t.count_inactive += 1
             q.frame_index += 1
