@@ -9,6 +9,7 @@
 #include "../../include/kinet_ops.h"
 #include "attn_plan.h"
 #include "common.h"
+#include "nms_rule.h"
 
 namespace kinet {
 namespace {
@@ -1036,26 +1037,18 @@ namespace kinet {
 namespace {
 constexpr int NMS_MAX = 4096;
 
-// one workgroup: rank every box by score (descending, ties by index -- a stable order; NaN
-// scores rank first), then
-// walk the ranks; each kept box suppresses, in parallel, every later box with IoU > thresh
+// one workgroup: rank every box by score (descending, ties by index -- a stable order; NaN scores rank
+// first), then walk the ranks; each kept box suppresses, in parallel, every later box with IoU > thresh
 __global__ __launch_bounds__(1024) void nms_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
                                                    uint8_t* __restrict__ keep, int n, float thresh) {
     __shared__ int order[NMS_MAX];
     __shared__ uint8_t supp[NMS_MAX];
     __shared__ int cur;
-    // scores compared as monotone integer keys: a strict total order even with NaNs (which
-    // rank first, as torch.sort(descending=True) places them), so every rank is written once
-    auto key = [](float f) -> uint32_t {
-        const uint32_t u = __float_as_uint(f);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-        return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    };
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const uint32_t si = key(scores[i]);
+        const uint32_t si = nms_score_key(scores[i]);
         int r = 0;
         for (int j = 0; j < n; ++j) {
-            const uint32_t sj = key(scores[j]);
+            const uint32_t sj = nms_score_key(scores[j]);
             r += (sj > si || (sj == si && j < i)) ? 1 : 0;
         }
         order[r] = i;
@@ -1073,12 +1066,7 @@ __global__ __launch_bounds__(1024) void nms_kernel(const float* __restrict__ box
             const float ai = (x2 - x1) * (y2 - y1);
             for (int k = r + 1 + threadIdx.x; k < n; k += blockDim.x) {
                 const int j = order[k];
-                const float* b = boxes + 4 * j;
-                const float w = fmaxf(fminf(x2, b[2]) - fmaxf(x1, b[0]), 0.f);
-                const float h = fmaxf(fminf(y2, b[3]) - fmaxf(y1, b[1]), 0.f);
-                const float inter = w * h;
-                const float iou = inter / (ai + (b[2] - b[0]) * (b[3] - b[1]) - inter);
-                if (iou > thresh) supp[j] = 1;
+                if (nms_suppresses(x1, y1, x2, y2, ai, boxes + 4 * j, thresh)) supp[j] = 1;
             }
         }
         __syncthreads();

@@ -402,6 +402,30 @@ __device__ __forceinline__ float segm_prob(const float* __restrict__ p, const Se
     return 1.f / (1.f + expf(-v));
 }
 
+// The tracker's pixel rule, shared by the two resolve kernels below so that they agree bit for bit: slot
+// t of src[0 .. T) is fresh (src[t] >= 0: the probability of row src[t] of the n rows of logits) or stale
+// (src[t] < 0: 1.0 where the previous label `was` is slot -src[t]-1, else 0.0); the label is torch's
+// argmax over the slots (first occurrence of the maximum, NaN the greatest) where that maximum exceeds
+// the threshold, else -1.  src is read with wave-uniform addresses.
+__device__ __forceinline__ int segm_resolve_label(const float* __restrict__ logits, const SegmTap& tap, int was,
+                                                  const int32_t* __restrict__ src, int T, int n, long hw,
+                                                  float threshold) {
+    int best = -1;
+    float pbest = 0.f;
+    for (int t = 0; t < T; ++t) {
+        const int s = src[t];
+        float p;
+        if (s >= 0) p = s < n ? segm_prob(logits + (long)s * hw, tap) : 0.f;   // (a row outside logits is never read)
+        else p = was == -s - 1 ? 1.f : 0.f;
+        // argmax: a NaN is taken once and then kept; otherwise strictly greater replaces
+        if (best < 0 || (pbest == pbest && (p > pbest || p != p))) {
+            best = t;
+            pbest = p;
+        }
+    }
+    return pbest > threshold ? best : -1;
+}
+
 template <bool PROBS>
 __global__ __launch_bounds__(256) void segm_postprocess_kernel(const float* __restrict__ logits, void* __restrict__ out,
                                                                long total, int h, int w, int img_h, int img_w, int oh,
@@ -420,11 +444,8 @@ __global__ __launch_bounds__(256) void segm_postprocess_kernel(const float* __re
 }
 
 // ---------------------------------------------------------------------------------
-// Tracker masks: one thread per output pixel resolves the T track slots into one label.  Slot t is
-// fresh (src[t] >= 0: the probability of row src[t] of logits) or stale (src[t] < 0: 1.0 where the
-// previous label map holds slot -src[t]-1, else 0.0); the label is torch's argmax over the slots
-// (first occurrence of the maximum, NaN the greatest) where that maximum exceeds the threshold.
-// The taps are formed once per pixel; src is read with wave-uniform addresses.
+// Tracker masks: one thread per output pixel resolves the T track slots into one label
+// (segm_resolve_label).  The taps are formed once per pixel.
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void segm_track_resolve_kernel(const float* __restrict__ logits,
                                                                  const int32_t* __restrict__ src,
@@ -438,20 +459,7 @@ __global__ __launch_bounds__(256) void segm_track_resolve_kernel(const float* __
         const int oy = (int)(i / ow);
         const SegmTap tap = segm_tap(oy, ox, h, w, img_h, img_w, bh, bw, nh, nw);
         const int was = prev ? (int)prev[i] : -1;
-        int best = -1;
-        float pbest = 0.f;
-        for (int t = 0; t < T; ++t) {
-            const int s = src[t];
-            float p;
-            if (s >= 0) p = s < n ? segm_prob(logits + (long)s * hw, tap) : 0.f;   // (a row outside logits is never read)
-            else p = was == -s - 1 ? 1.f : 0.f;
-            // argmax: a NaN is taken once and then kept; otherwise strictly greater replaces
-            if (best < 0 || (pbest == pbest && (p > pbest || p != p))) {
-                best = t;
-                pbest = p;
-            }
-        }
-        labels[i] = pbest > threshold ? (int16_t)best : (int16_t)-1;
+        labels[i] = (int16_t)segm_resolve_label(logits, tap, was, src, T, n, hw, threshold);
     }
 }
 
@@ -507,19 +515,7 @@ __global__ __launch_bounds__(256) void segm_track_resolve_segments_kernel(
         const int oy = (int)(i / g.ow);
         const SegmTap tap = segm_tap(oy, ox, h, w, g.img_h, g.img_w, bh, bw, g.nh, g.nw);
         const int was = g.prev_off >= 0 ? (int)prev[g.prev_off + i] : -1;
-        int best = -1;
-        float pbest = 0.f;
-        for (int t = 0; t < g.T; ++t) {
-            const int s = sseg[t];
-            float p;
-            if (s >= 0) p = s < n ? segm_prob(logits + (long)s * hw, tap) : 0.f;   // (a row outside logits is never read)
-            else p = was == -s - 1 ? 1.f : 0.f;
-            if (best < 0 || (pbest == pbest && (p > pbest || p != p))) {
-                best = t;
-                pbest = p;
-            }
-        }
-        const int lab = pbest > threshold ? best : -1;
+        const int lab = segm_resolve_label(logits, tap, was, sseg, g.T, n, hw, threshold);
         labels[g.pix_off + i] = (int16_t)lab;
         if (lab >= 0) {
             if (lab < RESOLVE_LDS_SLOTS) {

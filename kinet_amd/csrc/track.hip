@@ -3,6 +3,7 @@
 // distances, each one launch for all sequences.  f32 throughout, no atomics: every output element
 // has one writer and a fixed summation order, so reruns are bit-identical.
 #include "common.h"
+#include "nms_rule.h"
 #include "../../include/kinet_track.h"
 
 namespace kinet {
@@ -74,18 +75,13 @@ __global__ __launch_bounds__(1024) void nms_segments_kernel(
     const int beg = offsets[blockIdx.x], end = offsets[blockIdx.x + 1];
     const int n = end - beg;
     if (beg < 0 || end > total || n <= 0 || n > TRACK_MAX) return;   // (uniform over the workgroup)
-    // scores as monotone integer keys: a strict total order with NaNs first (ops.hip nms_kernel)
-    auto key = [](float f) -> uint32_t {
-        const uint32_t u = __float_as_uint(f);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-        return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    };
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         const int r = idx[beg + i];
         const bool ok = r >= 0 && r < bank_rows;
         row[i] = ok ? r : -1;
         // an entry outside the bank ranks last and is never kept
-        keys[i] = !ok ? 0u : (inf_flag && inf_flag[beg + i]) ? key(INFINITY) : key(scores[(long)r * score_stride]);
+        keys[i] = !ok ? 0u : (inf_flag && inf_flag[beg + i]) ? nms_score_key(INFINITY)
+                                                             : nms_score_key(scores[(long)r * score_stride]);
         supp[i] = ok ? 0 : 1;
         keep[beg + i] = 0;
     }
@@ -112,12 +108,7 @@ __global__ __launch_bounds__(1024) void nms_segments_kernel(
             for (int k = r + 1 + threadIdx.x; k < n; k += blockDim.x) {
                 const int j = order[k];
                 if (row[j] < 0) continue;
-                const float* b = boxes + (long)row[j] * box_stride;
-                const float w = fmaxf(fminf(x2, b[2]) - fmaxf(x1, b[0]), 0.f);
-                const float h = fmaxf(fminf(y2, b[3]) - fmaxf(y1, b[1]), 0.f);
-                const float inter = w * h;
-                const float iou = inter / (ai + (b[2] - b[0]) * (b[3] - b[1]) - inter);
-                if (iou > thresh) supp[j] = 1;
+                if (nms_suppresses(x1, y1, x2, y2, ai, boxes + (long)row[j] * box_stride, thresh)) supp[j] = 1;
             }
         }
         __syncthreads();

@@ -30,6 +30,8 @@ RESOLVED mask in the reference, which torch.stack promotes to 1.0 / 0.0 among th
 probabilities: its slot is "stale" and names its slot in the previous label map (two maps,
 ping-pong).  results[id][frame]['mask'] is a numpy bool (oh, ow), as in the reference.
 """
+import contextlib
+import functools
 import math
 import time
 from collections import deque
@@ -121,6 +123,132 @@ def reid_match_lsa(dist_mat):
     return linear_sum_assignment(dist_mat)
 
 
+@contextlib.contextmanager
+def deferred_masks(detector, on):
+    """Run the detector with `defer_masks` set (the mask head then runs after the bookkeeping, on the
+    surviving tracks' rows only) and restore the switch; nothing is touched when `on` is false."""
+    if not on:
+        yield
+        return
+    was_deferred, detector.defer_masks = detector.defer_masks, True
+    try:
+        yield
+    finally:
+        detector.defer_masks = was_deferred
+
+
+def copy_with_sizes(payload, size_tensors, to_host):
+    """A frame's decisions (`payload`, a flat uint8 device tensor) and its frame sizes (tensors whose first
+    two elements are (h, w)) through ONE `to_host(tensor) -> numpy` transfer: sizes that live on the device
+    ride behind the payload as int32 bytes, host sizes are read where they are -> (the payload's host copy,
+    (len(size_tensors), 2) int32 sizes)."""
+    size_t = [t.reshape(-1)[:2] for t in size_tensors]
+    if any(t.is_cuda for t in size_t):
+        extra = torch.cat([t.to(payload.device, torch.int32) for t in size_t]).view(torch.uint8)
+        host = to_host(torch.cat([payload, extra]))
+        return host[:payload.numel()], np.frombuffer(host[payload.numel():].tobytes(), np.int32).reshape(-1, 2)
+    return to_host(payload), np.asarray([[int(v) for v in t.tolist()] for t in size_t], np.int32).reshape(-1, 2)
+
+
+class _TrackRules:
+    """The reference's per-frame track rules, each once, for Tracker, TrackerKinematic and MultiTracker.
+    The tracker (`self`) holds the thresholds and the logger; `state` is the object with one sequence's
+    `tracks`, `inactive_tracks`, `track_num`, `num_reids`, `frame_index` and `results`: the tracker itself
+    for the single-sequence classes, the _Sequence for MultiTracker.  Where the trackers differ (what a
+    track takes from a row, how tracks go inactive, what a removed track releases) the caller passes the
+    action in."""
+
+    def _read_cfg(self, tracker_cfg, generate_attention_maps):
+        """The thresholds of cfgs/track.yaml:28-49; attention maps are refused."""
+        if generate_attention_maps:
+            raise NotImplementedError('attention maps (tracker.py:38-40) need the decoder\'s attention '
+                                      'probabilities, which the fused attention kernels do not export')
+        self.detection_obj_score_thresh = tracker_cfg['detection_obj_score_thresh']
+        self.track_obj_score_thresh = tracker_cfg['track_obj_score_thresh']
+        self.detection_nms_thresh = tracker_cfg['detection_nms_thresh']
+        self.track_nms_thresh = tracker_cfg['track_nms_thresh']
+        self.public_detections = tracker_cfg['public_detections']
+        self.inactive_patience = float(tracker_cfg['inactive_patience'])
+        self.reid_sim_threshold = tracker_cfg['reid_sim_threshold']
+        self.reid_sim_only = tracker_cfg['reid_sim_only']
+        self.reid_score_thresh = tracker_cfg['reid_score_thresh']
+        self.reid_greedy_matching = tracker_cfg['reid_greedy_matching']
+        self.prev_frame_dist = tracker_cfg['prev_frame_dist']
+        self.steps_termination = tracker_cfg['steps_termination']
+
+    def _score_phase(self, state, track_keep, reid_keep, take, go_inactive):
+        """tracker.py:351-432: an active track whose row i passes `track_keep` takes it (`take(i, track)`),
+        one that fails steps_termination times in a row goes inactive (`go_inactive(tracks)`); an inactive
+        track whose row passes `reid_keep` takes it and is active again (a re-identification by score)."""
+        to_inactive, from_inactive = [], []
+        for i, track in enumerate(state.tracks):
+            if track_keep[i]:
+                take(i, track)
+                track.count_termination = 0
+            else:
+                track.count_termination += 1
+                if track.count_termination >= self.steps_termination:
+                    to_inactive.append(track)
+        for i, track in enumerate(state.inactive_tracks, start=len(state.tracks)):
+            if reid_keep[i]:
+                take(i, track)
+                from_inactive.append(track)
+        if to_inactive:
+            self._logger(f'NEW INACTIVE TRACK IDS (track_obj_score_thresh={self.track_obj_score_thresh}): '
+                         f'{[t.id for t in to_inactive]}')
+        state.num_reids += len(from_inactive)
+        for track in from_inactive:
+            state.inactive_tracks.remove(track)
+            state.tracks.append(track)
+        go_inactive(to_inactive)
+
+    def _drop_suppressed(self, state, keep, what, release=None):
+        """tracker.py:437-447 / :511-527: drop the tracks NMS suppressed; keep[i] tells whether
+        state.tracks[i] survived, `what` names the threshold, `release(track)` frees what a dropped track
+        held."""
+        remove = [t for t, k in zip(state.tracks, keep) if not k]
+        if remove:
+            self._logger(f'REMOVE TRACK IDS ({what}={getattr(self, what)}): {[t.id for t in remove]}')
+            if release is not None:
+                for t in remove:
+                    release(t)
+            state.tracks = [t for t in state.tracks if t not in remove]
+
+    def _assign_reid(self, state, dist_mat, rows, cols, take):
+        """tracker.py:246-265: every matched (inactive track r, detection c) within reid_sim_threshold is
+        active again and takes its detection (`take(c, track)`) -> the detections assigned."""
+        assigned, remove_inactive = [], []
+        for r, c in zip(rows, cols):
+            if dist_mat[r, c] <= self.reid_sim_threshold:
+                track = state.inactive_tracks[r]
+                self._logger(f'REID: track.id={track.id} - count_inactive={track.count_inactive} - '
+                             f'to_inactive_frame={state.frame_index - track.count_inactive}')
+                track.count_inactive = 0
+                take(int(c), track)
+                assigned.append(int(c))
+                remove_inactive.append(track)
+                state.tracks.append(track)
+                state.num_reids += 1
+        for track in remove_inactive:
+            state.inactive_tracks.remove(track)
+        return assigned
+
+    def _count_new_tracks(self, state, new_track_ids):
+        state.track_num += len(new_track_ids)
+        if new_track_ids:
+            self._logger(f'INIT TRACK IDS (detection_obj_score_thresh={self.detection_obj_score_thresh}): '
+                         f'{new_track_ids}')
+
+    @staticmethod
+    def _end_frame(state, sim_only_move=None):
+        """tracker.py:553-557; `sim_only_move` (reid_sim_only) sends every active track inactive."""
+        for t in state.inactive_tracks:
+            t.count_inactive += 1
+        state.frame_index += 1
+        if sim_only_move is not None:
+            sim_only_move(state.tracks)
+
+
 class Track:
     """tracker.py:1056-1130."""
 
@@ -161,14 +289,12 @@ class Track:
         self.last_pos.append(self.pos.clone())
 
 
-class Tracker:
+class Tracker(_TrackRules):
     """tracker.py:18-562 (image detector path)."""
 
     def __init__(self, obj_detector, obj_detector_post, tracker_cfg, generate_attention_maps=False, logger=None,
                  verbose=False):
-        if generate_attention_maps:
-            raise NotImplementedError('attention maps (tracker.py:38-40) need the decoder\'s attention '
-                                      'probabilities, which the fused attention kernels do not export')
+        self._read_cfg(tracker_cfg, generate_attention_maps)
         self.masks = bool(tracker_cfg.get('masks', False))
         if 'segm' in obj_detector_post and not self.masks:
             # opt-in: the reference's own three-argument detector call (tracker.py:309) is a TypeError
@@ -179,19 +305,7 @@ class Tracker:
             raise ValueError('tracker_cfg[\'masks\'] needs the \'segm\' postprocessor of a masks model')
         self.obj_detector = obj_detector
         self.obj_detector_post = obj_detector_post
-        self.detection_obj_score_thresh = tracker_cfg['detection_obj_score_thresh']
-        self.track_obj_score_thresh = tracker_cfg['track_obj_score_thresh']
-        self.detection_nms_thresh = tracker_cfg['detection_nms_thresh']
-        self.track_nms_thresh = tracker_cfg['track_nms_thresh']
-        self.public_detections = tracker_cfg['public_detections']
-        self.inactive_patience = float(tracker_cfg['inactive_patience'])
-        self.reid_sim_threshold = tracker_cfg['reid_sim_threshold']
-        self.reid_sim_only = tracker_cfg['reid_sim_only']
         self.generate_attention_maps = False
-        self.reid_score_thresh = tracker_cfg['reid_score_thresh']
-        self.reid_greedy_matching = tracker_cfg['reid_greedy_matching']
-        self.prev_frame_dist = tracker_cfg['prev_frame_dist']
-        self.steps_termination = tracker_cfg['steps_termination']
         # compatibility switch for a reference defect (Track.reset_last_pos): False = keep the
         # relative-position history on re-identification (default), True = clear it as the
         # reference does (its next repeat_last_pos then raises IndexError)
@@ -245,10 +359,7 @@ class Tracker:
             if rows is not None:
                 self.tracks[-1].mask_row = rows[i]
             new_track_ids.append(self.track_num + i)
-        self.track_num += len(new_track_ids)
-        if new_track_ids:
-            self._logger(f'INIT TRACK IDS (detection_obj_score_thresh={self.detection_obj_score_thresh}): '
-                         f'{new_track_ids}')
+        self._count_new_tracks(self, new_track_ids)
         return new_track_ids
 
     def public_detections_mask(self, new_det_boxes, public_det_boxes):
@@ -278,27 +389,16 @@ class Tracker:
             sims = torch.stack([t.hs_embed[-1] for t in self.inactive_tracks])
             dist_mat = (sims[:, None, :] - new_det_hs_embeds[None, :, :] + 1e-6).norm(dim=-1).cpu().numpy()
             rows, cols = reid_match_lsa(dist_mat)
-        assigned, remove_inactive = [], []
-        for r, c in zip(rows, cols):
-            if dist_mat[r, c] <= self.reid_sim_threshold:
-                track = self.inactive_tracks[r]
-                self._logger(f'REID: track.id={track.id} - count_inactive={track.count_inactive} - '
-                             f'to_inactive_frame={self.frame_index - track.count_inactive}')
-                track.count_inactive = 0
-                track.pos = new_det_boxes[c]
-                track.score = new_det_scores[c]
-                track.hs_embed.append(new_det_hs_embeds[c])
-                track.reset_last_pos(self.reference_clear_last_pos_relative)
-                if new_det_rows is not None:
-                    track.mask_row = new_det_rows[int(c)]
-                assigned.append(int(c))
-                remove_inactive.append(track)
-                self.tracks.append(track)
-                self.num_reids += 1
-        for track in remove_inactive:
-            self.inactive_tracks.remove(track)
+
+        def take(c, track):
+            track.pos = new_det_boxes[c]
+            track.score = new_det_scores[c]
+            track.hs_embed.append(new_det_hs_embeds[c])
+            track.reset_last_pos(self.reference_clear_last_pos_relative)
+            if new_det_rows is not None:
+                track.mask_row = new_det_rows[c]
         mask = torch.ones(n, dtype=torch.bool)
-        for c in assigned:
+        for c in self._assign_reid(self, dist_mat, rows, cols, take):
             mask[c] = False
         return mask
 
@@ -328,15 +428,8 @@ class Tracker:
                        'image_id': torch.tensor([1], device=self.device),
                        'track_query_hs_embeds': torch.stack([t.hs_embed[-1] for t in prev])}]
 
-        defer = self.masks and hasattr(self.obj_detector, 'mask_logits')
-        if defer:
-            # the head runs after the bookkeeping, on the surviving tracks' rows only
-            was_deferred, self.obj_detector.defer_masks = self.obj_detector.defer_masks, True
-        try:
+        with deferred_masks(self.obj_detector, self.masks and hasattr(self.obj_detector, 'mask_logits')):
             outputs, _, features, _, _ = self.obj_detector(img, target, self._prev_features[0])
-        finally:
-            if defer:
-                self.obj_detector.defer_masks = was_deferred
         hs_embeds = outputs['hs_embed'][0]
         result = self.obj_detector_post['bbox'](outputs, orig_size)[0]
         boxes = result['boxes'] if self.obj_detector.overflow_boxes else clip_boxes_to_image(result['boxes'],
@@ -347,14 +440,10 @@ class Tracker:
         dec = torch.stack([scores > self.track_obj_score_thresh, scores > self.reid_score_thresh,
                            scores > self.detection_obj_score_thresh, person])
         if self.masks:
-            # the two frame sizes ride in the same copy when they live on the device
-            sizes = [blob['orig_size'].reshape(-1)[:2], blob['size'].reshape(-1)[:2]]
-            if any(t.is_cuda for t in sizes):
-                packed = torch.cat([dec.flatten().to(torch.int32)] + [t.to(self.device, torch.int32) for t in sizes]).cpu()
-                dec, sizes = packed[:-4].view(dec.shape).bool(), [packed[-4:-2], packed[-2:]]
-            else:
-                dec = dec.cpu()
-            out_hw, net_hw = (tuple(int(v) for v in t.tolist()) for t in sizes)
+            host, hw = copy_with_sizes(dec.flatten().view(torch.uint8), [blob['orig_size'], blob['size']],
+                                       lambda t: t.cpu().numpy())
+            dec = torch.from_numpy(host).view(dec.shape).bool()
+            out_hw, net_hw = (tuple(int(v) for v in s) for s in hw)
         else:
             dec = dec.cpu()
 
@@ -362,41 +451,15 @@ class Tracker:
             nt = num_prev_track
             track_keep = (dec[0, :nt] & dec[3, :nt]).tolist()
             reid_keep = (dec[1, :nt] & dec[3, :nt]).tolist()
-            to_inactive, from_inactive = [], []
-            for i, track in enumerate(self.tracks):
-                if track_keep[i]:
-                    track.score = scores[i]
-                    track.hs_embed.append(hs_embeds[i])
-                    track.pos = boxes[i]
-                    track.count_termination = 0
-                    track.mask_row = i
-                else:
-                    track.count_termination += 1
-                    if track.count_termination >= self.steps_termination:
-                        to_inactive.append(track)
-            for i, track in enumerate(self.inactive_tracks, start=len(self.tracks)):
-                if reid_keep[i]:
-                    track.score = scores[i]
-                    track.hs_embed.append(hs_embeds[i])
-                    track.pos = boxes[i]
-                    track.mask_row = i
-                    from_inactive.append(track)
-            if to_inactive:
-                self._logger(f'NEW INACTIVE TRACK IDS (track_obj_score_thresh={self.track_obj_score_thresh}): '
-                             f'{[t.id for t in to_inactive]}')
-            self.num_reids += len(from_inactive)
-            for track in from_inactive:
-                self.inactive_tracks.remove(track)
-                self.tracks.append(track)
-            self.move_tracks_to_inactive(to_inactive)
+
+            def take(i, track):
+                track.score = scores[i]
+                track.hs_embed.append(hs_embeds[i])
+                track.pos = boxes[i]
+                track.mask_row = i
+            self._score_phase(self, track_keep, reid_keep, take, self.move_tracks_to_inactive)
             if self.track_nms_thresh and self.tracks:
-                keep = set(K.nms(torch.stack([t.pos for t in self.tracks]),
-                                 torch.stack([t.score for t in self.tracks]), self.track_nms_thresh).tolist())
-                remove = [t for i, t in enumerate(self.tracks) if i not in keep]
-                if remove:
-                    self._logger(f'REMOVE TRACK IDS (track_nms_thresh={self.track_nms_thresh}): '
-                                 f'{[t.id for t in remove]}')
-                self.tracks = [t for t in self.tracks if t not in remove]
+                self._drop_suppressed(self, self._nms_keep(self.track_nms_thresh), 'track_nms_thresh')
 
         # new detections (tracker.py:456-505)
         det_keep = (dec[2, -Q:] & dec[3, -Q:]).nonzero().flatten()
@@ -421,25 +484,11 @@ class Tracker:
         new_track_ids = self.add_tracks(new_det_boxes, new_det_scores, new_det_hs_embeds, new_det_indices, det_rows)
 
         if self.detection_nms_thresh and self.tracks:
-            t_boxes = torch.stack([t.pos for t in self.tracks])
-            t_scores = torch.stack([t.score for t in self.tracks]).clone()
-            new_ids = set(new_track_ids)
-            old = torch.tensor([t.id not in new_ids for t in self.tracks], device=self.device)
-            t_scores[old] = float('inf')                       # existing tracks always win (:519)
-            keep = set(K.nms(t_boxes, t_scores, self.detection_nms_thresh).tolist())
-            remove = [t for i, t in enumerate(self.tracks) if i not in keep]
-            if remove:
-                self._logger(f'REMOVE TRACK IDS (detection_nms_thresh={self.detection_nms_thresh}): '
-                             f'{[t.id for t in remove]}')
-            self.tracks = [t for t in self.tracks if t not in remove]
+            self._drop_suppressed(self, self._nms_keep(self.detection_nms_thresh, new_track_ids), 'detection_nms_thresh')
 
         # results (tracker.py:529-552), one batched copy
         if self.tracks:
-            pos = torch.stack([t.pos for t in self.tracks])
-            if not self.obj_detector.overflow_boxes:
-                pos = clip_boxes_to_image(pos, orig_size[0])
-            packed = torch.cat([pos.float(), torch.stack([t.score for t in self.tracks]).float()[:, None],
-                                torch.stack([t.obj_ind.reshape(()) for t in self.tracks]).float()[:, None]], 1)
+            packed = self._result_rows(orig_size)
             if self.masks:
                 # the label map rides in the same copy, as bytes behind the packed rows
                 labels = self._resolve_masks(outputs, out_hw, net_hw)
@@ -450,17 +499,36 @@ class Tracker:
                 labels = both[nb:].view(np.int16).reshape(out_hw)
             else:
                 packed = packed.cpu().numpy()
-            for slot, (track, row) in enumerate(zip(self.tracks, packed)):
-                self.results.setdefault(track.id, {})[self.frame_index] = {
-                    'bbox': row[:4].copy(), 'score': np.float32(row[4]), 'obj_ind': int(row[5])}
-                if self.masks:
+            self._write_results(packed)
+            if self.masks:
+                for slot, track in enumerate(self.tracks):
                     self.results[track.id][self.frame_index]['mask'] = labels == slot
-        for t in self.inactive_tracks:
-            t.count_inactive += 1
-        self.frame_index += 1
         self._prev_features.append(features)
-        if self.reid_sim_only:
-            self.move_tracks_to_inactive(self.tracks)
+        self._end_frame(self, self.move_tracks_to_inactive if self.reid_sim_only else None)
+
+    def _nms_keep(self, thresh, new_track_ids=None):
+        """K.nms over the active tracks -> one keep flag per track.  With `new_track_ids` (the detection
+        NMS, tracker.py:511-521) every other track's score is lifted to inf: existing tracks always win."""
+        scores = torch.stack([t.score for t in self.tracks])
+        if new_track_ids is not None:
+            new_ids = set(new_track_ids)
+            scores[torch.tensor([t.id not in new_ids for t in self.tracks], device=self.device)] = float('inf')
+        keep = set(K.nms(torch.stack([t.pos for t in self.tracks]), scores, thresh).tolist())
+        return [i in keep for i in range(len(self.tracks))]
+
+    def _result_rows(self, orig_size):
+        """(tracks, 6) f32 on the device: the clipped box, the score and obj_ind of every active track."""
+        pos = torch.stack([t.pos for t in self.tracks])
+        if not self.obj_detector.overflow_boxes:
+            pos = clip_boxes_to_image(pos, orig_size[0])
+        return torch.cat([pos.float(), torch.stack([t.score for t in self.tracks]).float()[:, None],
+                          torch.stack([t.obj_ind.reshape(()) for t in self.tracks]).float()[:, None]], 1)
+
+    def _write_results(self, packed):
+        """tracker.py:529-552 from the host copy of `_result_rows`."""
+        for track, row in zip(self.tracks, packed):
+            self.results.setdefault(track.id, {})[self.frame_index] = {
+                'bbox': row[:4].copy(), 'score': np.float32(row[4]), 'obj_ind': int(row[5])}
 
     def _resolve_masks(self, outputs, out_hw, net_hw):
         """tracker.py:515-527 for the tracks alive at the end of the frame: slot t of the label map
@@ -468,18 +536,9 @@ class Tracker:
         being re-detected names its slot in the previous frame's map.  The head runs once, on the
         fresh rows; 0.5 is the reference's constant (:522), not the post-processor's threshold."""
         prev = self._label_maps[1 - self._label_cur]
-        rows, src = {}, []
-        for track in self.tracks:
-            if track.mask_row is not None:
-                src.append(rows.setdefault(track.mask_row, len(rows)))
-            elif track.mask_slot is not None:
-                if track.mask_size != out_hw:
-                    raise RuntimeError(f'track {track.id} keeps a mask of size {track.mask_size}, the frame is '
-                                       f'{out_hw} (the reference\'s torch.stack fails there too)')
-                src.append(-track.mask_slot - 1)
-            else:
-                raise RuntimeError(f'track {track.id} has neither a mask row of this frame nor a kept mask')
-        idx = torch.tensor(list(rows), dtype=torch.int64, device=self.device)
+        plan = plan_mask_resolve([self.tracks], [out_hw])
+        src = plan['src'].tolist()
+        idx = torch.tensor(plan['rows'], dtype=torch.int64, device=self.device)
         if hasattr(self.obj_detector, 'mask_logits'):
             logits = self.obj_detector.mask_logits(idx, 0)
         else:
@@ -681,10 +740,7 @@ class TrackerKinematic(Tracker):
                 metadata_encoded=self.encoder_tracklets_metada(metadata_trail[i, :, :self.dim_metadata]).flatten(0),
                 track_id=self.track_num + i, obj_ind=indices[i]))
             new_track_ids.append(self.track_num + i)
-        self.track_num += len(new_track_ids)
-        if new_track_ids:
-            self._logger(f'INIT TRACK IDS (detection_obj_score_thresh={self.detection_obj_score_thresh}): '
-                         f'{new_track_ids}')
+        self._count_new_tracks(self, new_track_ids)
         return new_track_ids
 
     @torch.no_grad()
@@ -726,35 +782,12 @@ class TrackerKinematic(Tracker):
             reid_keep = (dec[1, :nt] & dec[3, :nt]).tolist()
             track_boxes, track_rel = boxes[:nt], pred_boxes[:nt]
             track_meta = torch.stack([scores[:nt], cls[:nt].to(scores.dtype)], dim=1)
-            to_inactive, from_inactive = [], []
-            for i, track in enumerate(self.tracks):                        # manage_active_tracks (:933-955)
-                if track_keep[i]:
-                    self._update(track, track_boxes[i], track_rel[i], track_meta[i])
-                    track.count_termination = 0
-                else:
-                    track.count_termination += 1
-                    if track.count_termination >= self.steps_termination:
-                        to_inactive.append(track)
-            for i, track in enumerate(self.inactive_tracks, start=len(self.tracks)):   # (:922-931)
-                if reid_keep[i]:
-                    self._update(track, track_boxes[i], track_rel[i], track_meta[i])
-                    from_inactive.append(track)
-            if to_inactive:
-                self._logger(f'NEW INACTIVE TRACK IDS (track_obj_score_thresh={self.track_obj_score_thresh}): '
-                             f'{[t.id for t in to_inactive]}')
-            self.num_reids += len(from_inactive)
-            for track in from_inactive:
-                self.inactive_tracks.remove(track)
-                self.tracks.append(track)
-            self.move_tracks_to_inactive(to_inactive)
+            # manage_active_tracks (:933-955), manage_inactive_tracks (:922-931)
+            self._score_phase(self, track_keep, reid_keep,
+                              lambda i, track: self._update(track, track_boxes[i], track_rel[i], track_meta[i]),
+                              self.move_tracks_to_inactive)
             if self.track_nms_thresh and self.tracks:
-                keep = set(K.nms(torch.stack([t.pos for t in self.tracks]),
-                                 torch.stack([t.score for t in self.tracks]), self.track_nms_thresh).tolist())
-                remove = [t for i, t in enumerate(self.tracks) if i not in keep]
-                if remove:
-                    self._logger(f'REMOVE TRACK IDS (track_nms_thresh={self.track_nms_thresh}): '
-                                 f'{[t.id for t in remove]}')
-                self.tracks = [t for t in self.tracks if t not in remove]
+                self._drop_suppressed(self, self._nms_keep(self.track_nms_thresh), 'track_nms_thresh')
 
         # new detections (generate_new_tracks, :892-920)
         keep = (dec[2, nt:] & dec[4, nt:]).nonzero().flatten().to(dev)
@@ -770,31 +803,11 @@ class TrackerKinematic(Tracker):
         new_track_ids = self.add_tracks(new_boxes, new_rel, new_meta, new_tracklets, new_indices, nt)
 
         if self.detection_nms_thresh and self.tracks:                # (:790-808)
-            t_boxes = torch.stack([t.pos for t in self.tracks])
-            t_scores = torch.stack([t.score for t in self.tracks]).clone()
-            new_ids = set(new_track_ids)
-            old = torch.tensor([t.id not in new_ids for t in self.tracks], device=dev)
-            t_scores[old] = float('inf')
-            keep_n = set(K.nms(t_boxes, t_scores, self.detection_nms_thresh).tolist())
-            remove = [t for i, t in enumerate(self.tracks) if i not in keep_n]
-            if remove:
-                self._logger(f'REMOVE TRACK IDS (detection_nms_thresh={self.detection_nms_thresh}): '
-                             f'{[t.id for t in remove]}')
-            self.tracks = [t for t in self.tracks if t not in remove]
+            self._drop_suppressed(self, self._nms_keep(self.detection_nms_thresh, new_track_ids), 'detection_nms_thresh')
 
         if self.tracks:                                               # results (:828-841), one copy
-            pos = torch.stack([t.pos for t in self.tracks])
-            if not self.obj_detector.overflow_boxes:
-                pos = clip_boxes_to_image(pos, orig_size[0])
-            packed = torch.cat([pos.float(), torch.stack([t.score for t in self.tracks]).float()[:, None],
-                                torch.stack([t.obj_ind.reshape(()) for t in self.tracks]).float()[:, None]],
-                               1).cpu().numpy()
-            for track, row in zip(self.tracks, packed):
-                self.results.setdefault(track.id, {})[self.frame_index] = {
-                    'bbox': row[:4].copy(), 'score': np.float32(row[4]), 'obj_ind': int(row[5])}
-        for t in self.inactive_tracks:
-            t.count_inactive += 1
-        self.frame_index += 1
+            self._write_results(self._result_rows(orig_size).cpu().numpy())
+        self._end_frame(self)                                         # (this step has no reid_sim_only move)
 
 
 # ---------------------------------------------------------------------------------- multi-sequence
@@ -803,8 +816,9 @@ class TrackerKinematic(Tracker):
 # Kmax = max K_i rows per sample and marks rows K_i..Kmax-1 as placeholders
 # (targets[i]['track_queries_placeholder_mask'], kinet_amd/models/deformable_transformer.py).  The
 # tracks' embeddings, boxes and scores live in a device table (the track bank, one row = slot per
-# track, include/kinet_track.h); the state machine of each sequence is Tracker.step's, statement by
-# statement, on host mirrors (numpy) of the boxes and scores.
+# track, include/kinet_track.h); the state machine of each sequence is Tracker.step's -- the same
+# functions (_TrackRules), called with the sequence as their state -- on host mirrors (numpy) of the
+# boxes and scores.
 
 def plan_track_queries(n_active, n_inactive, num_queries):
     """The host plan of one frame's track queries: per-sequence counts of active and inactive tracks ->
@@ -875,8 +889,12 @@ class _Sequence:
         self.results = {}
         self.map_off = None     # masks: element offset of the sequence's map in the previous packed label buffer
 
+    def move_tracks_to_inactive(self, inactive_tracks):
+        self.tracks = [t for t in self.tracks if t not in inactive_tracks]
+        self.inactive_tracks += inactive_tracks
 
-class MultiTracker:
+
+class MultiTracker(_TrackRules):
     """`num_sequences` Trackers in one: reset(), step(blobs) with one blob per live sequence (the keys
     Tracker.step reads; frame sizes may differ), retire(i), get_results() -> one Tracker.get_results()
     dict per sequence.  Track ids, track_num, num_reids and frame_index are per sequence
@@ -895,9 +913,7 @@ class MultiTracker:
                  generate_attention_maps=False):
         from kinet_amd.models.deformable_detr import DeformablePostProcess
         from kinet_amd.models.kinet import KinematicDetectorTransformer
-        if generate_attention_maps or tracker_cfg.get('generate_attention_maps', False):
-            raise NotImplementedError('attention maps (tracker.py:38-40) need the decoder\'s attention '
-                                      'probabilities, which the fused attention kernels do not export')
+        self._read_cfg(tracker_cfg, generate_attention_maps or tracker_cfg.get('generate_attention_maps', False))
         self.masks = bool(tracker_cfg.get('masks', False))
         if self.masks and 'segm' not in obj_detector_post:
             raise NotImplementedError('MultiTracker carries segmentation masks (MOTS) only with the \'segm\' '
@@ -915,18 +931,6 @@ class MultiTracker:
         self.obj_detector = obj_detector
         self.obj_detector_post = obj_detector_post
         self.num_sequences = int(num_sequences)
-        self.detection_obj_score_thresh = tracker_cfg['detection_obj_score_thresh']
-        self.track_obj_score_thresh = tracker_cfg['track_obj_score_thresh']
-        self.detection_nms_thresh = tracker_cfg['detection_nms_thresh']
-        self.track_nms_thresh = tracker_cfg['track_nms_thresh']
-        self.public_detections = tracker_cfg['public_detections']
-        self.inactive_patience = float(tracker_cfg['inactive_patience'])
-        self.reid_sim_threshold = tracker_cfg['reid_sim_threshold']
-        self.reid_sim_only = tracker_cfg['reid_sim_only']
-        self.reid_score_thresh = tracker_cfg['reid_score_thresh']
-        self.reid_greedy_matching = tracker_cfg['reid_greedy_matching']
-        self.prev_frame_dist = tracker_cfg['prev_frame_dist']
-        self.steps_termination = tracker_cfg['steps_termination']
         self._logger = logger if logger is not None else (lambda *a: None)
         self.sync_count = 0
         self.reset()
@@ -1066,13 +1070,8 @@ class MultiTracker:
                 self._free(t.slot)
         q.inactive_tracks = kept
 
-    def _remove_tracks(self, q, keep, what, thresh):
-        remove = [t for t, k in zip(q.tracks, keep) if not k]
-        if remove:
-            self._logger(f'REMOVE TRACK IDS ({what}={thresh}): {[t.id for t in remove]}')
-            for t in remove:
-                self._free(t.slot)
-            q.tracks = [t for t in q.tracks if t not in remove]
+    def _release(self, track):
+        self._free(track.slot)
 
     # ------------------------------------------------------------------ masks
     def _resolve_masks(self, seqs, outputs, Nrows, out_hws, net_hws):
@@ -1161,16 +1160,9 @@ class MultiTracker:
             embeds, qboxes, mask = K.track_gather(self._bank, slots_d, off_d, sizes, Kmax, Q)
             targets = [{'track_query_boxes': qboxes[b], 'track_query_hs_embeds': embeds[b],
                         'track_queries_placeholder_mask': mask[b]} for b in range(B)]
-        defer = self.masks and hasattr(self.obj_detector, 'mask_logits_rows')
-        if defer:
-            # the head runs after the bookkeeping, on the surviving tracks' rows only
-            was_deferred, self.obj_detector.defer_masks = self.obj_detector.defer_masks, True
-        try:
+        with deferred_masks(self.obj_detector, self.masks and hasattr(self.obj_detector, 'mask_logits_rows')):
             outputs, _, features, _, _ = self.obj_detector(samples, targets, self._prev_features[0])
-        finally:
-            if defer:
-                self.obj_detector.defer_masks = was_deferred
-        hs = outputs['hs_embed'].float().contiguous()
+        hs =outputs['hs_embed'].float().contiguous()
         logits = outputs['pred_logits'].float().contiguous()
         if tuple(logits.shape[:2]) != (B, Nrows):
             raise RuntimeError(f'the detector returned {tuple(logits.shape[:2])} rows for {B} sequences of {Kmax} track '
@@ -1186,18 +1178,10 @@ class MultiTracker:
         # every box, score and threshold decision of this frame, all sequences, in ONE copy
         out_hws = net_hws = None
         if self.masks:
-            # the frames' two sizes as host ints; where they live on the device they ride in the same copy
-            size_t = [t.reshape(-1)[:2] for blob in blobs for t in (blob['orig_size'], blob['size'])]
-            if any(t.is_cuda for t in size_t):
-                extra = torch.cat([t.to(dev, torch.int32) for t in size_t]).view(torch.uint8)
-                host = self._to_host(torch.cat([packed, extra]))
-                hw = np.frombuffer(host[packed.numel():].tobytes(), np.int32).reshape(B, 2, 2)
-                host = host[:packed.numel()]
-            else:
-                host = self._to_host(packed)
-                hw = np.asarray([[int(v) for v in t.tolist()] for t in size_t], np.int32).reshape(B, 2, 2)
-            out_hws = [(int(hw[b, 0, 0]), int(hw[b, 0, 1])) for b in range(B)]
-            net_hws = [(int(hw[b, 1, 0]), int(hw[b, 1, 1])) for b in range(B)]
+            host, hw = copy_with_sizes(packed, [t for blob in blobs for t in (blob['orig_size'], blob['size'])],
+                                       self._to_host)
+            out_hws = [tuple(int(v) for v in s) for s in hw[0::2]]
+            net_hws = [tuple(int(v) for v in s) for s in hw[1::2]]
         else:
             host = self._to_host(packed)
         boxes, scores, _, dec = K.track_decide_views(host, B, Nrows)
@@ -1222,34 +1206,13 @@ class MultiTracker:
                 continue
             track_keep = ((dec[b, :nt] & K.TRACK_DEC_TRACK) != 0) & person[b, :nt]
             reid_keep = ((dec[b, :nt] & K.TRACK_DEC_REID) != 0) & person[b, :nt]
-            to_inactive, from_inactive = [], []
-            for i, track in enumerate(q.tracks):
-                if track_keep[i]:
-                    update(b, i, track)
-                    track.count_termination = 0
-                else:
-                    track.count_termination += 1
-                    if track.count_termination >= self.steps_termination:
-                        to_inactive.append(track)
-            for i, track in enumerate(q.inactive_tracks, start=len(q.tracks)):
-                if reid_keep[i]:
-                    update(b, i, track)
-                    from_inactive.append(track)
-            if to_inactive:
-                self._logger(f'NEW INACTIVE TRACK IDS (track_obj_score_thresh={self.track_obj_score_thresh}): '
-                             f'{[t.id for t in to_inactive]}')
-            q.num_reids += len(from_inactive)
-            for track in from_inactive:
-                q.inactive_tracks.remove(track)
-                q.tracks.append(track)
-            q.tracks = [t for t in q.tracks if t not in to_inactive]
-            q.inactive_tracks += to_inactive
+            self._score_phase(q, track_keep, reid_keep, functools.partial(update, b), q.move_tracks_to_inactive)
             segments.append([t.slot for t in q.tracks] if self.track_nms_thresh else [])
         keeps = self._nms(frame, segments, self.track_nms_thresh)
         if keeps is not None:
             for q, seg, keep in zip(seqs, segments, keeps):
                 if seg:
-                    self._remove_tracks(q, keep, 'track_nms_thresh', self.track_nms_thresh)
+                    self._drop_suppressed(q, keep, 'track_nms_thresh', self._release)
 
         # new detections (tracker.py:456-505): thresholds and public-detection gating on the host mirrors
         dets = []
@@ -1295,29 +1258,15 @@ class MultiTracker:
                 else:
                     dist_mat = dist[b]
                     rows, cols = reid_match_lsa(dist_mat)
-                remove_inactive = []
-                for r, c in zip(rows, cols):
-                    if dist_mat[r, c] <= self.reid_sim_threshold:
-                        track = q.inactive_tracks[r]
-                        self._logger(f'REID: track.id={track.id} - count_inactive={track.count_inactive} - '
-                                     f'to_inactive_frame={q.frame_index - track.count_inactive}')
-                        track.count_inactive = 0
-                        update(b, Kmax + int(det_keep[c]), track)
-                        reid_mask[c] = False
-                        remove_inactive.append(track)
-                        q.tracks.append(track)
-                        q.num_reids += 1
-                for track in remove_inactive:
-                    q.inactive_tracks.remove(track)
+                reid_mask[self._assign_reid(q, dist_mat, rows, cols,
+                                            lambda c, track: update(b, Kmax + int(det_keep[c]), track))] = False
             new_ids = []
             for j in det_keep[reid_mask].tolist():
                 track = _SlotTrack(None, None, q.track_num + len(new_ids), self._alloc(), j)
                 update(b, Kmax + j, track)
                 q.tracks.append(track)
                 new_ids.append(track.id)
-            q.track_num += len(new_ids)
-            if new_ids:
-                self._logger(f'INIT TRACK IDS (detection_obj_score_thresh={self.detection_obj_score_thresh}): {new_ids}')
+            self._count_new_tracks(q, new_ids)
             if self.detection_nms_thresh and q.tracks:
                 fresh = set(new_ids)
                 segments.append([t.slot for t in q.tracks])
@@ -1329,7 +1278,7 @@ class MultiTracker:
         if keeps is not None:
             for q, seg, keep in zip(seqs, segments, keeps):
                 if seg:
-                    self._remove_tracks(q, keep, 'detection_nms_thresh', self.detection_nms_thresh)
+                    self._drop_suppressed(q, keep, 'detection_nms_thresh', self._release)
         self._flush(frame)                                   # (commits no launch of this frame carried)
 
         masks = self._resolve_masks(seqs, outputs, Nrows, out_hws, net_hws) if self.masks else None
@@ -1341,10 +1290,5 @@ class MultiTracker:
                     'bbox': track.pos.copy(), 'score': np.float32(track.score), 'obj_ind': int(track.obj_ind)}
                 if masks is not None:
                     q.results[track.id][q.frame_index]['mask'] = masks[b][slot]
-            for t in q.inactive_tracks:
-                t.count_inactive += 1
-            q.frame_index += 1
-            if self.reid_sim_only:
-                q.inactive_tracks += q.tracks
-                q.tracks = []
+            self._end_frame(q, q.move_tracks_to_inactive if self.reid_sim_only else None)
         self._prev_features.append(features)

@@ -146,6 +146,52 @@ def reid_dist_ref(x, y):
     return (x.double()[:, None, :] - y.double()[None, :, :] + 1e-6).norm(dim=-1)
 
 
+# ---------------------------------------------------------------------------------- stand-ins for K.*
+# Thin adapters with the signatures and return layouts of kinet_amd.kernels' six tracker calls over the
+# restatements above, so the three trackers' state machines run on CPU tensors (test_tracker_state_cpu.py).
+def nms_adapter(boxes, scores, iou_threshold):
+    """K.nms: the kept indices by descending score, ties by index, NaN first."""
+    s = scores.float()
+    idx = nms_ref(boxes.float(), s, iou_threshold).nonzero().flatten()
+    return idx[torch.sort(s[idx], descending=True, stable=True)[1]]
+
+
+def track_decide_adapter(pred_logits, pred_boxes, sizes, n_active, n_inactive, Kmax, track_thresh, reid_thresh,
+                         detection_thresh, clip, out=None):
+    """K.track_decide: the packed uint8 buffer K.track_decide_views reads."""
+    boxes, scores, labels, dec = decide_ref(pred_logits, pred_boxes, sizes, (n_active + n_inactive).tolist(), Kmax,
+                                            track_thresh, reid_thresh, detection_thresh, clip)
+    return torch.cat([t.contiguous().view(torch.uint8).flatten() for t in (boxes.float(), scores.float(), labels, dec)])
+
+
+def nms_segments_adapter(boxes, scores, idx, offsets, total, iou_threshold, inf_flag=None, keep=None):
+    assert int(offsets[-1]) == total
+    return nms_segments_ref(boxes, scores, idx, offsets, iou_threshold, inf_flag)
+
+
+def track_commit_adapter(hs_embed, boxes, scores, rows, slots, n, bank):
+    commit_ref(bank, hs_embed, boxes, scores, rows[:n], slots[:n])
+
+
+def track_gather_adapter(bank, slots, offsets, sizes, Kmax, Q):
+    return gather_ref(bank, slots, offsets, sizes, Kmax, Q)
+
+
+def track_reid_dist_adapter(bank, hs_embed, slots, slot_off, rows, row_off, out_off, total):
+    d = hs_embed.shape[1]
+    out = torch.empty(int(total), dtype=torch.float32)
+    for s in range(out_off.numel() - 1):
+        a = slots[int(slot_off[s]):int(slot_off[s + 1])].long()
+        r = rows[int(row_off[s]):int(row_off[s + 1])].long()
+        out[int(out_off[s]):int(out_off[s + 1])] = reid_dist_ref(bank[a, :d], hs_embed[r]).float().flatten()
+    return out
+
+
+KERNEL_ADAPTERS = {'nms': nms_adapter, 'track_decide': track_decide_adapter, 'nms_segments': nms_segments_adapter,
+                   'track_commit': track_commit_adapter, 'track_gather': track_gather_adapter,
+                   'track_reid_dist': track_reid_dist_adapter}
+
+
 def small_tracking_model(golden_dir):
     """The small multi-frame Deformable tracking model of test_model_gpu.py's tracking tests (name-seeded
     weights of tests/golden/detr_tracking_mf_small.keys.txt), on the GPU in tracking mode."""

@@ -99,9 +99,16 @@ def test_shared_helpers_are_the_trackers():
     """Tracker and MultiTracker call the same gating / matching helpers (none is copied)."""
     import inspect
     from kinet_amd import tracker as T
-    for name in ('public_detections_mask', 'reid_match_greedy', 'reid_match_lsa'):
+    for name in ('public_detections_mask', 'reid_match_greedy', 'reid_match_lsa', 'deferred_masks', 'copy_with_sizes',
+                 'plan_mask_resolve', 'self._score_phase', 'self._drop_suppressed', 'self._assign_reid',
+                 'self._count_new_tracks', 'self._end_frame', 'self._read_cfg'):
         assert name + '(' in inspect.getsource(T.Tracker), name
         assert name + '(' in inspect.getsource(T.MultiTracker), name
+    # the per-frame rules themselves are written once, in the class both inherit
+    for cls in (T.Tracker, T.TrackerKinematic, T.MultiTracker):
+        assert issubclass(cls, T._TrackRules)
+        for name in ('_score_phase', '_drop_suppressed', '_assign_reid', '_count_new_tracks', '_end_frame', '_read_cfg'):
+            assert getattr(cls, name) is getattr(T._TrackRules, name), (cls, name)
 
 
 def test_header_declares_what_the_bindings_bind():
