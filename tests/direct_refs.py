@@ -1,7 +1,7 @@
 """High-precision restatements of the small kernels' operations, shared by
 test_ops_direct_gpu.py / test_grad_prims_gpu.py / test_grad_norm_attn_gpu.py /
-test_train_ops_direct_gpu.py / test_gemm_tiles_direct_gpu.py / test_msda_direct_gpu.py / test_attn_direct_gpu.py
-and checked on the CPU by test_direct_refs_cpu.py.
+test_train_ops_direct_gpu.py / test_gemm_tiles_direct_gpu.py / test_msda_direct_gpu.py / test_attn_direct_gpu.py /
+test_stem_conv3x3_direct_gpu.py and checked on the CPU by test_direct_refs_cpu.py.
 Plain torch on the CPU; nothing here touches the GPU or the native library."""
 import functools
 import math
@@ -2828,3 +2828,149 @@ def attn_mutation_arg(mut, case, kt=ATTN_KT):
     if mut == 'drop_block':
         return kt // 32 - 1 if kt < Lk else None
     return True
+
+
+# ======================= the stem (csrc/stem.hip) and the direct 3x3 (csrc/conv3x3.hip), path by path
+# The case tables and references of tests/test_stem_conv3x3_direct_gpu.py.  The two operand classes are
+# gemm.hip's (above): EXACT -- the image / activation from exact_x, the weights from exact_w at the
+# filter's K, scale and bias from exact_epilogue: every f32 partial sum is exact in any order and the
+# kernel must equal the f64 result rounded once; GENERIC -- randn operands under gemm_generic_bound.
+#   'c3':   x (B, H, W, 64) NHWC, w (64, 64, 3, 3) OIHW, stride 1, pad 1, K = 576
+#   'stem': x (B, 3, H, W) f32 NCHW image, w (64, 3, 7, 7) OIHW, stride 2, pad 3, K = 147
+FRONT_GEO = {'c3': (3, 1, 1, 64, 576), 'stem': (7, 2, 3, 3, 147)}       # filter, stride, pad, Cin, K
+FRONT_FAULTS = ('drop_tap', 'left_halo', 'prev_image_row', 'swap_kw_c')
+
+
+def conv_taps64(x_nhwc, w_ohwi, stride, pad, fault=None):
+    """The convolution as a plain f64 sum over the filter taps of (shifted, strided input slice) @
+    (the tap's (Cin, Cout) weights) -> (B*Ho*Wo, Cout), on the operands' device.  No im2col and no
+    library convolution: it runs wherever an f64 matmul does, and a fault is one line:
+      drop_tap        one (kh, kw, c) weight (the last row's middle tap, last channel) is left out;
+      left_halo       the padding columns left of the image repeat column 0 instead of zeros;
+      prev_image_row  the padding row just above image b holds the last row of image b - 1;
+      swap_kw_c       the weights of (kw, c) = (0, 0) and (KW - 1, Cin - 1) of the middle row trade places."""
+    x, w = x_nhwc.double(), w_ohwi.double()
+    B, H, W, C = x.shape
+    Co, KH, KW, _ = w.shape
+    (sh, sw), (ph, pw) = _pair(stride), _pair(pad)
+    Ho, Wo = out_size(H, W, KH, KW, stride, pad)
+    xp = F.pad(x, (0, 0, pw, pw, ph, ph))
+    if fault == 'left_halo':
+        xp[:, :, :pw] = xp[:, :, pw:pw + 1]
+    elif fault == 'prev_image_row':
+        xp[1:, ph - 1, pw:pw + W] = x[:-1, H - 1]
+    elif fault == 'drop_tap':
+        w = w.clone()
+        w[:, KH - 1, KW // 2, C - 1] = 0
+    elif fault == 'swap_kw_c':
+        w0, w = w, w.clone()
+        w[:, KH // 2, 0, 0], w[:, KH // 2, KW - 1, C - 1] = w0[:, KH // 2, KW - 1, C - 1], w0[:, KH // 2, 0, 0]
+    else:
+        assert fault is None, fault
+    out = x.new_zeros(B, Ho, Wo, Co)
+    for kh in range(KH):
+        for kw in range(KW):
+            out += xp[:, kh:kh + sh * (Ho - 1) + 1:sh, kw:kw + sw * (Wo - 1) + 1:sw] @ w[:, kh, kw].T
+    return out.reshape(B * Ho * Wo, Co)
+
+
+# conv3x3_c64_kernel: output tiles of 8 rows x 32 columns (halo 10 x 34), 2 channel halves x 4 row
+# pairs of waves, 16-column sub-tiles.  (1,1,1): every halo pixel but the centre is padding; (1,5,7)
+# below a tile; (1,8,32) one tile; (1,9,33) four tiles, the ragged ones 1 wide and 1 high; (1,2,17)
+# the sub-tile boundary; (3,17,65) batch boundaries (a halo row of image b +- 1, a column of the row before)
+C3_SHAPES = [(1, 1, 1), (1, 5, 7), (1, 8, 32), (1, 9, 33), (1, 2, 17), (3, 17, 65)]
+C3_MULTI_TILE = (1, 9, 33)                  # the smallest multi-tile case; with a batch: C3_SHAPES[-1]
+C3_LDC_SHAPE = (3, 17, 65)                  # written into the first 64 of 96 channels
+C3_EPILOGUES = {'plain': (False, False), 'scale_bias': (True, False), 'relu': (False, True), 'full': (True, True)}
+
+
+def c3_persistent_shape(cus=256):
+    """(B, 20, 70): 3 x 3 ragged tiles per image, B the least with more than 2 * cus tiles -- the grid is
+    one workgroup per CU, so some walk three tiles (both halo buffers reused, the vmcnt(4) wait)."""
+    return (2 * cus) // 9 + 1, 20, 70
+
+
+# stem_conv_kernel / stem_img_kernel: output tiles of 4 conv rows x 64 conv columns, a 512-wide grid.
+# (1,8,128) exactly one tile; (1,9,129) ragged in both directions; (1,16,126) / (1,15,125) the same
+# 8 x 63 map from an even and an odd image (the bottom and right padding differ)
+STEM_SHAPES = [(1, 1, 1), (1, 9, 7), (1, 8, 128), (1, 9, 129), (2, 7, 130), (1, 16, 126), (1, 15, 125)]
+STEM_MULTI_TILE = (1, 9, 129)               # with a batch: (2, 7, 130)
+# 6 tiles (and, pooled at seg_tiles = 1, 6 work units) per image: 1026 > 2 * 512, a workgroup walks three
+STEM_PERSISTENT = (171, 18, 130)
+# stem_pool_kernel: strips of 62 conv = 31 pooled columns.  Widths: Wo = 61 and 62 (Wp = 31, one strip),
+# 63 and 64 (Wp = 32: the second strip has one pooled column), 125 and 150 (test_stem_pool_gpu's);
+# heights: Ho = 4, 5, 8, 9 (one tile; a ragged second; two; a ragged third -- with seg_tiles 1 and 2 the
+# carried conv row and the pre step are both taken).  Alternately one and two images.
+POOL_SHAPES = [(1 + (i + j) % 2, H, W) for i, W in enumerate((122, 124, 125, 127, 250, 300))
+               for j, H in enumerate((7, 10, 16, 17))]
+POOL_SEG_TILES = (0, 1, 2, 3)
+POOL_BIAS1_SHAPE = (2, 17, 250)             # bias = 1 on every channel: padded conv rows / columns would win a border maximum
+POOL_ZERO_SHAPE = (1, 10, 127)              # all weights and biases zero
+FRONT_RESEED = {}                           # (kind, shape, variant) -> seed offset, where a draw missed exact_headroom
+
+
+def stem_out(H, W):
+    return (H - 1) // 2 + 1, (W - 1) // 2 + 1
+
+
+def _front_seed(kind, shape, cls, variant):
+    B, H, W = shape
+    return ((1 if kind == 'stem' else 2) * 1000003 + B * 7919 + H * 131 + W + (0 if cls == 'exact' else 5)
+            + 17 * len(variant or '') + 100 * FRONT_RESEED.get((kind, shape, variant), 0))
+
+
+@functools.lru_cache(maxsize=6)
+def front_case(kind, shape, cls, dtype=None, variant=None, dev='cpu'):
+    """One case of either family (the exact class does not depend on dtype: pass None).
+      x      what the entry point is given: 'c3' (B, H, W, 64) holding `dtype` values; 'stem' the f32 NCHW
+             image -- exact class: exact_x, the in-kernel rounding is the identity; generic: randn NOT yet
+             rounded, the reference rounds it to `dtype` as torch does (to nearest even);
+      w      OIHW, f32 holding `dtype` values;   scale, bias (64,) f32
+      acc, absprod  (B*Ho*Wo, 64) f64 on the CPU: the convolution of the rounded operands and of their
+             absolute values, computed on `dev`.
+    variant (stem, exact class): 'bias1' -- bias 1 on every channel; 'zero' -- all weights and biases 0."""
+    k, stride, pad, Cin, K = FRONT_GEO[kind]
+    B, H, W = shape
+    g = torch.Generator().manual_seed(_front_seed(kind, shape, cls, variant))
+    xshape = (B, H, W, 64) if kind == 'c3' else (B, 3, H, W)
+    if cls == 'exact':
+        x, w = exact_x(xshape, g), exact_w((64, Cin, k, k), K, g)
+        scale, bias = exact_epilogue(64, g)
+        xr = x
+    else:
+        assert variant is None
+        xr, w = generic_operands(xshape, (64, Cin, k, k), K, dtype, g)
+        x = xr
+        if kind == 'stem':          # the kernel is given the unrounded draw of the same generator state
+            x = torch.randn(xshape, generator=torch.Generator().manual_seed(_front_seed(kind, shape, cls, variant)))
+            assert torch.equal(x.to(dtype).float(), xr)
+        scale, bias = generic_epilogue(64, g)
+    if variant == 'bias1':
+        bias = torch.ones(64)
+    elif variant == 'zero':
+        w, bias = torch.zeros_like(w), torch.zeros(64)
+    xn = (xr if kind == 'c3' else xr.permute(0, 2, 3, 1)).to(dev)
+    wn = w.permute(0, 2, 3, 1).to(dev)
+    Ho, Wo = out_size(H, W, k, k, stride, pad)
+    return {'x': x, 'w': w, 'scale': scale, 'bias': bias, 'K': K, 'B': B, 'Ho': Ho, 'Wo': Wo,
+            'acc': conv_taps64(xn, wn, stride, pad).cpu(), 'absprod': conv_taps64(xn.abs(), wn.abs(), stride, pad).cpu()}
+
+
+def front_expected(case, scale_bias=True, relu=True):
+    """(f64 value before the output rounding, the bound's majorant, the scale the bound carries)."""
+    s, b = (case['scale'], case['bias']) if scale_bias else (None, None)
+    return epilogue64(case['acc'], s, b, None, relu) + (s,)
+
+
+def pool_rows(v, B, Ho, Wo):
+    """torch's 3x3 / stride 2 / pad 1 max_pool2d of the (B*Ho*Wo, C) rows of an NHWC map -> (B*Hp*Wp, C)
+    (in f64 for a 16-bit v: the maximum of exactly held values)."""
+    t = v.double().reshape(B, Ho, Wo, -1).permute(0, 3, 1, 2)
+    return F.max_pool2d(t, 3, 2, 1).permute(0, 2, 3, 1).reshape(-1, v.shape[-1]).to(v.dtype)
+
+
+def front_exact_cases(cus=256):
+    """(kind, shape, variant) of every exact-class case of the GPU module."""
+    out = [('c3', s, None) for s in C3_SHAPES + [c3_persistent_shape(cus)]]
+    out += [('stem', s, None) for s in STEM_SHAPES + [STEM_PERSISTENT] + POOL_SHAPES]
+    return out + [('stem', POOL_BIAS1_SHAPE, 'bias1'), ('stem', POOL_ZERO_SHAPE, 'zero')]

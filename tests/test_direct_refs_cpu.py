@@ -1508,3 +1508,161 @@ def test_attn_mutations_are_caught(D, mut):
 @functools.lru_cache(maxsize=None)
 def _attn_bound(D, dtype, name):
     return R.attn_fwd_bound(dict(_attn_generic_cases(dtype, D))[name], 'resident', dtype)
+
+
+# ------------------------------------- the stem and direct 3x3 kernels (test_stem_conv3x3_direct_gpu.py)
+_FRONT_DT = [torch.bfloat16, torch.float16]
+
+
+def _front_nhwc(kind, x):
+    return x if kind == 'c3' else x.permute(0, 2, 3, 1)
+
+
+def _front_f32(kind, c, scale_bias=True, relu=True, x=None):
+    """torch's own f32 convolution and f32 epilogue of a case's operands -> (B*Ho*Wo, 64) f32."""
+    k, stride, pad, Cin, K = R.FRONT_GEO[kind]
+    x = c['x'] if x is None else x
+    y = F.conv2d(x.permute(0, 3, 1, 2) if kind == 'c3' else x, c['w'], stride=stride, padding=pad)
+    y = y.permute(0, 2, 3, 1).reshape(-1, 64)
+    if scale_bias:
+        y = y * c['scale'] + c['bias']
+    return torch.relu(y) if relu else y
+
+
+def test_front_tables_reach_the_paths_they_name():
+    """The geometry behind the tables' comments: tiles, strips, persistent walks."""
+    def tiles(shape, th, tw, stem):
+        B, H, W = shape
+        Ho, Wo = R.stem_out(H, W) if stem else (H, W)
+        return B, -(-Ho // th), -(-Wo // tw)
+    assert [tiles(s, 8, 32, False) for s in R.C3_SHAPES] == [(1, 1, 1), (1, 1, 1), (1, 1, 1), (1, 2, 2), (1, 1, 1), (3, 3, 3)]
+    for cus in (256, 304, 64):
+        B, ty, tx = tiles(R.c3_persistent_shape(cus), 8, 32, False)
+        assert (ty, tx) == (3, 3) and 2 * cus < B * 9 <= 2 * cus + 9
+    assert [tiles(s, 4, 64, True) for s in R.STEM_SHAPES] == [(1, 1, 1), (1, 2, 1), (1, 1, 1), (1, 2, 2), (2, 1, 2), (1, 2, 1),
+                                                              (1, 2, 1)]
+    assert R.stem_out(8, 128) == (4, 64) and R.stem_out(16, 126) == R.stem_out(15, 125) == (8, 63)
+    B, ty, tx = tiles(R.STEM_PERSISTENT, 4, 64, True)
+    assert B * ty * tx > 2 * 512
+    Ho, Wo = R.stem_out(*R.STEM_PERSISTENT[1:])
+    assert B * -(-((Wo - 1) // 2 + 1) // 31) * -(-Ho // 4) > 2 * 512              # pooled, at seg_tiles = 1
+    geo = {(R.stem_out(H, W)[0], (R.stem_out(H, W)[1] - 1) // 2 + 1) for _, H, W in R.POOL_SHAPES}
+    assert {h for h, _ in geo} == {4, 5, 8, 9} and {w for _, w in geo} == {31, 32, 63, 75}
+    assert {R.stem_out(H, W)[1] for _, H, W in R.POOL_SHAPES} == {61, 62, 63, 64, 125, 150}
+    assert {b for b, _, _ in R.POOL_SHAPES} == {1, 2}
+
+
+@pytest.mark.parametrize('kind,shape,variant', R.front_exact_cases(), ids=str)
+def test_front_exact_cases_are_exact_with_headroom(kind, shape, variant):
+    """Every exact-class case of the GPU module: operands on the class's grids and representable in both
+    16-bit types; the tap-sum reference equals F.conv2d in f64; torch's f32 convolution and f32 epilogue
+    equal the f64 result (the class is order-free); a 16-bit output resolves one dropped product on
+    every element, under every epilogue the module runs."""
+    c = R.front_case(kind, shape, 'exact', None, variant)
+    k, stride, pad, Cin, K = R.FRONT_GEO[kind]
+    x, w = c['x'], c['w']
+    assert ((x * 2) == (x * 2).round()).all() and x.abs().max() <= 1
+    assert ((w * 8) == (w * 8).round()).all() and w.abs().max() <= 0.25 and w.shape == (64, Cin, k, k)
+    assert (w != 0).float().mean() > 0.15 or variant == 'zero'
+    for dt in _FRONT_DT:
+        assert (x.to(dt).float() == x).all() and (w.to(dt).float() == w).all()
+    assert torch.equal(c['acc'], R.conv64(_front_nhwc(kind, x), w.permute(0, 2, 3, 1), stride, pad))
+    assert c['acc'].shape == (c['B'] * c['Ho'] * c['Wo'], 64)
+    for sb, relu in (R.C3_EPILOGUES.values() if kind == 'c3' else [(True, True)]):
+        pre, _, s = R.front_expected(c, sb, relu)
+        assert torch.equal(_front_f32(kind, c, sb, relu).double(), pre)
+        if not relu:
+            assert (pre < 0).any()
+        for dt in _FRONT_DT:
+            assert R.exact_headroom(pre, s, dt).all(), (sb, relu, dt, pre.abs().max().item())
+
+
+@pytest.mark.parametrize('fault', R.FRONT_FAULTS)
+@pytest.mark.parametrize('kind', ['c3', 'stem'])
+def test_front_exact_inputs_discriminate(kind, fault):
+    """The smallest multi-tile exact case (with a batch for the row leaking from image b - 1) recomputed with
+    one fault differs from the true reference -- in the accumulator, in the rounded 16-bit output and, for
+    the stem, in the pooled map."""
+    multi, batch = {'c3': (R.C3_MULTI_TILE, R.C3_SHAPES[-1]), 'stem': (R.STEM_MULTI_TILE, (2, 7, 130))}[kind]
+    c = R.front_case(kind, batch if fault == 'prev_image_row' else multi, 'exact')
+    k, stride, pad, Cin, K = R.FRONT_GEO[kind]
+    xn, wn = _front_nhwc(kind, c['x']), c['w'].permute(0, 2, 3, 1)
+    assert torch.equal(R.conv_taps64(xn, wn, stride, pad), c['acc'])
+    bad = R.conv_taps64(xn, wn, stride, pad, fault)
+    assert (bad != c['acc']).any()
+    pre = R.front_expected(c)[0]
+    pre_bad = R.epilogue64(bad, c['scale'], c['bias'], None, True)[0]
+    for dt in _FRONT_DT:
+        assert (pre_bad.to(dt) != pre.to(dt)).any()
+        if kind == 'stem':
+            geo = (c['B'], c['Ho'], c['Wo'])
+            assert (R.pool_rows(pre_bad.to(dt), *geo) != R.pool_rows(pre.to(dt), *geo)).any()
+
+
+def _truncate(x, dtype):
+    """f32 -> dtype rounded towards zero (what a kernel that drops the low bits would feed the MFMAs)."""
+    if dtype == torch.bfloat16:
+        return (x.view(torch.int32) & -65536).view(torch.float32)
+    h = x.half()
+    over = h.float().abs() > x.abs()
+    return torch.where(over, (h.view(torch.int16) - 1).view(torch.float16), h).float()
+
+
+@pytest.mark.parametrize('dtype', _FRONT_DT, ids=str)
+@pytest.mark.parametrize('kind,shape', [('c3', R.C3_MULTI_TILE), ('stem', R.STEM_MULTI_TILE), ('stem', R.POOL_BIAS1_SHAPE)], ids=str)
+def test_front_generic_bound_holds_for_torch_f32_and_rejects_defects(kind, shape, dtype):
+    """torch's f32 convolution of the rounded operands + f32 epilogue + one output rounding stays inside the
+    generic bound, and its pooled map inside the pooled bound; one dropped tap leaves it, and so does (stem)
+    an image truncated to the 16-bit type instead of rounded to nearest."""
+    c = R.front_case(kind, shape, 'generic', dtype)
+    k, stride, pad, Cin, K = R.FRONT_GEO[kind]
+    xr = c['x'].to(dtype).float()
+    assert (c['w'].to(dtype).float() == c['w']).all()
+    assert (xr != c['x']).any() == (kind == 'stem')
+    pre, maj, s = R.front_expected(c)
+    bound = R.gemm_generic_bound(c['absprod'], K, maj, pre, dtype, s)
+    geo = (c['B'], c['Ho'], c['Wo'])
+    good = _front_f32(kind, c, x=xr).to(dtype).double()
+    err = (good - pre).abs()
+    print(f'{kind} {shape} {dtype}: torch f32 worst err / bound {(err / bound).max().item():.3f}')
+    assert (err <= bound).all()
+    dropped = R.epilogue64(R.conv_taps64(_front_nhwc(kind, xr), c['w'].permute(0, 2, 3, 1), stride, pad, 'drop_tap'),
+                           c['scale'], c['bias'], None, True)[0].to(dtype).double()
+    # (ReLU clears half of the map, and at the bottom rows the dropped tap lies in the padding)
+    assert ((dropped - pre).abs() > bound).float().mean() > 0.1
+    if kind == 'stem':
+        pooled, pbound = R.pool_rows(pre, *geo), R.pool_rows(bound, *geo)
+        assert ((R.pool_rows(good, *geo) - pooled).abs() <= pbound).all()
+        assert ((R.pool_rows(dropped, *geo) - pooled).abs() > pbound).float().mean() > 0.1
+        xt = _truncate(c['x'], dtype)
+        assert (xt.abs() <= c['x'].abs()).all() and (xt.to(dtype).float() == xt).all() and (xt != xr).any()
+        trunc = _front_f32(kind, c, x=xt).to(dtype).double()
+        share = ((trunc - pre).abs() > bound).float().mean().item()
+        pshare = ((R.pool_rows(trunc, *geo) - pooled).abs() > pbound).float().mean().item()
+        print(f'truncated image: {share:.3f} of the conv map and {pshare:.3f} of the pooled map outside the bound')
+        assert share > 0.01 and pshare > 0.01
+
+
+@pytest.mark.parametrize('dtype', _FRONT_DT, ids=str)
+def test_pool_border_case_tells_parked_padding_from_computed_padding(dtype):
+    """The bias = 1 case: the signed 16-bit maximum over post-ReLU patterns, with the taps outside the conv map
+    parked as -0.0 (0x8000, the smallest int16), is torch's max_pool2d; were those taps computed from the
+    zero-padded image instead (relu(bias) = 1), the last pooled row and column would change."""
+    c = R.front_case('stem', R.POOL_BIAS1_SHAPE, 'exact', None, 'bias1')
+    B, Ho, Wo = c['B'], c['Ho'], c['Wo']
+    conv = R.front_expected(c)[0].to(dtype)
+    want = R.pool_rows(conv, B, Ho, Wo).view(B, (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1, 64)
+    bits = conv.view(torch.int16).double().view(B, Ho, Wo, 64).permute(0, 3, 1, 2)
+    assert (bits >= 0).all()                                       # post-ReLU: the sign bit is clear
+    parked = F.max_pool2d(F.pad(bits, (1, 1, 1, 1), value=-32768.0), 3, 2, 0).permute(0, 2, 3, 1)
+    assert torch.equal(parked.to(torch.int16).view(dtype), want)
+    ones = F.max_pool2d(F.pad(conv.double().view(B, Ho, Wo, 64).permute(0, 3, 1, 2), (1, 1, 1, 1), value=1.0), 3, 2, 0)
+    differ = ones.permute(0, 2, 3, 1) != want.double()
+    assert Ho % 2 == 1 and Wo % 2 == 1                             # the last pooled row and column reach past the map
+    assert differ[:, -1].any() and differ[:, :, -1].any()
+
+
+def test_pool_zero_case_is_all_positive_zero():
+    c = R.front_case('stem', R.POOL_ZERO_SHAPE, 'exact', None, 'zero')
+    assert (c['w'] == 0).all() and (c['bias'] == 0).all() and (c['x'] != 0).any()
+    assert (R.front_expected(c)[0] == 0).all()

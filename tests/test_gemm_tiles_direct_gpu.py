@@ -20,7 +20,8 @@ pytestmark = pytest.mark.gpu
 BF16, F16, F32 = torch.bfloat16, torch.float16, torch.float32
 TYPES = [(BF16, BF16), (BF16, F32), (BF16, F16), (F16, F16), (F16, F32), (F32, F32)]
 SENTINEL = 77.0
-NO_SPECIAL = 4 | 32 | 1024      # never the resident-weight, stem or direct 3x3 kernels
+NO_SPECIAL = 4 | 32 | 1024      # never the resident-weight, stem or direct 3x3 kernels (test_gemm_rw_direct_gpu.py,
+#                                 test_stem_conv3x3_direct_gpu.py hold those to their own f64 references)
 DMA4 = 16                       # LDS-DMA staging of the 4-wave tiles
 
 _LOG = {'t0': time.time(), 'generic': {}, 'exact_bad': 0, 'exact_n': 0, 'kernels': set()}
