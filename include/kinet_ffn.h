@@ -145,12 +145,35 @@ enum kinet_ffn_plan_field {
 };
 enum kinet_ffn_pack_kind { KINET_FFN_PACK_FFN = 0, KINET_FFN_PACK_PAIR, KINET_FFN_PACK_DS, KINET_FFN_PACK_ATTN };
 
+/* kinet_ffn_sched: the ring schedule of the 8-wave x 32-row FFN kernel (csrc/ffn_sched.h; no GPU
+ * call) for a workgroup that walks `cnt` row tiles of `pch` pre-chunks (4 with the attention
+ * out-projection, else 0) and `nch` hidden chunks each: what a wave of `role` (0: waves 0-3, 1: waves
+ * 4-7) does around the barrier of ring chunk q in [0, cnt (pch + nch)), or in the prologue (q = -1:
+ * the issue list only).  A chunk half is a pair (chunk, half), half 0 = fragments 0 .. FR/2 - 1 (W1
+ * of a hidden chunk), 1 = the rest (W2); `half_ops` = LDS-DMA operations of a wave per half.  Lists
+ * are in program order, unused places -1.  KINET_ERR_ARG outside these ranges. */
+enum kinet_ffn_sched_field {
+    KINET_FFNS_TOTAL = 0,     /* ring chunks of the workgroup */
+    KINET_FFNS_BARRIERS,      /* barriers a wave of this role executes behind the prologue, in all */
+    KINET_FFNS_BARRIER,       /* index of the barrier that opens interval q (= q) */
+    KINET_FFNS_SLOT,          /* ring slot of chunk q */
+    KINET_FFNS_VMCNT,         /* vmcnt argument of the wait in front of barrier q (the ring's own operations) */
+    KINET_FFNS_N_ISSUE,       /* halves issued behind barrier q, then 3 (chunk, half) pairs */
+    KINET_FFNS_ISSUE,
+    KINET_FFNS_N_EARLY = KINET_FFNS_ISSUE + 6,   /* halves read ahead in front of barrier q (behind barrier q - 1) */
+    KINET_FFNS_EARLY,
+    KINET_FFNS_N_READ = KINET_FFNS_EARLY + 6,    /* halves read between barriers q and q + 1 */
+    KINET_FFNS_READ,
+    KINET_FFNS_FIELDS = KINET_FFNS_READ + 6
+};
+
 int kinet_ffn_set_debug(int flags);
 int kinet_ffn_grid_cap(int max_wgs);
 int kinet_ffn_launch_plan(const int* problem, int cus, int* plan_out);
 int kinet_ffn_last_kernel(void);
 const char* kinet_ffn_kernel_name(int kernel);
 int kinet_ffn_pack_map(int kind, int D, int F, int DB, int32_t* out);
+int kinet_ffn_sched(int role, int cnt, int pch, int nch, int q, int half_ops, int* out);
 
 #ifdef __cplusplus
 }

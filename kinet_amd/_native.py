@@ -62,6 +62,7 @@ _SIGS = {
     'kinet_ffn_last_kernel': [],
     'kinet_ffn_kernel_name': [I],
     'kinet_ffn_pack_map': [I, I, I, I, P],
+    'kinet_ffn_sched': [I, I, I, I, I, I, P],
     'kinet_ffn_fused': [P, I, P, P, P, P, P, F, P, I, I, I, I, I, P],
     'kinet_ffn_pack_attn': [P, P, P, P, I, I, I, P],
     'kinet_attn_out_ffn_fused': [P, I, P, I, P, P, P, P, F, P, P, P, P, F, P, I, I, I, I, I, P],

@@ -26,6 +26,7 @@
 #include "../../include/kinet_ffn.h"
 #include "common.h"
 #include "ffn_plan.h"
+#include "ffn_sched.h"
 #include "gemm_common.h"
 
 namespace kinet {
@@ -71,12 +72,20 @@ constexpr bool ffn_entry_is(const FfnKernel k) {
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+// two floats rounded (nearest even, NaN stays NaN: f32_to_bf16's cast) into one 32-bit word, a in
+// the low half: the 2-vector conversion is ONE v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32 d, a, b; two
+// scalar casts glued with a shift and an or were four instructions per word
 template <typename T>
 __device__ __forceinline__ uint32_t pack2(float a, float b) {
+    const f32x2 v{a, b};
     if constexpr (std::is_same<T, bf16_t>::value) {
-        return (uint32_t)f32_to_bf16(a).x | ((uint32_t)f32_to_bf16(b).x << 16);
+        return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
     } else {
-        return (uint32_t)__builtin_bit_cast(uint16_t, (f16_t)a) | ((uint32_t)__builtin_bit_cast(uint16_t, (f16_t)b) << 16);
+        return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
     }
 }
 
@@ -403,10 +412,13 @@ __global__ __launch_bounds__(WAVES * 64) void ffn_fused_kernel(const FfnArgs p, 
 // 8 waves x 32 rows (two 16-row tiles per wave; the default at D = 256): every 1-KiB weight
 // fragment read from the ring feeds two MFMAs -- half the LDS reads per MFMA of the 16-row tile,
 // whose 8 waves saturate the LDS read port.  To stay within 256 VGPRs (two waves
-// per SIMD) the tile's x fragments are loaded at the tile start instead of one tile ahead, phase
-// B of a chunk follows its own phase A (no cross-chunk software pipeline) and the ring holds 3
-// chunks (2 in flight + the one being computed).  Same packed weights, same sums in the same
-// order per output element as ffn_fused_kernel (bit-identical results).
+// per SIMD) the tile's x fragments are loaded at the tile start instead of one tile ahead and the
+// ring holds 3 chunks, staged and recycled by halves (W1 | W2).  The two waves of a SIMD take two
+// roles (ffn_sched.h): waves 0-3 run a chunk's phase B behind its own phase A, waves 4-7 run it one
+// chunk barrier later (hb kept in registers), so one role's ReLU / convert block and its wait for
+// the first fragments fall beside the partner's MFMAs instead of beside the same stretch of the
+// same program.  Same packed weights, same sums in the same order per output element as
+// ffn_fused_kernel (bit-identical results).
 //
 // PRE (kinet_attn_out_ffn_fused): the attention out-projection and its post-norm run in front of
 // the FFN on the same tile, x = LN1(R + A Wo^T + bo), so x is never written to or read from HBM.
@@ -425,8 +437,11 @@ __global__ __launch_bounds__(512) void ffn_fused_rt2_kernel(const FfnArgs p, con
     constexpr int KS = G::KS, NT = G::NT, FR = G::FR;
     static_assert(FR % WAVES == 0, "whole DMA rounds per chunk");
     constexpr int FRW = FR / WAVES;
+    static_assert(FRW % 2 == 0 && 2 * KS == FR / 2, "a chunk is staged as two halves: W1 | W2");
+    constexpr int HW = FRW / 2;              // LDS-DMA instructions per wave per chunk half
     constexpr int ROWS = WAVES * 16 * RT;
-    constexpr int NS = 3;
+    constexpr int NS = kFfnSchedSlots;
+    static_assert(WAVES == 2 * kFfnSchedRoleSplit, "SIMD partners w, w + 4 take the two roles");
     constexpr unsigned OOB = 0x80000000u;
     constexpr int PCH = PRE ? KS * NT / FR : 0;   // Wo chunks per tile (FR fragments each)
     static_assert(!PRE || (KS * NT) % FR == 0, "Wo must fill whole ring chunks");
@@ -469,13 +484,14 @@ __global__ __launch_bounds__(512) void ffn_fused_rt2_kernel(const FfnArgs p, con
             pbe1[i] = p.be1[i];
         }
     }
-    // chunk c of the packed stream ([PCH Wo chunks,] then the hidden chunks) -> ring slot q % NS
-    auto dma_chunk = [&](int q, int c) {
-        char* dst = ring + (q % NS) * G::CHUNK;
+    // half `half` of chunk c of the packed stream ([PCH Wo chunks,] then the hidden chunks) -> its
+    // half of ring slot q % NS (ffn_sched.h): fragments 16 half + wave, 16 half + 8 + wave
+    auto dma_half = [&](int q, int c, int half) {
+        char* dst = ring + ffn_sched_slot(q) * G::CHUNK;
         const unsigned src = (unsigned)c * (unsigned)G::CHUNK + (unsigned)lane * 16u;
 #pragma unroll
-        for (int k = 0; k < FRW; ++k) {
-            const int f = k * WAVES + wave;
+        for (int k = 0; k < HW; ++k) {
+            const int f = (half * HW + k) * WAVES + wave;
             if constexpr (PRE) {
                 // the wave-uniform part of the source goes in the scalar offset: the unrolled Wo
                 // chunks otherwise keep FRW loop-invariant vector addresses each (spilled)
@@ -486,10 +502,47 @@ __global__ __launch_bounds__(512) void ffn_fused_rt2_kernel(const FfnArgs p, con
         }
     };
     const int ncht = nch + PCH;   // ring chunks per tile
-    const int total = cnt * ncht;
+    const int total = ffn_sched_total(cnt, PCH, nch);
+    // The one barrier of chunk q, executed by every wave of either role exactly once per chunk: the
+    // tile loop, the PCH pre-chunks and the nch hidden chunks have the same trip counts for all
+    // waves (cnt, nch and PCH are workgroup-uniform) and each iteration calls this once, so every
+    // wave executes ffn_sched_barriers() = cnt (PCH + nch) barriers; the roles differ only in the
+    // MFMA work between two of them.  In front of the barrier the wave's DMA of both halves of
+    // chunk q has landed: younger are at most LO of chunk q + 1 (HW operations) and EXTRA loads the
+    // caller counts (at a tile boundary also the previous tile's stores and this tile's operand
+    // loads -- then this waits for some of those too).  Behind it chunk q is visible to all, and
+    // every wave has finished interval q - 1: HI of chunk q - 2 and LO of chunk q - 1 have had
+    // their last reads, their half-slots take HI of chunk q + 1 and LO of chunk q + 2.
+    // u = q's position in its tile's stream
+    auto ring_step = [&](int q, int u, auto extra) {
+        constexpr int EXTRA = decltype(extra)::value;
+        constexpr int MID = ffn_sched_vmcnt(0, 2, HW), END = ffn_sched_vmcnt(0, 1, HW);   // a chunk follows / the last
+        if (q + 1 < total) ffn_wait_vmcnt<MID + EXTRA>();
+        else ffn_wait_vmcnt<END>();
+        ffn_lds_barrier();
+#pragma unroll
+        for (int i = 0; i < kFfnSchedIssues; ++i) {
+            const int ahead = kFfnSchedIssue[i].chunk;
+            if (q + ahead < total) {
+                int cn = u + ahead;
+                if (cn >= ncht) cn -= ncht;
+                if (cn >= ncht) cn -= ncht;   // ncht == 1
+                dma_half(q + ahead, cn, kFfnSchedIssue[i].half);
+            }
+        }
+    };
+    using no_extra = std::integral_constant<int, 0>;
     __syncthreads();   // parameters in LDS
-    dma_chunk(0, 0);
-    if (total > 1) dma_chunk(1, ncht > 1 ? 1 : 0);
+    {   // what the barriers -2 and -1 would have issued: LO(0), HI(0), LO(1)
+        dma_half(0, 0, FFN_HALF_LO);
+        dma_half(0, 0, FFN_HALF_HI);
+        if (total > 1) dma_half(1, ncht > 1 ? 1 : 0, FFN_HALF_LO);
+    }
+    // The roles are split with the pre-phase only: the plain kernel measured SLOWER staggered (batch-28
+    // encoder rows: 541.9 us against 527.1 us with every wave in role 0) where the PRE kernel gained
+    // (656.7 against 669.1 us), profiles/ffn_stagger_ab.txt; both run the one half-slot ring protocol
+    constexpr bool STAGGER = PRE;
+    const int role = STAGGER ? ffn_sched_role(wave) : 0;
 
     u32x4 xr[RT][KS];
     f32x4 acc[RT][NT];
@@ -523,30 +576,24 @@ __global__ __launch_bounds__(512) void ffn_fused_rt2_kernel(const FfnArgs p, con
                 }
             };
             constexpr int KPC = FR / NT;   // k-steps per Wo chunk
-            constexpr int PDW = RV == 1 ? 3 : 4;   // Wo fragments read ahead of their MFMAs (RV 1: 4 spill)
+            constexpr int PDW = RV == 1 ? 2 : 4;   // Wo fragments read ahead of their MFMAs (RV 1: 3 and 4 spill)
 #pragma unroll
             for (int u = 0; u < PCH; ++u) {
                 const int q = ti * ncht + u;
                 // chunk q landed (a hidden chunk always follows: q + 1 < total).  Younger than its
-                // DMA: chunk q+1's DMA and, with RV == 1 from u = 2 on, the RT * KPC residual loads
-                // of pre-chunk u-1 (those of pre-chunk u-2 are counted as older, whichever side of
-                // that iteration's DMA they were issued on); at u = 0 also the previous tile's
+                // halves' DMA: LO of chunk q+1 and, with RV == 1 from u = 2 on, the RT * KPC residual
+                // loads of pre-chunk u-1 (those of pre-chunk u-2 are counted as older, whichever side
+                // of that iteration's DMA they were issued on); at u = 0 also the previous tile's
                 // stores and this tile's A loads, which this then waits for too
-                if (RV == 1 && u >= 2) ffn_wait_vmcnt<FRW + RT * KPC>();
-                else ffn_wait_vmcnt<FRW>();
-                ffn_lds_barrier();   // chunk q visible; slot (q+2) % NS (chunk q-1) free
-                if (q + 2 < total) {
-                    int cn = u + 2;
-                    if (cn >= ncht) cn -= ncht;
-                    dma_chunk(q + 2, cn);
-                }
+                if (RV == 1 && u >= 2) ring_step(q, u, std::integral_constant<int, RT * KPC>{});
+                else ring_step(q, u, no_extra{});
                 if constexpr (RV == 1) {
                     if (u > 0) {
 #pragma unroll
                         for (int k = 0; k < KPC; ++k) load_res((u - 1) * KPC + k);
                     }
                 }
-                const char* wb = ring + (q % NS) * G::CHUNK;
+                const char* wb = ring + ffn_sched_slot(q) * G::CHUNK;
                 auto frag = [&](int f) { return *reinterpret_cast<const u32x4*>(wb + lane * 16 + f * 1024); };
                 // x^T(D x rows) += Wo[:, k-steps of this chunk] A^T: fragment f = (k-step f / NT,
                 // tile f % NT), each feeding both row tiles; per accumulator the k-steps ascend
@@ -623,56 +670,43 @@ __global__ __launch_bounds__(512) void ffn_fused_rt2_kernel(const FfnArgs p, con
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) acc[rt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        for (int c = 0; c < nch; ++c) {
-            const int q = ti * ncht + PCH + c;
-            // chunk q landed: younger are at most chunk q+1's DMA (plus, at a tile boundary, the
-            // previous tile's stores and this tile's x loads -- then this waits for those too;
-            // with PRE everything issued before LN1 has been waited for by the loads it consumed)
-            if (q + 1 < total) ffn_wait_vmcnt<FRW>();
-            else ffn_wait_vmcnt<0>();
-            ffn_lds_barrier();   // chunk q visible; slot (q+2) % NS (chunk q-1) free
-            if (q + 2 < total) {
-                int cn = PCH + c + 2;
-                if (cn >= ncht) cn -= ncht;
-                if (cn >= ncht) cn -= ncht;
-                dma_chunk(q + 2, cn);
-            }
-            const char* wb = ring + (q % NS) * G::CHUNK;
+        // ---- the hidden chunks ----
+        // Fragments are read ahead of their MFMAs: phase A's two k-steps ahead, phase B's four
+        // fragments ahead.  The scheduling barriers keep the compiler from sinking the reads back
+        // next to their uses, where each pair of MFMAs waited for its own LDS round trip: 593-599
+        // -> 566-569 us per batch-28 encoder FFN, bit-identical
+        // (profiles/r06af_ffn_prefetch_ab.txt; 3 or 6 ahead: the same time)
+        constexpr int PDA = 2, PDB = 4;
+        static_assert(KS >= PDA && NT >= PDB && PDB > PDA, "prefetch depths");
+        auto slot_of = [&](int q) { return ring + ffn_sched_slot(q) * G::CHUNK; };
+        auto frag = [&](const char* wb, int f) { return *reinterpret_cast<const u32x4*>(wb + lane * 16 + f * 1024); };
+        auto read_a = [&](const char* wb, u32x4(&fa)[KS][2], int ks) {
+            fa[ks][0] = frag(wb, ks);
+            fa[ks][1] = frag(wb, KS + ks);
+        };
+        auto read_bias = [&](int c, f32x4(&bb)[2]) {
+            bb[0] = *reinterpret_cast<const f32x4*>(pb1 + c * 32 + 4 * g);
+            bb[1] = *reinterpret_cast<const f32x4*>(pb1 + c * 32 + 16 + 4 * g);
+        };
+        // phase A of the hidden chunk in slot wb: H^T chunk (32 hidden x 32 rows) = W1c x^T + b1 (bb:
+        // folded into the accumulator init), then ReLU + round -> hb.  fa[0 .. PDA) are read already;
+        // tail_b: the chunk's own phase B follows, its first PDB reads are spread over the last PDA
+        // k-steps (so the ReLU / rounding between the phases overlaps their latency)
+        auto phase_a = [&](const char* wb, const f32x4(&bb)[2], u32x4(&fa)[KS][2], u32x4(&fw)[NT], u32x4(&hb)[RT], auto tail_b) {
             f32x4 h0[RT], h1[RT];
-            {
-                const f32x4 bb0 = *reinterpret_cast<const f32x4*>(pb1 + c * 32 + 4 * g);
-                const f32x4 bb1 = *reinterpret_cast<const f32x4*>(pb1 + c * 32 + 16 + 4 * g);
 #pragma unroll
-                for (int rt = 0; rt < RT; ++rt) {
-                    h0[rt] = bb0;
-                    h1[rt] = bb1;
-                }
+            for (int rt = 0; rt < RT; ++rt) {
+                h0[rt] = bb[0];
+                h1[rt] = bb[1];
             }
-            // Fragments are read ahead of their MFMAs: phase A's two k-steps ahead, phase B's four
-            // fragments ahead, the first four issued during phase A's last two k-steps (so the
-            // ReLU / rounding between the phases overlaps their latency).  The scheduling barriers
-            // keep the compiler from sinking the reads back next to their uses, where each pair of
-            // MFMAs waited for its own LDS round trip: 593-599 -> 566-569 us per batch-28 encoder
-            // FFN, bit-identical (profiles/r06af_ffn_prefetch_ab.txt; 3 or 6 ahead: the same time)
-            auto frag = [&](int f) { return *reinterpret_cast<const u32x4*>(wb + lane * 16 + f * 1024); };
-            constexpr int PDA = 2, PDB = 4;
-            static_assert(KS >= PDA && NT >= PDB, "prefetch depths");
-            u32x4 fa[KS][2], fw[NT];
-#pragma unroll
-            for (int i = 0; i < PDA; ++i) {
-                fa[i][0] = frag(i);
-                fa[i][1] = frag(KS + i);
-            }
-            // phase A: H^T chunk (32 hidden x 32 rows) = W1c x^T + b1
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 if (ks + PDA < KS) {
-                    fa[ks + PDA][0] = frag(ks + PDA);
-                    fa[ks + PDA][1] = frag(KS + ks + PDA);
-                } else {   // phase B's first PDB reads, spread over phase A's last PDA k-steps
+                    read_a(wb, fa, ks + PDA);
+                } else if constexpr (decltype(tail_b)::value) {
                     const int t = ks + PDA - KS;
 #pragma unroll
-                    for (int j = t * PDB / PDA; j < (t + 1) * PDB / PDA; ++j) fw[j] = frag(2 * KS + j);
+                    for (int j = t * PDB / PDA; j < (t + 1) * PDB / PDA; ++j) fw[j] = frag(wb, 2 * KS + j);
                 }
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) {
@@ -685,7 +719,6 @@ __global__ __launch_bounds__(512) void ffn_fused_rt2_kernel(const FfnArgs p, con
             // ReLU as a signed-integer max on the bit pattern (one VALU op; fmaxf on an MFMA
             // result costs a canonicalising max first): the same value for every finite input
             auto relu = [](float v) { return __builtin_bit_cast(float, max(__builtin_bit_cast(int, v), 0)); };
-            u32x4 hb[RT];
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 hb[rt][0] = pack2<T>(relu(h0[rt][0]), relu(h0[rt][1]));
@@ -694,14 +727,70 @@ __global__ __launch_bounds__(512) void ffn_fused_rt2_kernel(const FfnArgs p, con
                 hb[rt][3] = pack2<T>(relu(h1[rt][2]), relu(h1[rt][3]));
             }
             __builtin_amdgcn_sched_barrier(0);
-            // phase B: out^T += W2c H^T, each W2 fragment feeding both row tiles
+        };
+        // phase B of the chunk in slot ws: out^T += W2c H^T, each W2 fragment feeding both row tiles;
+        // fw[0 .. PDB) are read already.  next_a: phase A of hidden chunk cn (slot wn) follows, its
+        // bias and first PDA fragment pairs are read during the last PDB steps
+        auto phase_b = [&](const char* ws, const char* wn, int cn, f32x4(&bb)[2], u32x4(&fa)[KS][2], u32x4(&fw)[NT],
+                           const u32x4(&hb)[RT], auto next_a) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
-                if (nt + PDB < NT) fw[nt + PDB] = frag(2 * KS + nt + PDB);
+                if (nt + PDB < NT) {
+                    fw[nt + PDB] = frag(ws, 2 * KS + nt + PDB);
+                } else if constexpr (decltype(next_a)::value) {
+                    const int t = nt + PDB - NT;
+                    if (t < PDA) read_a(wn, fa, t);
+                    else if (t == PDA) read_bias(cn, bb);
+                }
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) Mma<T>::run(acc[rt][nt], fw[nt], hb[rt]);
                 __builtin_amdgcn_sched_barrier(0);
             }
+        };
+        const int q0 = ti * ncht + PCH;   // the tile's first hidden chunk
+        if (ffn_sched_b_lag(role) == 0) {
+            // role 0, per interval: A(c), ReLU, B(c)
+            for (int c = 0; c < nch; ++c) {
+                ring_step(q0 + c, PCH + c, no_extra{});
+                const char* wb = slot_of(q0 + c);
+                u32x4 fa[KS][2], fw[NT], hb[RT];
+                f32x4 bb[2];
+                read_bias(c, bb);
+#pragma unroll
+                for (int i = 0; i < PDA; ++i) read_a(wb, fa, i);
+                phase_a(wb, bb, fa, fw, hb, std::true_type{});
+                phase_b(wb, wb, 0, bb, fa, fw, hb, std::false_type{});
+            }
+        } else {
+            // role 1, per interval: B(c - 1), A(c), ReLU(c).  hb (and the first PDB W2 fragments of
+            // chunk c - 1, read in front of the barrier: that chunk has been visible since the
+            // barrier before) stay in registers across the barrier, so the MFMAs start as it
+            // releases, while role 0 waits for chunk c's first fragments; each role's ReLU block
+            // then runs beside the partner's MFMAs.  The lag ends with the tile: B of the last chunk
+            // runs behind its A in the same interval (role 0 is in the tile epilogue by then)
+            u32x4 fa[KS][2], fw[NT], hb[RT];
+            f32x4 bb[2];
+            ring_step(q0, PCH, no_extra{});
+            {
+                const char* wb = slot_of(q0);
+                read_bias(0, bb);
+#pragma unroll
+                for (int i = 0; i < PDA; ++i) read_a(wb, fa, i);
+                phase_a(wb, bb, fa, fw, hb, std::false_type{});
+            }
+            for (int c = 1; c < nch; ++c) {
+                const char* wp = slot_of(q0 + c - 1);
+#pragma unroll
+                for (int j = 0; j < PDB; ++j) fw[j] = frag(wp, 2 * KS + j);
+                ring_step(q0 + c, PCH + c, no_extra{});
+                const char* wb = slot_of(q0 + c);
+                phase_b(wp, wb, c, bb, fa, fw, hb, std::true_type{});
+                phase_a(wb, bb, fa, fw, hb, std::false_type{});
+            }
+            const char* wl = slot_of(q0 + nch - 1);
+#pragma unroll
+            for (int j = 0; j < PDB; ++j) fw[j] = frag(wl, 2 * KS + j);
+            phase_b(wl, wl, 0, bb, fa, fw, hb, std::false_type{});
         }
         // ---- tile epilogue (as ffn_fused_kernel): + b2 + residual x, LayerNorm, 16-byte stores ----
 #pragma unroll
@@ -1416,6 +1505,32 @@ extern "C" int kinet_ffn_launch_plan(const int* problem, int cus, int* plan_out)
     const int rec[KINET_FFNPL_FIELDS] = {pl.kernel, pl.tiles, pl.grid, k.block(), k.waves, k.tile_rows,
                                          k.wg_tiles, k.wg_per_cu, ffn_kernel_lds(k)};
     for (int i = 0; i < KINET_FFNPL_FIELDS; ++i) plan_out[i] = rec[i];
+    return KINET_OK;
+}
+
+extern "C" int kinet_ffn_sched(int role, int cnt, int pch, int nch, int q, int half_ops, int* out) {
+    KINET_CHECK_ARG(out != nullptr && (role == 0 || role == 1) && cnt > 0 && pch >= 0 && nch > 0 && half_ops > 0,
+                    "ffn_sched: invalid arguments");
+    const int total = ffn_sched_total(cnt, pch, nch);
+    KINET_CHECK_ARG(q >= -1 && q < total, "ffn_sched: chunk %d outside [-1, %d)", q, total);
+    for (int i = 0; i < KINET_FFNS_FIELDS; ++i) out[i] = -1;
+    out[KINET_FFNS_TOTAL] = total;
+    out[KINET_FFNS_BARRIERS] = ffn_sched_barriers(role, cnt, pch, nch);
+    auto put = [&](int n_field, int field, const FfnHalfList& l) {
+        out[n_field] = l.n;
+        for (int i = 0; i < l.n; ++i) {
+            out[field + 2 * i] = l.e[i].chunk;
+            out[field + 2 * i + 1] = l.e[i].half;
+        }
+    };
+    put(KINET_FFNS_N_ISSUE, KINET_FFNS_ISSUE, ffn_sched_issue(q, total));
+    out[KINET_FFNS_N_EARLY] = out[KINET_FFNS_N_READ] = 0;
+    if (q < 0) return KINET_OK;
+    out[KINET_FFNS_BARRIER] = q;
+    out[KINET_FFNS_SLOT] = ffn_sched_slot(q);
+    out[KINET_FFNS_VMCNT] = ffn_sched_vmcnt(q, total, half_ops);
+    put(KINET_FFNS_N_EARLY, KINET_FFNS_EARLY, ffn_sched_early_reads(role, q, pch, nch));
+    put(KINET_FFNS_N_READ, KINET_FFNS_READ, ffn_sched_reads(role, q, pch, nch));
     return KINET_OK;
 }
 
